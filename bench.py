@@ -10,7 +10,15 @@ A "step" is one apply of the stencil over the whole 512^3 grid on synthetic inpu
 resident in HBM.  With N > 1 the SAME 512^3 grid is split over the ranks (strong scaling); a step is
 then halo exchange (RCCL send/recv) + kernel(s), see DESIGN.md section 6.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line (see DESIGN.md "Measurement"):
+A plain run sets up, warms up, times the --steps steps and prints the line: `value` (GLUPS over the timed steps, wall clock
+between barriers), `ms_per_step`, `pct_hbm_roofline` and the configuration.  `--dump-outputs DIR` also writes what the last
+timed step computed (see dump_outputs).  Everything else -- the objects below, the copy ceilings, the host cost per call, the
+allocator variants, the other kernels, the memory-group report, the summary and, at N > 1, the time steppers -- is measured
+with `--full` only:
+
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
+
+Extra objects in the line with --full (see DESIGN.md "Measurement"):
   roofline      HBM roofline of the dominant kernel: algorithmic bytes (16 B per lattice update) / average launch
                 duration measured with HIP events on the launch stream over K back-to-back launches (median and
                 minimum of a second, per-launch-event pass are reported next to it), against the 8.0 TB/s nominal peak; `traffic` = HBM bytes per launch from the
@@ -143,6 +151,37 @@ class Watchdog:
                             f"exiting with status 3\n".encode())
         finally:
             os._exit(status)
+
+
+DUMP_SAMPLES = 1 << 22  # positions of out_sample.npy: 32 MiB of fp64
+DUMP_SEED = 4096
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(field, directory) -> dict:
+    """--dump-outputs: what a caller of the timed path receives -- the output field of the last timed step -- as .npy files of
+    at most 64 MB together.  `out_sample.npy`: the field at DUMP_SAMPLES positions drawn with a fixed seed over its whole shape
+    (halo included); `out_k<k>.npy`: its first, middle and last level, whole.  The positions depend only on the field's shape,
+    and the inputs only on the seed of the workload, so two builds run with the same arguments compare value for value.
+    Returns {file name: bytes}."""
+    import torch
+
+    t = field.tensor
+    assert t.dtype in (torch.float32, torch.float64), t.dtype
+    shape = tuple(t.shape)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = [torch.from_numpy(rng.integers(0, n, DUMP_SAMPLES)).to(t.device) for n in shape]
+    arrays = {"out_sample": t[idx[0], idx[1], idx[2]]}
+    for k in sorted({0, shape[2] // 2, shape[2] - 1}):
+        arrays[f"out_k{k}"] = t[:, :, k]
+    host = {name: np.ascontiguousarray(a.cpu().numpy()) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    out = pathlib.Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in host.items():
+        np.save(out / f"{name}.npy", a)
+    return {f"{name}.npy": a.nbytes for name, a in host.items()}
 
 
 def copy_ceiling_gbs(steps: int = 10, nbytes: int = 1 << 30, classes=None) -> float:
@@ -717,7 +756,20 @@ def main() -> None:
                          "(512/PI x 512/PJ x 512), periodic along every cut axis (W / E neighbours too)")
     ap.add_argument("--selfloop-ranks", type=int, default=1,
                     help="with --dist-selfloop and lap512: shrink J to 512/N, the per-rank share of an N-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the dominant kernel's roofline from a pass of its own, "
+                         "the copy ceilings, the host cost per call, the allocator variants, the other kernels, the memory-group "
+                         "report, the CPU baseline, the summary and (N > 1) the time steppers.  Off: set up, warm up, time --steps "
+                         "steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed to DIR/<name>.npy (lap512 at N = 1 only): "
+                         "out_sample.npy = the output field at %d seeded positions, out_k<k>.npy = its first, middle and last "
+                         "level (fp64, %d MB at most)" % (DUMP_SAMPLES, DUMP_LIMIT_BYTES // 1_000_000))
     args = ap.parse_args()
+    if args.dump_outputs is not None and (args.workload != "lap512" or args.dist_selfloop
+                                          or int(os.environ.get("WORLD_SIZE", "1")) > 1
+                                          or os.environ.get("GT4MI_BENCH_FORCE_DISTRIBUTED", "0") == "1"):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the single-GPU lap512 workload only")
 
     import numpy as np
     import torch
@@ -803,9 +855,11 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_output = None  # lap512 at N = 1: () -> the output field of the last timed step (--dump-outputs)
+
     def measure(step, kernel_step, local_domain, total_lups, config, phase=""):
-        """Warm-up, EXACTLY --steps timed steps between barriers (slowest rank), the dominant kernel's launch durations from
-        HIP events -> the contract's line (without the informational sections)."""
+        """Warm-up, EXACTLY --steps timed steps between barriers (slowest rank), --dump-outputs, and with --full the dominant
+        kernel's launch durations from HIP events -> the contract's line (without the informational sections)."""
         dog.arm(120 + 2.0 * args.warmup, "warm-up steps" + phase)
         for i in range(args.warmup):
             step(i)
@@ -820,18 +874,12 @@ def main() -> None:
             t = torch.tensor([elapsed], dtype=torch.float64, device=ctx.get("collective_device", "cuda"))
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        # dominant kernel: launch durations from HIP events on the launch stream (>= 50 launches when --steps allows)
-        dog.arm(300, "kernel timing" + phase)
-        torch.cuda.synchronize()
-        for i in range(3):
-            kernel_step(i)
-        torch.cuda.synchronize()
-        kt = _time_launches(kernel_step, max(args.steps, 50))  # (SURVEY.md section 8d: >= 50 timed launches)
-        kernel_ms = kt["mean"]
-        local_lups = float(np.prod(local_domain))
-        achieved = bytes_per_lup * local_lups / (kernel_ms * 1e-3) / 1e9
+        if args.dump_outputs is not None and last_output is not None:
+            dog.arm(120, "--dump-outputs")
+            written = dump_outputs(last_output(), args.dump_outputs)
+            print(f"bench.py: wrote {', '.join(written)} ({sum(written.values()) / 1e6:.1f} MB) to {args.dump_outputs}", file=sys.stderr)
         glups = total_lups * args.steps / elapsed / 1e9
-        return {
+        line = {
             "metric": metric,
             "value": round(glups, 2),
             "unit": "GLUPS",
@@ -846,6 +894,22 @@ def main() -> None:
             "data": "synthetic",
             "config": config,
             "pct_hbm_roofline": round(100.0 * glups * bytes_per_lup / (PEAK_GBS * n_gpus), 2),
+        }
+        if not args.full:
+            line["device"] = _lib.device_info()
+            return line
+        # dominant kernel: launch durations from HIP events on the launch stream (>= 50 launches when --steps allows)
+        dog.arm(300, "kernel timing" + phase)
+        torch.cuda.synchronize()
+        for i in range(3):
+            kernel_step(i)
+        torch.cuda.synchronize()
+        kt = _time_launches(kernel_step, max(args.steps, 50))  # (SURVEY.md section 8d: >= 50 timed launches)
+        kernel_ms = kt["mean"]
+        local_lups = float(np.prod(local_domain))
+        achieved = bytes_per_lup * local_lups / (kernel_ms * 1e-3) / 1e9
+        return {
+            **line,
             "roofline": {
                 "bound": "hbm",
                 "kernel": kernel_name,
@@ -919,6 +983,7 @@ def main() -> None:
 
         local_domain = GRID
         kernel_step = step
+        last_output = lambda: pairs[(args.steps - 1) % len(pairs)][1]  # noqa: E731
         config = {"workload": "fp64 5-point Laplacian 512x512x512 (examples/lap_cartesian_vs_next.ipynb cell 7), "
                               "origin (1,1,0), hip:mi300 storage layout", "grid": list(GRID), "decomposition": "1x1",
                   "call_path": "FrozenStencil",
@@ -930,7 +995,7 @@ def main() -> None:
 
     line = measure(step, kernel_step, local_domain, total_lups, config)
     headline = args.workload == "lap512" and not decomposed
-    if headline:
+    if headline and args.full:
         line["roofline"]["traffic"], line["roofline"]["traffic_source"] = _committed_traffic("lap5_f64_512")
     if decomposed:
         line.update(decomposed_line_keys(extras.get("proof"), bool(extras.get("transport_fallback")), n_gpus, None))
@@ -945,16 +1010,20 @@ def main() -> None:
             config["direct_transport_status"] = {"timed_out": any(st["timed_out"] for st in status),
                                                  "exchanges": sum(st["exchanges"] for st in status)}
     timestep = None
-    _test_hang(dog, "informational")
-    if callable(extras.get("timestep")):  # collective: every rank runs it
-        dog.arm(420, "communication-avoiding time steppers (informational)")
-        try:
-            timestep = extras["timestep"]()
-        except Exception as ex:
-            print(f"rank {rank}: time-stepper measurement failed ({ex!r})", file=sys.stderr)
+    if args.full:  # (every rank has the same arguments)
+        _test_hang(dog, "informational")
+        if callable(extras.get("timestep")):  # collective: every rank runs it
+            dog.arm(420, "communication-avoiding time steppers (informational)")
+            try:
+                timestep = extras["timestep"]()
+            except Exception as ex:
+                print(f"rank {rank}: time-stepper measurement failed ({ex!r})", file=sys.stderr)
+    # Everything below the headline except the decomposed runs' keys comes with --full only: a plain run prints the line as it is.
+    informational = headline and args.full
     if rank == 0:
-        dog.arm(900, "informational kernels and CPU baseline")
-        if not decomposed:
+        if args.full:
+            dog.arm(900, "informational kernels and CPU baseline")
+        if args.full and not decomposed:
             # what a plain streaming copy reaches on this device in this run (not the bar, the context)
             line["roofline"]["measured_copy_gbs"] = round(copy_ceiling_gbs(), 1)
             if headline:  # the same copy with its two buffers in one memory group and in two (None: no second group in reach)
@@ -965,12 +1034,12 @@ def main() -> None:
                     print(f"copy ceiling by memory groups failed: {ex!r}", file=sys.stderr)
         if decomposed:
             line.update(decomposed_line_keys(extras.get("proof"), bool(extras.get("transport_fallback")), n_gpus, timestep))
-        if headline:
+        if informational:
             try:
                 line["host_cost_per_call"] = host_cost_per_call(lap)
             except Exception as ex:
                 print(f"host_cost_per_call failed: {ex!r}", file=sys.stderr)
-        if headline and not args.no_allocator_variants:
+        if informational and not args.no_allocator_variants:
             # What a drop-in user gets: the headline kernel on fields from the storage allocator AT ITS
             # DEFAULTS (6 plain candidates per search, no spacers, no parked neighbours, no role hints: plain gt_storage.empty) and
             # with the memory-group placer OFF -- 5 + 20 launches each, outside the contract's timed steps.
@@ -981,25 +1050,25 @@ def main() -> None:
                 line.update(allocator_variants(lap, frozen, shape, args.steps))
             except Exception as ex:
                 print(f"allocator_variants failed: {ex!r}", file=sys.stderr)
-        if headline and not args.no_other_kernels:
+        if informational and not args.no_other_kernels:
             try:
                 line["other_kernels"] = other_kernels()
             except Exception as ex:
                 line["other_kernels"] = None
                 print(f"other_kernels failed: {ex!r}", file=sys.stderr)
-        if headline:
+        if informational:
             from gt4py_amd.storage import placement as _placement
 
             groups = _placement.report() or {}  # what the allocator's placer did for the big fields of this run (per-field records:
             groups.pop("fields", None)          # 3 KB -- left out of the line; placement.report() has them)
             line["memory_groups"] = groups
-        if headline and not args.no_cpu_baseline:
+        if informational and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as ex:  # the baseline must never take the GPU number down with it
                 line["cpu_baseline"] = None
                 print(f"cpu_baseline failed: {ex!r}", file=sys.stderr)
-        if headline:
+        if informational:
             # LAST key of the line (a record that keeps only the tail of a long line keeps this): every BASELINE config's figure
             ok = line.get("other_kernels") or {}
             line["summary"] = {"lap5_f64_512": {"glups": line["value"], "frac": line["roofline"]["frac"],

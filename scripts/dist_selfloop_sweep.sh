@@ -15,13 +15,13 @@ for WG in 0 4 3 2 1; do
   for CH in default 8 32; do
     if [ "$CH" = default ]; then unset NCCL_MIN_P2P_NCHANNELS NCCL_MAX_P2P_NCHANNELS; else export NCCL_MIN_P2P_NCHANNELS=$CH NCCL_MAX_P2P_NCHANNELS=$CH; fi
     export GT4MI_DIST_INTERIOR_WG_PER_CU=$WG
-    timeout 200 python3 bench.py --workload hdiff2048 --dist-selfloop --steps 100 --warmup 20 2>/dev/null | line "hdiff2048 wg_per_cu=$WG p2p_channels=$CH" >> "$LOG"
+    timeout 200 python3 bench.py --workload hdiff2048 --dist-selfloop --steps 100 --warmup 20 --full 2>/dev/null | line "hdiff2048 wg_per_cu=$WG p2p_channels=$CH" >> "$LOG"
   done
 done
 unset NCCL_MIN_P2P_NCHANNELS NCCL_MAX_P2P_NCHANNELS
 for WG in 0 4 2 1; do
   export GT4MI_DIST_INTERIOR_WG_PER_CU=$WG
-  timeout 300 python3 bench.py --dist-selfloop --selfloop-ranks 8 --steps 200 --warmup 20 2>/dev/null | line "lap512 share of 8 wg_per_cu=$WG" >> "$LOG"
+  timeout 300 python3 bench.py --dist-selfloop --selfloop-ranks 8 --steps 200 --warmup 20 --full 2>/dev/null | line "lap512 share of 8 wg_per_cu=$WG" >> "$LOG"
 done
 unset GT4MI_DIST_INTERIOR_WG_PER_CU
 cd /tmp && export TMPDIR=/tmp

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; cd $R
 export GT4MI_BENCH_ONE_DEVICE=1 GT4MI_BENCH_CALIBRATION_SECONDS=20 GT4MI_BENCH_DIRECT_CALIBRATION_SECONDS=30 GT4MI_BENCH_INFORMATIONAL_SECONDS=15
 export GT4MI_BENCH_DIRECT_TIMEOUT_MS=${GT4MI_BENCH_DIRECT_TIMEOUT_MS:-120000} GT4MI_BENCH_VERBOSE=1
 PORT=$(python3 -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
-time timeout 1500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $N --steps 20 --warmup 3 --workload $W > $OUT/bench_one_device_${W}_$N.json 2> $OUT/bench_one_device_${W}_$N.stderr
+time timeout 1500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $N --steps 20 --warmup 3 --full --workload $W > $OUT/bench_one_device_${W}_$N.json 2> $OUT/bench_one_device_${W}_$N.stderr
 echo "status $?"
 python3 - $OUT/bench_one_device_${W}_$N.json <<'PY'
 import json, sys

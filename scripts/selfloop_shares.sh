@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 export GT4MI_BENCH_TIMESTEP=0
 for G in $GRIDS; do
-  python3 "$R/bench.py" --dist-selfloop --selfloop-grid $G --steps 200 --warmup 20 > "$OUT/${TAG}_bench_lap512_selfloop_share_${G}.json" 2> "$OUT/${TAG}_bench_lap512_selfloop_share_${G}.stderr"
+  python3 "$R/bench.py" --dist-selfloop --selfloop-grid $G --steps 200 --warmup 20 --full > "$OUT/${TAG}_bench_lap512_selfloop_share_${G}.json" 2> "$OUT/${TAG}_bench_lap512_selfloop_share_${G}.stderr"
   python3 - "$OUT/${TAG}_bench_lap512_selfloop_share_${G}.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -338,3 +338,49 @@ def test_the_decomposed_workloads_live_in_the_package_and_bench_re_exports_them(
     finally:
         workloads.GRID, workloads.HDIFF_SHARE, workloads.HDIFF_GLOBAL = before
     assert bench.GRID == (512, 512, 512)
+
+
+def test_dump_outputs_writes_a_seeded_sample_and_three_levels_of_the_output_field(tmp_path):
+    """`--dump-outputs DIR`: the field the last timed step wrote, as .npy files of at most 64 MB together -- the same positions on
+    every run (they depend on the field's shape only), so that two builds run with the same arguments compare value for value."""
+    import numpy as np
+    import torch
+
+    class Field:
+        def __init__(self, t):
+            self.tensor = t
+
+    shape = (9, 7, 6)
+    t = torch.arange(np.prod(shape), dtype=torch.float64).reshape(shape)
+    written = bench.dump_outputs(Field(t), tmp_path / "a")
+    assert set(written) == {"out_sample.npy", "out_k0.npy", "out_k3.npy", "out_k5.npy"}
+    assert sum(written.values()) <= 64_000_000
+    files = {name: np.load(tmp_path / "a" / name) for name in written}
+    assert all(a.dtype == np.float64 for a in files.values())
+    for k in (0, 3, 5):
+        assert np.array_equal(files[f"out_k{k}.npy"], t[:, :, k].numpy())
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    i, j, k = (rng.integers(0, n, bench.DUMP_SAMPLES) for n in shape)
+    assert files["out_sample.npy"].shape == (bench.DUMP_SAMPLES,) and np.array_equal(files["out_sample.npy"], t.numpy()[i, j, k])
+    bench.dump_outputs(Field(t.clone()), tmp_path / "b")
+    assert all(np.array_equal(files[name], np.load(tmp_path / "b" / name)) for name in written)
+    # a float32 field stays float32; the full-size field of the headline stays under the limit
+    bench.dump_outputs(Field(t.float()), tmp_path / "c")
+    assert np.load(tmp_path / "c" / "out_k0.npy").dtype == np.float32 and np.load(tmp_path / "c" / "out_sample.npy").dtype == np.float32
+    grid = (bench.GRID[0] + 2, bench.GRID[1] + 2, bench.GRID[2])
+    assert 8 * (bench.DUMP_SAMPLES + 3 * grid[0] * grid[1]) <= bench.DUMP_LIMIT_BYTES <= 64_000_000
+
+
+def test_dump_outputs_is_refused_before_any_work_where_it_is_not_implemented():
+    """Only the single-GPU lap512 line dumps its outputs; anything else says so at once (no GPU, no torch needed to find out)."""
+    for extra in (["--workload", "hdiff2048"], ["--dist-selfloop"]):
+        proc = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "1", "--warmup", "0", "--dump-outputs", "unused", *extra],
+                              capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+        assert proc.returncode != 0 and "--dump-outputs is implemented for the single-GPU lap512 workload only" in proc.stderr, extra
+        assert not (ROOT / "unused").exists()
+
+
+def test_full_is_an_option_of_its_own_and_off_by_default():
+    """A plain run measures only the headline; `--full` adds the informational sections (tests and scripts that read them pass it)."""
+    proc = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert proc.returncode == 0 and "--full" in proc.stdout and "--dump-outputs DIR" in proc.stdout

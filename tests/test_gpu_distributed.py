@@ -864,7 +864,7 @@ def test_bench_n_gpu_code_path_with_a_world_of_one(workload, tmp_path):
         port = sock.getsockname()[1]
     env = dict(os.environ, GT4MI_BENCH_FORCE_DISTRIBUTED="1")
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                           "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2",
+                           "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--full",
                            "--workload", workload], env=env, capture_output=True, text=True, timeout=900, cwd=str(root))
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -921,7 +921,7 @@ def test_bench_prints_what_it_measured_when_a_later_phase_hangs(workload, phase,
         port = sock.getsockname()[1]
     env = dict(os.environ, GT4MI_BENCH_FORCE_DISTRIBUTED="1", GT4MI_BENCH_TEST_HANG=phase, GT4MI_BENCH_DEADLINE_SCALE="0.5")
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                           "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2",
+                           "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--full",
                            "--workload", workload], env=env, capture_output=True, text=True, timeout=900, cwd=str(root))
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -1478,7 +1478,7 @@ def test_bench_n_gpu_code_path_with_real_ranks_on_one_device(workload, ranks, tm
                GT4MI_BENCH_INFORMATIONAL_SECONDS="10", GT4MI_BENCH_DIRECT_TIMEOUT_MS="60000")
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
                            "127.0.0.1", "--master-port", str(port), str(root / "bench.py"), "--gpus", str(ranks), "--steps", "10", "--warmup",
-                           "2", "--workload", workload], env=env, capture_output=True, text=True, timeout=1200, cwd=str(root))
+                           "2", "--full", "--workload", workload], env=env, capture_output=True, text=True, timeout=1200, cwd=str(root))
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, proc.stdout[-2000:]  # ONE JSON line, from rank 0

@@ -457,7 +457,7 @@ def test_an_empty_axis_is_a_call_that_writes_nothing():
 
 @pytest.mark.multiprocess
 def test_the_headline_line_of_bench_py_carries_what_the_contract_and_the_verdicts_ask_for():
-    """`python bench.py` at N = 1 (short: 3 steps, no CPU baseline, no other kernels): ONE JSON line on stdout with the contract's keys,
+    """`python bench.py --full` at N = 1 (short: 3 steps, no CPU baseline, no other kernels): ONE JSON line on stdout with the contract's keys,
     the `roofline` object, the figures a drop-in user gets (`value_default_allocator`, `value_allocator_off`), and -- as the LAST key, so
     that a record which keeps only the tail of a long line keeps it -- the `summary` of every config's figure."""
     import json
@@ -467,7 +467,7 @@ def test_the_headline_line_of_bench_py_carries_what_the_contract_and_the_verdict
     import sys
 
     root = pathlib.Path(__file__).resolve().parent.parent
-    proc = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-kernels"],
+    proc = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-kernels"],
                           capture_output=True, text=True, timeout=600, cwd=str(root), env=dict(os.environ))
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
@@ -483,3 +483,54 @@ def test_the_headline_line_of_bench_py_carries_what_the_contract_and_the_verdict
     assert line["value_default_allocator"] > 0 and line["value_allocator_off"] > 0 and "allocator_note" in line
     assert list(line)[-1] == "summary" and line["summary"]["lap5_f64_512"]["glups"] == line["value"]
     assert line["memory_groups"]["enabled"] in (True, False) and "fields" not in line["memory_groups"]
+
+
+@pytest.mark.multiprocess
+def test_a_plain_bench_run_times_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """`python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` without --full: ONE JSON line with the contract's keys and
+    none of the informational sections, and DIR holds the output field of the last timed step -- a seeded sample of it and three whole
+    levels, fp64, at most 64 MB together -- bit-identical to the oracle's Laplacian of the bench's seeded input."""
+    import json
+    import os
+    import pathlib
+    import subprocess
+    import sys
+
+    import torch
+
+    import bench
+    from oracle import ref_numpy as R
+
+    root = pathlib.Path(__file__).resolve().parent.parent
+    dump = tmp_path / "dump"
+    proc = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+                          capture_output=True, text=True, timeout=600, cwd=str(root), env=dict(os.environ))
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key, want in (("n_gpus", 1), ("steps", 3), ("warmup", 1), ("higher_is_better", True), ("dtype", "f64"), ("unit", "GLUPS")):
+        assert line[key] == want, key
+    assert "512" in line["metric"] and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] - 512 ** 3 / 1e6) / (512 ** 3 / 1e6) < 1e-3  # GLUPS x ms per step = the grid
+    assert not {"roofline", "other_kernels", "cpu_baseline", "summary", "value_by_events", "host_cost_per_call", "memory_groups"} & set(line)
+
+    files = {p.name: np.load(p) for p in dump.glob("*.npy")}
+    shape = (bench.GRID[0] + 2, bench.GRID[1] + 2, bench.GRID[2])
+    levels = sorted({0, shape[2] // 2, shape[2] - 1})
+    assert set(files) == {"out_sample.npy", *(f"out_k{k}.npy" for k in levels)}
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64_000_000
+    # the bench's input of the pair the last of 3 timed steps wrote (pairs[2 % 2], the first one drawn: workloads._device_fields)
+    gen = torch.Generator(device="cuda").manual_seed(1337)
+    inp = (torch.rand(shape, dtype=torch.float64, device="cuda", generator=gen) * 2 - 1).cpu().numpy()
+    for k in levels:
+        want = np.zeros((shape[0], shape[1], 1))
+        R.laplacian(np.ascontiguousarray(inp[:, :, k:k + 1]), want)
+        assert np.array_equal(files[f"out_k{k}.npy"], want[:, :, 0]), k
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    i, j, k = (rng.integers(0, n, bench.DUMP_SAMPLES) for n in shape)
+    inner = (i > 0) & (i < shape[0] - 1) & (j > 0) & (j < shape[1] - 1)
+    a, b, c = i[inner], j[inner], k[inner]
+    want = np.zeros(bench.DUMP_SAMPLES)  # (the halo of `out` is never written: zeros)
+    want[inner] = (-4.0 * inp[a, b, c]) + inp[a - 1, b, c] + inp[a + 1, b, c] + inp[a, b - 1, c] + inp[a, b + 1, c]
+    assert np.array_equal(files["out_sample.npy"], want)
