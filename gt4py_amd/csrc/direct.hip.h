@@ -151,21 +151,6 @@ __device__ __forceinline__ void direct_block(U* field, int64_t si, int64_t sj, i
             }
         }
     };
-#ifdef GT4MI_DIRECT_ROUND3_LOAD_ORDER
-    // (evidence build only, `make r3order`: the receive side as rounds 2-3 had it -- payload loads first, one look at the flag
-    // while they are in flight, a reload only if that look said "not yet"; profiles/r4_two_rank_direct_loop.log)
-    __shared__ int first_look;
-    load_all();
-    if (threadIdx.x == 0) {
-        first_look = (int)(__hip_atomic_load(d.wait_flag[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - d.wait_value[m]) >= 0;
-        ready = direct_wait(d.wait_flag[m], d.wait_value[m], d.timeout_ticks, d.error) ? 1 : 0;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (!ready) return;
-    if constexpr (!PACK)
-        if (!first_look) load_all();
-#else
     if constexpr (PACK) load_all();  // my own field: in flight while lane 0 looks at the flag
     if (threadIdx.x == 0) ready = direct_wait(d.wait_flag[m], d.wait_value[m], d.timeout_ticks, d.error) ? 1 : 0;
     __syncthreads();
@@ -176,7 +161,6 @@ __device__ __forceinline__ void direct_block(U* field, int64_t si, int64_t sj, i
     __atomic_signal_fence(__ATOMIC_ACQUIRE);
     if (d.fenced) direct_acquire_fence();
     if constexpr (!PACK) load_all();  // what the peer stored before it raised the flag
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the asm loads of the unpack side are invisible to the compiler)
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {

@@ -22,19 +22,16 @@
 
 namespace gt4mi {
 // How a fused distributed step is laid out on the two streams, and how far the interior kernel is throttled while the
-// exchange runs next to it: the plan's options (gt4mi_halo_plan_set_option), else the environment (experiments), else the
-// entry point's default -- measured on the 1-GPU self-loop, profiles/r3_dist_*_timeline*.txt.
+// exchange runs next to it: the plan's options (gt4mi_halo_plan_set_option), else the entry point's default -- measured on
+// the 1-GPU self-loop, profiles/r3_dist_*_timeline*.txt.
 inline int plan_schedule(const gt4mi_halo_plan* plan, int fallback) {
-    static const int env = env_int("GT4MI_DIST_SCHEDULE", -1);
-    return plan->schedule >= 0 ? plan->schedule : (env >= 0 ? env : fallback);
+    return plan->schedule >= 0 ? plan->schedule : fallback;
 }
 inline int plan_edge_columns(const gt4mi_halo_plan* plan, int fallback) {
-    static const int env = env_int("GT4MI_DIST_EDGE_COLUMNS", -1);
-    return plan->edge_columns >= 0 ? plan->edge_columns : (env >= 0 ? env : fallback);
+    return plan->edge_columns >= 0 ? plan->edge_columns : fallback;
 }
 inline int plan_interior_wg_per_cu(const gt4mi_halo_plan* plan, int fallback) {
-    static const int env = env_int("GT4MI_DIST_INTERIOR_WG_PER_CU", -1);
-    return plan->interior_wg_per_cu >= 0 ? plan->interior_wg_per_cu : (env >= 0 ? env : fallback);
+    return plan->interior_wg_per_cu >= 0 ? plan->interior_wg_per_cu : fallback;
 }
 }  // namespace gt4mi
 

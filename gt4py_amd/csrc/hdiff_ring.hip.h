@@ -134,7 +134,7 @@ inline int hdiff_launch_ring(const View<const T>& in, const View<T>& out, const 
     if (hi_i > 0 && dj - lo_j - hi_j > 0) boxes[n++] = {1, di - hi_i, lo_j, hi_i, dj - lo_j - hi_j};
     if (n == 0 || dk == 0) return GT4MI_OK;
     const bool contiguous = in.si == 1 && out.si == 1 && (!COEFF_FIELD || cf.si == 1);
-    const bool fits = contiguous && !point_per_thread && hdiff_jmarch_enabled();  // point_per_thread: `coeff` IS `out_field` (hdiff.hip.h)
+    const bool fits = contiguous && !point_per_thread;  // point_per_thread: `coeff` IS `out_field` (hdiff.hip.h)
     for (int m = 0; m < n; ++m)
         if (boxes[m].kind == 1 && boxes[m].ei != 2) boxes[m].kind = 2;  // not the 2-column shape: J-march strips
     if (!fits) {

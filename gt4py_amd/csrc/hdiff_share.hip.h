@@ -33,19 +33,30 @@
 
 namespace gt4mi {
 
+// Rows per wave / waves per workgroup (MI355X; profiles/r6_hdiff_lds_tile.txt).  4 x 4 is the fastest shape for both BASELINE
+// configurations AND the one with the least memory-side traffic (1.05-1.06 x; 6 rows x 4 waves: 1.12 x, 4 rows x 8 waves: 1.07-1.09 x);
+// 8, 12 and 16 waves lose 5-30 % for float32 fields with float64 internals (128 registers there: the barrier then spans most of a CU).
+struct HdiffShareTuning {
+    static constexpr int LJ = 4;
+    static constexpr int NW = 4;
+    // workgroups per XCD run: 2 (1, 2 and no remap are within 0.3 %; 4 -- the J-march's value -- is 0.5-2 % behind, 8 and 16 2-4 %)
+    static constexpr int XCDG = 2;
+    static constexpr int MINW = 4;
+};
+
 // `lead`: the views' origins lie that many items past a 16-byte boundary (all three alike, hdiff_common_lead): the lanes start
 // `lead` columns further left, which makes every lane's vector naturally aligned.
-template <typename T, typename W, typename PW, bool LIMITER, bool COEFF_FIELD, int VEC, int LJ, int NW, int XCDG, int MINW>
-__global__ void __launch_bounds__(NW * 64, MINW)
+template <typename T, typename W, typename PW, bool LIMITER, bool COEFF_FIELD>
+__global__ void __launch_bounds__(HdiffShareTuning::NW * 64, HdiffShareTuning::MINW)
 hdiff_share_kernel(View<const T> in, View<T> out, View<const T> cf, PW coeff_scalar, int dI, int dJ, unsigned waves_i,
                    unsigned groups_j, int lead) {
-    static_assert(VEC * sizeof(T) == 16 && LJ >= 4, "16-byte lanes; a wave publishes two rows at either end of its block");
+    constexpr int VEC = 16 / sizeof(T), LJ = HdiffShareTuning::LJ, NW = HdiffShareTuning::NW, XCDG = HdiffShareTuning::XCDG;
+    static_assert(LJ >= 4, "a wave publishes two rows at either end of its block");
     using V = typename VecT<T, VEC>::type;
     __shared__ __attribute__((aligned(16))) char shared_rows[NW * 4 * 1024];
 
     // workgroups ordered along J, then I, then K; runs of XCDG of them share an XCD (see lap5.hip.h)
-    unsigned wg = blockIdx.x;
-    if constexpr (XCDG > 0) wg = xcd_remap_grouped<(unsigned)XCDG>(wg, gridDim.x);
+    const unsigned wg = xcd_remap_grouped<(unsigned)XCDG>(blockIdx.x, gridDim.x);
     const unsigned jg = wg % groups_j, column = wg / groups_j;
     const unsigned wi = column % waves_i, k = column / waves_i;
     const unsigned lane = threadIdx.x & 63;
@@ -235,22 +246,10 @@ hdiff_share_kernel(View<const T> in, View<T> out, View<const T> cf, PW coeff_sca
     else body(std::false_type{});
 }
 
-// Rows per wave / waves per workgroup (MI355X; profiles/r6_hdiff_lds_tile.txt).  4 x 4 is the fastest shape for both BASELINE
-// configurations AND the one with the least memory-side traffic (1.05-1.06 x; 6 rows x 4 waves: 1.12 x, 4 rows x 8 waves: 1.07-1.09 x);
-// 8, 12 and 16 waves lose 5-30 % for float32 fields with float64 internals (128 registers there: the barrier then spans most of a CU).
-template <typename T>
-struct HdiffShareTuning {
-    static constexpr int LJ = 4;
-    static constexpr int NW = 4;
-    // workgroups per XCD run: 2 (1, 2 and no remap are within 0.3 %; 4 -- the J-march's value -- is 0.5-2 % behind, 8 and 16 2-4 %)
-    static constexpr int XCDG = 2;
-    static constexpr int XCDG_ALT = 4;
-    static constexpr int MINW = 4;
-};
-
-template <typename T, typename W, typename PW, bool LIMITER, bool COEFF_FIELD, int VEC, int LJ, int NW, int XCDG, int MINW>
-inline int hdiff_launch_share_shape(const View<const T>& in, const View<T>& out, const View<const T>& cf, PW coeff_scalar,
-                                    const int64_t d[3], hipStream_t stream, int lead) {
+template <typename T, typename W, typename PW, bool LIMITER, bool COEFF_FIELD>
+inline int hdiff_launch_share(const View<const T>& in, const View<T>& out, const View<const T>& cf, PW coeff_scalar,
+                              const int64_t d[3], hipStream_t stream, int lead) {
+    constexpr int VEC = 16 / sizeof(T), LJ = HdiffShareTuning::LJ, NW = HdiffShareTuning::NW;
     const unsigned waves_i = (unsigned)cdiv(d[0] + lead, (int64_t)62 * VEC);
     const unsigned groups_j = (unsigned)cdiv(d[1], (int64_t)LJ * NW);
     const int64_t nblocks = (int64_t)waves_i * groups_j * d[2];
@@ -259,22 +258,9 @@ inline int hdiff_launch_share_shape(const View<const T>& in, const View<T>& out,
     // share a CU (common.hip.h lds_for_workgroups_per_cu).  This kernel has static LDS of its own: only the rest is requested.
     constexpr unsigned own_lds = NW * 4 * 1024;
     const unsigned throttle = launch_dynamic_lds() > own_lds ? launch_dynamic_lds() - own_lds : 0u;
-    hipLaunchKernelGGL((hdiff_share_kernel<T, W, PW, LIMITER, COEFF_FIELD, VEC, LJ, NW, XCDG, MINW>), dim3((unsigned)nblocks),
-                       dim3(NW * 64), throttle, stream, in, out, cf, coeff_scalar, (int)d[0], (int)d[1], waves_i, groups_j, lead);
+    hipLaunchKernelGGL((hdiff_share_kernel<T, W, PW, LIMITER, COEFF_FIELD>), dim3((unsigned)nblocks), dim3(NW * 64), throttle, stream,
+                       in, out, cf, coeff_scalar, (int)d[0], (int)d[1], waves_i, groups_j, lead);
     return GT4MI_OK;
-}
-
-template <typename T, typename W, typename PW, bool LIMITER, bool COEFF_FIELD, int VEC>
-inline int hdiff_launch_share(const View<const T>& in, const View<T>& out, const View<const T>& cf, PW coeff_scalar,
-                              const int64_t d[3], hipStream_t stream, int lead) {
-    using Tu = HdiffShareTuning<T>;
-    // GT4MI_HDIFF_SHARE_XCD=<runs>: the other measured XCD run length, for A/B runs on ONE box in the product's call path
-    static const int runs = env_int("GT4MI_HDIFF_SHARE_XCD", Tu::XCDG);
-    if (runs != Tu::XCDG)
-        return hdiff_launch_share_shape<T, W, PW, LIMITER, COEFF_FIELD, VEC, Tu::LJ, Tu::NW, Tu::XCDG_ALT, Tu::MINW>(in, out, cf, coeff_scalar, d,
-                                                                                                                 stream, lead);
-    return hdiff_launch_share_shape<T, W, PW, LIMITER, COEFF_FIELD, VEC, Tu::LJ, Tu::NW, Tu::XCDG, Tu::MINW>(in, out, cf, coeff_scalar, d,
-                                                                                                         stream, lead);
 }
 
 }  // namespace gt4mi

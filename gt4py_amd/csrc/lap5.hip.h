@@ -57,7 +57,7 @@ __device__ __forceinline__ T lap5_expr(T c, T w, T e, T s, T n) {
 // is not on a 16-byte boundary, or whose width is odd, shifted onto the boundary (lap5_launch_variant): vectors are loaded
 // whole (they reach at most one column into the halo on either side), stored element by element where they straddle the
 // domain's edge, and a neighbour column outside the halo is never loaded (its consumer is not a domain point).
-template <typename T, typename W, int VARIANT, int VEC, int LJ, int NTL = 0, bool MASKED = false>
+template <typename T, typename W, int VARIANT, int VEC, int LJ, bool MASKED = false>
 __device__ __forceinline__ void lap5_strip_lane(const View<const T>& in, const View<T>& out, int dJ, int i0, bool active,
                                                 bool edge_w, bool edge_e, int j0, unsigned k, int c_lo = 0, int c_hi = 0) {
     const T* __restrict__ col = in.p + (int64_t)k * in.sk + i0;
@@ -72,20 +72,7 @@ __device__ __forceinline__ void lap5_strip_lane(const View<const T>& in, const V
         int jr = j0 - 1 + t;
         jr = jr > dJ ? dJ : jr;
         roff[t] = (int64_t)jr * in.sj;
-        // NTL: rows no other strip needs (t = 2 .. LJ-1) may be loaded non-temporally so that they do not
-        // displace the rows neighbouring strips share in L2 (1 = those rows only, 2 = every row)
-        if constexpr (NTL == 2 || (NTL == 1 && VEC == 2 && sizeof(T) == 8)) {
-            if (NTL == 2 || (t >= 2 && t <= LJ - 1)) {
-                using V = typename VecT<T, VEC>::type;
-                const V v = __builtin_nontemporal_load(reinterpret_cast<const V*>(col + roff[t]));
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) r[t][q] = v[q];
-            } else {
-                vload<T, VEC>(col + roff[t], r[t]);
-            }
-        } else {
-            vload<T, VEC>(col + roff[t], r[t]);
-        }
+        vload<T, VEC>(col + roff[t], r[t]);
     }
     bool first_in = true, last_in = true;  // the lane's first / last column is a domain point
     if constexpr (MASKED) {
@@ -125,7 +112,7 @@ __device__ __forceinline__ void lap5_strip_lane(const View<const T>& in, const V
 }
 
 // One strip: columns [bx*BLOCK*VEC, ...) x rows [j0, min(j0+LJ, dJ)) of level k; the lanes of a wave lie along I.
-template <typename T, typename W, int VARIANT, int VEC, int LJ, int BLOCK, int NTL = 0, bool MASKED = false>
+template <typename T, typename W, int VARIANT, int VEC, int LJ, int BLOCK, bool MASKED = false>
 __device__ __forceinline__ void lap5_strip_tile(const View<const T>& in, const View<T>& out, int dI, int dJ,
                                                 unsigned bx, int j0, unsigned k, int c_lo = 0) {
     const unsigned lane = threadIdx.x & 63;
@@ -135,8 +122,8 @@ __device__ __forceinline__ void lap5_strip_tile(const View<const T>& in, const V
     int i0 = (int)(bx * BLOCK + threadIdx.x) * VEC;
     const bool active = i0 < dI;
     if (!active) i0 = MASKED ? ((dI + VEC - 1) / VEC - 1) * VEC : dI - VEC;
-    lap5_strip_lane<T, W, VARIANT, VEC, LJ, NTL, MASKED>(in, out, dJ, i0, active, lane == 0, (lane == 63) || (i0 + VEC >= dI), j0, k,
-                                                        c_lo, dI);
+    lap5_strip_lane<T, W, VARIANT, VEC, LJ, MASKED>(in, out, dJ, i0, active, lane == 0, (lane == 63) || (i0 + VEC >= dI), j0, k,
+                                                   c_lo, dI);
 }
 
 // A box only LPR * VEC columns wide (the W / E boxes of a decomposed apply): a wave is 64 / LPR rows of LPR lanes, each row of
@@ -155,18 +142,25 @@ __device__ __forceinline__ void lap5_narrow_tile(const View<const T>& in, const 
                                             j0 < dJ ? j0 : dJ, k);
 }
 
-template <typename T, typename W, int VARIANT, int VEC, int LJ, int BLOCK, int XCDG = 0, int NTL = 0, bool MASKED = false>
+struct Lap5Tuning {
+    static constexpr int LJ = 8;  // rows per strip; all LJ+2 row loads are in flight at once
+    // Runs of 4 consecutive strips per XCD: measured 382 vs 372 GLUPS (none) vs 370 (one contiguous
+    // range per XCD) at 512^3, and L2->fabric reads 1.13x instead of 1.33x the algorithmic bytes
+    // (profiles/r1_microbench_g_xcd_groups.log, r1_lap512_fetch_by_variant.txt).
+    static constexpr int XCDG = 4;
+};
+
+// Runs of Lap5Tuning::XCDG consecutive strips share an XCD (private L2), so the halo rows they share are L2 hits instead of a
+// second fabric fetch.
+template <typename T, typename W, int VARIANT, int VEC, int BLOCK, bool MASKED = false>
 __global__ void __launch_bounds__(BLOCK)
 lap5_strip_kernel(View<const T> in, View<T> out, int dI, int dJ, unsigned tiles_x, unsigned tiles_y, int c_lo = 0) {
-    // XCDG > 0: runs of XCDG consecutive strips share an XCD (private L2), so the halo rows they
-    // share are L2 hits instead of a second fabric fetch.  XCDG = -1: one contiguous range per XCD.
-    unsigned b = blockIdx.x;
-    if constexpr (XCDG > 0) b = xcd_remap_grouped<(unsigned)XCDG>(b, gridDim.x);
-    if constexpr (XCDG < 0) b = xcd_remap(b, gridDim.x);
+    constexpr int LJ = Lap5Tuning::LJ;
+    const unsigned b = xcd_remap_grouped<(unsigned)Lap5Tuning::XCDG>(blockIdx.x, gridDim.x);
     const unsigned bx = b % tiles_x;
     const unsigned by = (b / tiles_x) % tiles_y;
     const unsigned k = b / (tiles_x * tiles_y);
-    lap5_strip_tile<T, W, VARIANT, VEC, LJ, BLOCK, NTL, MASKED>(in, out, dI, dJ, bx, (int)by * LJ, k, c_lo);
+    lap5_strip_tile<T, W, VARIANT, VEC, LJ, BLOCK, MASKED>(in, out, dI, dJ, bx, (int)by * LJ, k, c_lo);
 }
 
 // Up to two single J rows (row_a, row_b) of every level in ONE launch: the boundary strips of a
@@ -198,14 +192,6 @@ lap5_generic_kernel(View<const T> in, View<T> out, int dI, int dJ, int dK) {
 }
 
 // ---- launch configuration ------------------------------------------------------------------
-struct Lap5Tuning {
-    static constexpr int LJ = 8;  // rows per strip; all LJ+2 row loads are in flight at once
-    // Runs of 4 consecutive strips per XCD: measured 382 vs 372 GLUPS (none) vs 370 (one contiguous
-    // range per XCD) at 512^3, and L2->fabric reads 1.13x instead of 1.33x the algorithmic bytes
-    // (profiles/r1_microbench_g_xcd_groups.log, r1_lap512_fetch_by_variant.txt).
-    static constexpr int XCDG = 4;
-};
-
 template <typename T, typename W, int VARIANT, int VEC, int BLOCK>
 inline int lap5_launch_strip(const View<const T>& in, const View<T>& out, const int64_t d[3],
                              hipStream_t stream) {
@@ -214,7 +200,7 @@ inline int lap5_launch_strip(const View<const T>& in, const View<T>& out, const 
     const unsigned ty = (unsigned)cdiv(d[1], LJ);
     const int64_t n = (int64_t)tx * ty * d[2];
     if (n > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "lap5: domain too large for one launch");
-    hipLaunchKernelGGL((lap5_strip_kernel<T, W, VARIANT, VEC, LJ, BLOCK, Lap5Tuning::XCDG>), dim3((unsigned)n), dim3(BLOCK),
+    hipLaunchKernelGGL((lap5_strip_kernel<T, W, VARIANT, VEC, BLOCK>), dim3((unsigned)n), dim3(BLOCK),
                        launch_dynamic_lds(), stream, in, out, (int)d[0], (int)d[1], tx, ty, 0);
     return GT4MI_OK;
 }
@@ -231,7 +217,7 @@ inline int lap5_launch_strip_masked(const View<const T>& in, const View<T>& out,
     const unsigned ty = (unsigned)cdiv(d[1], LJ);
     const int64_t n = (int64_t)tx * ty * d[2];
     if (n > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "lap5: domain too large for one launch");
-    hipLaunchKernelGGL((lap5_strip_kernel<T, W, VARIANT, VEC, LJ, BLOCK, Lap5Tuning::XCDG, 0, true>), dim3((unsigned)n), dim3(BLOCK),
+    hipLaunchKernelGGL((lap5_strip_kernel<T, W, VARIANT, VEC, BLOCK, true>), dim3((unsigned)n), dim3(BLOCK),
                        launch_dynamic_lds(), stream, in_a, out_a, (int)width, (int)d[1], tx, ty, lead);
     return GT4MI_OK;
 }

@@ -309,8 +309,8 @@ lap5_step_kernel(View<const T> in, View<T> out, int dI, int dJ_int, unsigned til
         int i0 = (int)(bx * LANES + threadIdx.x % LANES) * VEC;
         const bool active = i0 < dI;
         if (!active) i0 = dI - VEC;
-        lap5_strip_lane<T, W, VARIANT, VEC, LJ, 0, MASKED>(in, out, dJ_int, i0, active, lane == 0, (lane == 63) || (i0 + VEC >= dI),
-                                                          (int)by * LJ, k, c_lo, c_hi);
+        lap5_strip_lane<T, W, VARIANT, VEC, LJ, MASKED>(in, out, dJ_int, i0, active, lane == 0, (lane == 63) || (i0 + VEC >= dI),
+                                                       (int)by * LJ, k, c_lo, c_hi);
         return;
     }
     const unsigned tail = rel - split;
@@ -335,8 +335,7 @@ inline int lap5_edge_prepare(gt4mi_halo_plan* plan, const int64_t domain[3], con
     const bool direct = plan->transport == GT4MI_TRANSPORT_DIRECT;
     const int64_t di = domain[0], dj = domain[1], dk = domain[2];
     constexpr int VEC = 16 / (int)sizeof(T);
-    static const int enabled = env_int("GT4MI_DIST_EDGE_UNITS", 1);
-    if (!enabled || (direct && !dx.prepared) || plan->edge_words == nullptr) return GT4MI_OK;
+    if ((direct && !dx.prepared) || plan->edge_words == nullptr) return GT4MI_OK;
     if (sides == 0 || di < 2 * VEC || dj < 2 || dk <= 0 || di % VEC != 0) return GT4MI_OK;
     int phase = -1;
     for (int p = 0; p < 2; ++p)
@@ -495,9 +494,8 @@ inline int lap5_step_run(gt4mi_halo_plan* plan, const int64_t domain[3], const g
     const int64_t pad = cdiv(per_box * pb.n, (int64_t)8) * 8;
     const int64_t tail = cdiv((int64_t)cp.blocks + cdiv((int64_t)g.first[4], (int64_t)4), (int64_t)8) * 8;
     if (tiles > INT32_MAX || interior + pad + tail > INT32_MAX) return GT4MI_OK;
-    // the units start after this share of the interior's workgroups (GT4MI_DIST_EDGE_AFTER_PERCENT; 100: as the last workgroups)
-    static const int after = env_int("GT4MI_DIST_EDGE_AFTER_PERCENT", 85);
-    const int64_t split = (interior * (after < 0 ? 0 : (after > 100 ? 100 : after)) / 100) / 8 * 8;
+    // the units start after 85 % of the interior's workgroups
+    const int64_t split = (interior * 85 / 100) / 8 * 8;
     const dim3 grid((unsigned)(pad + interior + tail));
 #define GT4MI_LAP5_STEP_T(V, TPB, M)                                                                                              \
     hipLaunchKernelGGL((lap5_step_kernel<T, W, V, U, TPB, M>), grid, dim3(256), launch_dynamic_lds(), stream, in_i, out_i, (int)di, \

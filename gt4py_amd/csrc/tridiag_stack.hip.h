@@ -191,41 +191,30 @@ struct TridiagBwdBatch {
     T s[U], r[U];
 };
 
-// WPB waves per workgroup, one J row each (threadIdx.y): the waves that share a CU then work on adjacent rows of the
-// same I tile -- the same pages at every level -- instead of whatever tiles the dispatcher hands the CU.
-// MAP: which (I tile, J row) a workgroup takes.  Workgroup b runs on XCD b % 8 (round-robin dispatch); with one wave per SIMD
-// 1 024 workgroups are resident: 64 rows of a 1 024-column domain, 512 KB of every K level of every field.
-//   0  b -> tile b % tiles_i of row b / tiles_i: every XCD works on two 512-byte pieces of EVERY resident row
-//   1  whole rows per XCD: XCD x takes row 8 n + x (its L2 and UTCL2 see contiguous 8 KB rows)
-//   2  a contiguous eighth of the rows per XCD (rows [x dJ / 8, (x + 1) dJ / 8): every XCD inside its own pages)
-//   3  row-major inside bands of 256 rows = ONE 2 MiB page of every level: band by band, tile-column by tile-column
-// (round 4, VERDICT item 5: profiles/r4_tridiag_translation.txt has time and translation counters of all four)
-// NTL (round 5): 1 = nontemporal loads of all four input streams of the forward sweep (a column kernel reads every element exactly
-// once, level after level, a plane apart: nothing is worth keeping in the L1), 2 = of the two read-only ones (inf, diag) only, 0 = plain
-// loads.  1024 x 1024 x 160 fp64, same box A-B-A x 3 (experiments/microbench.hip `trint`): 1.795 ms plain, 1.738 ms with 2, 1.650 ms
-// with 1 (+8.7 %), bit-identical (profiles/r5_nt_loads_column_kernels.txt).  The Laplacian LOST 6-9 % with nontemporal loads in
-// round 1 (its halo rows are re-read through the L1).
-template <typename T, int RL, int LL, int U, int WPB = 1, int MAP = 0, int NTL = 1>
-__global__ void __launch_bounds__(64 * WPB)
+// Nontemporal loads of all four input streams of the forward sweep (round 5): a column kernel reads every element exactly once,
+// level after level, a plane apart, so nothing is worth keeping in the L1.  1024 x 1024 x 160 fp64, same box A-B-A x 3: 1.795 ms
+// plain, 1.738 ms with the hint on the two read-only streams only, 1.650 ms with it on all four (+8.7 %), bit-identical
+// (profiles/r5_nt_loads_column_kernels.txt).  The Laplacian LOST 6-9 % with nontemporal loads in round 1 (its halo rows are
+// re-read through the L1).
+// TRIDIAG_PIPE_WPB waves per workgroup, one J row each (threadIdx.y): the waves that share a CU then work on adjacent rows of the
+// same I tile -- the same pages at every level -- instead of whatever tiles the dispatcher hands the CU.  Two waves, round 5,
+// with the nontemporal loads: 1.582-1.592 ms against 1.624-1.634 for one on one box, 1.713-1.721 against 1.748-1.755 on another
+// (+2-2.6 %, A-B x 3 each; four waves +1 %; without the nontemporal loads the same change is +0.6 %;
+// profiles/r5_nt_loads_column_kernels.txt); K = 80 (32 + 40 levels) 0.878 -> 0.867 ms, K = 60 (16 + 40) 0.628 -> 0.615 ms.
+// 80 KB of LDS per workgroup at 40 LDS levels, still one wave per SIMD.  Workgroup b takes I tile b % tiles_i of row b / tiles_i
+// (round 4 compared three other mappings: profiles/r4_tridiag_translation.txt).
+constexpr int TRIDIAG_PIPE_WPB = 2;
+
+template <typename T, int RL, int LL, int U>
+__global__ void __launch_bounds__(64 * TRIDIAG_PIPE_WPB)
 tridiag_pipe_kernel(View<const T> inf, View<const T> diag, View<T> sup, View<T> rhs, View<T> out, int dI, int dJ,
                     int dK, unsigned tiles_i) {
+    constexpr int WPB = TRIDIAG_PIPE_WPB;
     static_assert(RL % U == 0 && LL % U == 0 && RL >= U, "level ranges are processed in batches of U");
     __shared__ T lds_all[LL > 0 ? LL * 2 * 64 * WPB : 1];
     T* const lds = lds_all + (LL > 0 ? threadIdx.y * (LL * 2 * 64) : 0);
-    unsigned b = blockIdx.x;
-    if constexpr (MAP == 1) {
-        const unsigned R = 8 * tiles_i, full = (gridDim.x / R) * R;
-        if (b < full) b = (b / R) * R + (b % 8) * tiles_i + (b % R) / 8;
-    } else if constexpr (MAP == 2) {
-        b = xcd_remap(b, gridDim.x);
-    }
-    unsigned bi = b % tiles_i, jrow = b / tiles_i;
-    if constexpr (MAP == 3) {
-        const unsigned band = 256 / WPB, per_band = band * tiles_i, nb = b / per_band, r = b % per_band;
-        const unsigned rows_here = min(band, (unsigned)((dJ + WPB - 1) / WPB) - nb * band);
-        bi = r / rows_here;
-        jrow = nb * band + r % rows_here;
-    }
+    const unsigned b = blockIdx.x;
+    const unsigned bi = b % tiles_i, jrow = b / tiles_i;
     const unsigned j = jrow * WPB + threadIdx.y;
     if ((int)j >= dJ) return;
     const int lane = threadIdx.x;
@@ -256,20 +245,10 @@ tridiag_pipe_kernel(View<const T> inf, View<const T> diag, View<T> sup, View<T> 
     auto load = [&](FB& b, int k) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if constexpr (NTL >= 1) {
-                b.a[u] = __builtin_nontemporal_load(p_inf + (int64_t)(k + u) * inf.sk);
-                b.d[u] = __builtin_nontemporal_load(p_diag + (int64_t)(k + u) * diag.sk);
-            } else {
-                b.a[u] = p_inf[(int64_t)(k + u) * inf.sk];
-                b.d[u] = p_diag[(int64_t)(k + u) * diag.sk];
-            }
-            if constexpr (NTL == 1) {
-                b.s[u] = __builtin_nontemporal_load(p_sup + (int64_t)(k + u) * sup.sk);
-                b.r[u] = __builtin_nontemporal_load(p_rhs + (int64_t)(k + u) * rhs.sk);
-            } else {
-                b.s[u] = p_sup[(int64_t)(k + u) * sup.sk];
-                b.r[u] = p_rhs[(int64_t)(k + u) * rhs.sk];
-            }
+            b.a[u] = __builtin_nontemporal_load(p_inf + (int64_t)(k + u) * inf.sk);
+            b.d[u] = __builtin_nontemporal_load(p_diag + (int64_t)(k + u) * diag.sk);
+            b.s[u] = __builtin_nontemporal_load(p_sup + (int64_t)(k + u) * sup.sk);
+            b.r[u] = __builtin_nontemporal_load(p_rhs + (int64_t)(k + u) * rhs.sk);
         }
     };
     auto forward_mem = [&](const FB& b, int k) {

@@ -1,6 +1,6 @@
 """Run on the GPU box: the two-process direct-transport test in a loop, every rank's report kept.
 
-    python3 scripts/two_rank_direct_loop.py [--runs 50] [--rounds 64] [--lib gt4py_amd/lib/libgt4py_amd_r3order.so] > log
+    python3 scripts/two_rank_direct_loop.py [--runs 50] [--rounds 64] > log
 
 Each run starts TWO fresh processes on the one device (tests/mp_util.py: a report per rank, no barrier-then-destroy race); each
 rank runs ``tests/test_gpu_distributed._two_rank_direct_worker`` on the one-stream ("inline") schedule -- the parity cases
@@ -9,8 +9,8 @@ each, ghost cells and results against the oracle -- and then ``--rounds`` rounds
 (``FormCheck.check``: a NEW EPOCH of the probe every round -- the payload the previous round left in the receive buffers is wrong
 in every cell, so EVERY round can see a buffer read too early, not only a plan's first --, both ranks launch together behind a
 barrier, one fused apply, every ghost cell and every ring point compared with exactly known values; ``--load``: which rounds run
-next to an HBM-saturating background).  ``--lib`` selects another build of the library (``make r3order``: the receive side with
-the load order of rounds 2-3) -- the A/B behind profiles/r5_two_rank_direct_loop.log; ``--fenced``: the transport's fenced mode.
+next to an HBM-saturating background).  ``--lib`` selects another build of the library; ``--fenced``: the
+transport's fenced mode.
 A failing round does not end a run: the worker collects every verdict, the tally counts SENSITIVE ROUNDS and failed ones.
 """
 
