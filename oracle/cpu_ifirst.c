@@ -4,8 +4,9 @@
  * (layout (2,1,0), /root/reference/src/gt4py/storage/cartesian/layout_registry.py:87-94), threads
  * over (K, J) rows, I innermost; K innermost and serial for the vertical solve.
  *
- * Used (a) as a second, independent check of the numpy restatement (tests/test_oracle.py) and
- * (b) as the CPU baseline timed next to the GPU numbers (bench.py "cpu_baseline", kind "port").
+ * Used (a) as a second, independent check of the numpy restatement (tests/test_oracle.py), (b) as the CPU baseline timed
+ * next to the GPU numbers (bench.py "cpu_baseline", kind "port", oracle_lap5_f64 only) and (c) as the whole-field oracle of
+ * the full-size GPU tests (tests/fullsize_util.py): every variant, dtype and internal precision the kernel library ships.
  * It is NOT GridTools: the reference's gt:cpu_ifirst needs gridtools-cpp 2.3.9 headers that are not
  * in this image.  Same arithmetic as oracle/ref_numpy.py: expression trees
  * of the stencil definitions, one rounding per operation; build with -ffp-contract=off.
@@ -62,88 +63,136 @@ void oracle_lap5_f64(const double* in, int64_t isi, int64_t isj, int64_t isk, do
         }
 }
 
-/* Horizontal diffusion with flux limiter; T = field type, W = double (default float64 literals).
- * Row-blocked: per (k, j) the lap/flx/fly rows it needs are recomputed into small stack/heap
- * buffers, which is value-identical to full temporaries. */
-#define HDIFF_IMPL(NAME, T)                                                                          \
+/* All four Laplacian variants of csrc/lap5.hip.h:lap5_expr (GT4MI_LAP_NOTEBOOK / DOCS / SUITE / AVG = 0 / 1 / 2 / 3).
+ * T = field type, W = dtype the float literals promote to (double by default; float for float fields under
+ * literal_float_precision=32).  Each bracket sum is evaluated in T, every other operation in W, one rounding to T at the end.
+ * c = in[0,0], w = in[-1,0], e = in[+1,0], s = in[0,-1], n = in[0,+1]. */
+#define LAP5_LOOP(T, EXPR)                                                                             \
+    _Pragma("omp parallel for collapse(2) schedule(static)")                                           \
+    for (int64_t k = 0; k < dk; ++k)                                                                   \
+        for (int64_t j = 0; j < dj; ++j) {                                                             \
+            const T* p = in + k * isk + j * isj;                                                       \
+            T* q = out + k * osk + j * osj;                                                            \
+            for (int64_t i = 0; i < di; ++i) {                                                         \
+                const T* x = p + i * isi;                                                              \
+                const T c = x[0], w = x[-isi], e = x[isi], s = x[-isj], n = x[isj];                    \
+                (void)c; /* (the avg variant does not read the centre) */                              \
+                q[i * osi] = (EXPR);                                                                   \
+            }                                                                                          \
+        }
+
+#define LAP5_IMPL(NAME, T, W)                                                                          \
+    int NAME(const T* in, int64_t isi, int64_t isj, int64_t isk, T* out, int64_t osi, int64_t osj,     \
+             int64_t osk, int64_t di, int64_t dj, int64_t dk, int variant) {                           \
+        if (variant == 0) {                                                                            \
+            LAP5_LOOP(T, (T)(((((((W)(-4.0) * (W)c) + (W)w) + (W)e) + (W)s) + (W)n)))                  \
+        } else if (variant == 1) {                                                                     \
+            LAP5_LOOP(T, (T)(((W)(-4.0) * (W)c) + (W)(T)(((e + w) + n) + s)))                          \
+        } else if (variant == 2) {                                                                     \
+            LAP5_LOOP(T, (T)(((W)4.0 * (W)c) - (W)(T)(((e + w) + n) + s)))                             \
+        } else if (variant == 3) {                                                                     \
+            LAP5_LOOP(T, (T)((W)0.25 * (W)(T)(((n + s) + e) + w)))                                     \
+        } else {                                                                                       \
+            return -1;                                                                                 \
+        }                                                                                              \
+        return 0;                                                                                      \
+    }
+
+LAP5_IMPL(oracle_lap5_f64_variant, double, double)
+LAP5_IMPL(oracle_lap5_f32, float, double)
+LAP5_IMPL(oracle_lap5_f32_lit32, float, float)
+
+/* Horizontal diffusion, optional flux limiter, in the (W, PW) combinations csrc/hdiff.hip.h:hdiff_run dispatches to.
+ * T = field type, W = dtype of lap / flx / fly, PW = dtype of coeff * (...) and of the final subtraction.  The coefficient
+ * is the field `cf` or, when `cf` is NULL, the scalar `coeff` rounded to PW.
+ * Row-blocked: per (k, j) the lap rows it needs are recomputed into small heap buffers, which is value-identical to full
+ * temporaries. */
+#define HDIFF_IMPL(NAME, T, W, PW)                                                                   \
     void NAME(const T* in, int64_t isi, int64_t isj, int64_t isk, T* out, int64_t osi, int64_t osj,   \
-              int64_t osk, const T* cf, int64_t csi, int64_t csj, int64_t csk, int64_t di, int64_t dj, \
-              int64_t dk, int limiter) {                                                             \
+              int64_t osk, const T* cf, int64_t csi, int64_t csj, int64_t csk, double coeff,         \
+              int64_t di, int64_t dj, int64_t dk, int limiter) {                                     \
         _Pragma("omp parallel") {                                                                    \
-            double* lapm = (double*)malloc(sizeof(double) * (size_t)(di + 2) * 3);                   \
-            double* lap0 = lapm + (di + 2);                                                          \
-            double* lapp = lap0 + (di + 2);                                                          \
+            W* lapm = (W*)malloc(sizeof(W) * (size_t)(di + 2) * 3);                                  \
+            W* lap0 = lapm + (di + 2);                                                               \
+            W* lapp = lap0 + (di + 2);                                                               \
+            const PW cs = (PW)coeff;                                                                 \
             _Pragma("omp for collapse(2) schedule(static)")                                          \
             for (int64_t k = 0; k < dk; ++k)                                                         \
                 for (int64_t j = 0; j < dj; ++j) {                                                   \
                     const T* base = in + k * isk + j * isj;                                          \
                     /* lap on rows j-1, j, j+1 for i in [-1, di] */                                  \
                     for (int r = -1; r <= 1; ++r) {                                                  \
-                        double* dst = r < 0 ? lapm : (r == 0 ? lap0 : lapp);                         \
+                        W* dst = r < 0 ? lapm : (r == 0 ? lap0 : lapp);                              \
                         const T* row = base + r * isj;                                               \
                         for (int64_t i = -1; i <= di; ++i) {                                         \
                             const T* c = row + i * isi;                                              \
                             const T sum = ((c[isi] + c[-isi]) + c[isj]) + c[-isj];                   \
-                            dst[i + 1] = (4.0 * (double)c[0]) - (double)sum;                         \
+                            dst[i + 1] = ((W)4.0 * (W)c[0]) - (W)sum;                                \
                         }                                                                            \
                     }                                                                                \
                     for (int64_t i = 0; i < di; ++i) {                                               \
                         const T* c = base + i * isi;                                                 \
-                        double flx, flxm, fly, flym, res;                                            \
+                        W flx, flxm, fly, flym, res;                                                 \
                         res = lap0[i + 2] - lap0[i + 1];                                             \
-                        flx = (limiter && (res * (double)(T)(c[isi] - c[0])) > 0.0) ? 0.0 : res;     \
+                        flx = (limiter && (res * (W)(T)(c[isi] - c[0])) > (W)0) ? (W)0 : res;        \
                         res = lap0[i + 1] - lap0[i];                                                 \
-                        flxm = (limiter && (res * (double)(T)(c[0] - c[-isi])) > 0.0) ? 0.0 : res;   \
+                        flxm = (limiter && (res * (W)(T)(c[0] - c[-isi])) > (W)0) ? (W)0 : res;      \
                         res = lapp[i + 1] - lap0[i + 1];                                             \
-                        fly = (limiter && (res * (double)(T)(c[isj] - c[0])) > 0.0) ? 0.0 : res;     \
+                        fly = (limiter && (res * (W)(T)(c[isj] - c[0])) > (W)0) ? (W)0 : res;        \
                         res = lap0[i + 1] - lapm[i + 1];                                             \
-                        flym = (limiter && (res * (double)(T)(c[0] - c[-isj])) > 0.0) ? 0.0 : res;   \
-                        const double s = ((flx - flxm) + fly) - flym;                                \
-                        const double coeff = (double)cf[k * csk + j * csj + i * csi];                \
-                        out[k * osk + j * osj + i * osi] = (T)((double)c[0] - (coeff * s));          \
+                        flym = (limiter && (res * (W)(T)(c[0] - c[-isj])) > (W)0) ? (W)0 : res;      \
+                        const W s = ((flx - flxm) + fly) - flym;                                     \
+                        const PW cv = cf ? (PW)cf[k * csk + j * csj + i * csi] : cs;                 \
+                        out[k * osk + j * osj + i * osi] = (T)((PW)c[0] - (cv * (PW)s));             \
                     }                                                                                \
                 }                                                                                    \
             free(lapm);                                                                              \
         }                                                                                            \
     }
 
-HDIFF_IMPL(oracle_hdiff_f64, double)
-HDIFF_IMPL(oracle_hdiff_f32, float)
+HDIFF_IMPL(oracle_hdiff_f64, double, double, double)
+HDIFF_IMPL(oracle_hdiff_f32, float, double, double)
+HDIFF_IMPL(oracle_hdiff_f32_w32, float, float, float)
+HDIFF_IMPL(oracle_hdiff_f32_w32_p64, float, float, double)
 
-/* Thomas solve, column by column (K innermost, serial); threads over (J, I-blocks). */
-void oracle_tridiag_f64(const double* inf, const double* diag, double* sup, double* rhs, double* out,
-                        int64_t si, int64_t sj, int64_t sk, int64_t di, int64_t dj, int64_t dk) {
-#pragma omp parallel for schedule(static)
-    for (int64_t j = 0; j < dj; ++j) {
-        /* level by level over a whole row of columns keeps the I-contiguous accesses streaming */
-        const int64_t r = j * sj;
-        for (int64_t i = 0; i < di; ++i) {
-            const int64_t o = r + i * si;
-            sup[o] = sup[o] / diag[o];
-            rhs[o] = rhs[o] / diag[o];
-        }
-        for (int64_t k = 1; k < dk; ++k) {
-            const int64_t b = r + k * sk;
-            for (int64_t i = 0; i < di; ++i) {
-                const int64_t o = b + i * si, m = o - sk;
-                const double den1 = diag[o] - (sup[m] * inf[o]);
-                const double ns = sup[o] / den1;
-                const double num = rhs[o] - (inf[o] * rhs[m]);
-                const double den2 = diag[o] - (sup[m] * inf[o]);
-                sup[o] = ns;
-                rhs[o] = num / den2;
-            }
-        }
-        {
-            const int64_t b = r + (dk - 1) * sk;
-            for (int64_t i = 0; i < di; ++i) out[b + i * si] = rhs[b + i * si];
-        }
-        for (int64_t k = dk - 2; k >= 0; --k) {
-            const int64_t b = r + k * sk;
-            for (int64_t i = 0; i < di; ++i) {
-                const int64_t o = b + i * si;
-                out[o] = rhs[o] - (sup[o] * out[o + sk]);
-            }
-        }
+/* Thomas solve, column by column (K innermost, serial); threads over (J, I-blocks).  T = field type, arithmetic in T. */
+#define TRIDIAG_IMPL(NAME, T)                                                                          \
+    void NAME(const T* inf, const T* diag, T* sup, T* rhs, T* out,                                     \
+              int64_t si, int64_t sj, int64_t sk, int64_t di, int64_t dj, int64_t dk) {                \
+    _Pragma("omp parallel for schedule(static)")                                                       \
+        for (int64_t j = 0; j < dj; ++j) {                                                             \
+            /* level by level over a whole row of columns keeps the I-contiguous accesses streaming */ \
+            const int64_t r = j * sj;                                                                  \
+            for (int64_t i = 0; i < di; ++i) {                                                         \
+                const int64_t o = r + i * si;                                                          \
+                sup[o] = sup[o] / diag[o];                                                             \
+                rhs[o] = rhs[o] / diag[o];                                                             \
+            }                                                                                          \
+            for (int64_t k = 1; k < dk; ++k) {                                                         \
+                const int64_t b = r + k * sk;                                                          \
+                for (int64_t i = 0; i < di; ++i) {                                                     \
+                    const int64_t o = b + i * si, m = o - sk;                                          \
+                    const T den1 = diag[o] - (sup[m] * inf[o]);                                        \
+                    const T ns = sup[o] / den1;                                                        \
+                    const T num = rhs[o] - (inf[o] * rhs[m]);                                          \
+                    const T den2 = diag[o] - (sup[m] * inf[o]);                                        \
+                    sup[o] = ns;                                                                       \
+                    rhs[o] = num / den2;                                                               \
+                }                                                                                      \
+            }                                                                                          \
+            {                                                                                          \
+                const int64_t b = r + (dk - 1) * sk;                                                   \
+                for (int64_t i = 0; i < di; ++i) out[b + i * si] = rhs[b + i * si];                    \
+            }                                                                                          \
+            for (int64_t k = dk - 2; k >= 0; --k) {                                                    \
+                const int64_t b = r + k * sk;                                                          \
+                for (int64_t i = 0; i < di; ++i) {                                                     \
+                    const int64_t o = b + i * si;                                                      \
+                    out[o] = rhs[o] - (sup[o] * out[o + sk]);                                          \
+                }                                                                                      \
+            }                                                                                          \
+        }                                                                                              \
     }
-}
+
+TRIDIAG_IMPL(oracle_tridiag_f64, double)
+TRIDIAG_IMPL(oracle_tridiag_f32, float)

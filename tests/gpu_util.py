@@ -91,7 +91,7 @@ def lap5(inp: DevArray, out: DevArray, origin_in, origin_out, domain, variant=0,
 
 def hdiff(inp: DevArray, out: DevArray, coeff, origin_in, origin_out, origin_coeff, domain, flags):
     name = "gt4mi_hdiff_f64" if inp.dtype == np.float64 else "gt4mi_hdiff_f32"
-    if isinstance(coeff, DevArray):
+    if hasattr(coeff, "field"):  # (a DevArray or anything else that describes a field: fullsize_util.StorageField)
         cf, cs = ctypes.byref(coeff.field(origin_coeff)), 0.0
     else:
         cf, cs = None, float(coeff)

@@ -534,3 +534,366 @@ def test_a_plain_bench_run_times_its_steps_and_dumps_what_the_last_one_computed(
     want = np.zeros(bench.DUMP_SAMPLES)  # (the halo of `out` is never written: zeros)
     want[inner] = (-4.0 * inp[a, b, c]) + inp[a - 1, b, c] + inp[a + 1, b, c] + inp[a, b - 1, c] + inp[a, b + 1, c]
     assert np.array_equal(files["out_sample.npy"], want)
+
+
+# ---- full-size, whole-field parity: every element of every output against the C oracle --------------------------------------------
+# The cases above check the BASELINE sizes with known answers and slivers of random data.  These run every shipped kernel at
+# the sizes bench.py launches it (and at the shapes around them that reach its edge paths) on random inputs, and compare EVERY
+# element of each output array -- halo and row padding included, which must still hold the sentinel -- bit for bit with
+# oracle/cpu_ifirst.c, slab by slab (tests/fullsize_util.py).  "API" cases go through gtscript.stencil + FrozenStencil with fields
+# placed by the stencil's placement_hint() the way bench.py calls them, "ABI" cases through the C ABI (tests/gpu_util.py).
+def _fullsize():
+    import torch
+
+    import fullsize_util as F
+    from oracle import cpu_ifirst as C
+
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()  # (the previous case's fields are gone)
+    return F, C
+
+
+def _field(F, shape, dtype, aligned, gen=None, lo=0.0, hi=1.0, quantum=0.0, cls=None):
+    """A storage whose every element (row padding included) holds the sentinel; then U[lo, hi) on its shape when ``gen``."""
+    gt_storage, _ = _imports()
+    a = gt_storage.empty(shape, dtype, backend=BACKEND, aligned_index=aligned, memory_class=cls)
+    F.fill_sentinel(a.tensor)
+    if gen is not None:
+        F.fill_uniform(a.tensor, gen, lo, hi, quantum)
+    return a
+
+
+def _gen(seed):
+    import torch
+
+    return torch.Generator(device="cuda").manual_seed(seed)
+
+
+def _k_range(lo, hi, origin, domain):
+    return max(lo, origin[2]), min(hi, origin[2] + domain[2])
+
+
+def _check_lap5(F, C, what, inp, out, origin, domain, variant=0, literal32=False):
+    to = out.tensor
+
+    def expect(lo, hi):
+        want = F.sentinel_slab(to, 2, lo, hi)
+        klo, khi = _k_range(lo, hi, origin, domain)
+        if khi > klo:
+            C.lap5(F.host(inp.tensor, 2, klo, khi), want, (origin[0], origin[1], 0), (origin[0], origin[1], klo - lo),
+                   (domain[0], domain[1], khi - klo), variant=variant, literal32=literal32, threads=F.oracle_threads())
+        return {"out": want}
+
+    F.check_slabs(what, {"out": to}, expect, axis=2, step=F.slab_step(to, 2))
+
+
+def _check_hdiff(F, C, what, inp, out, coeff, origin, domain, limiter=True, internal32=False, coeff_f32=False):
+    """``coeff``: a storage (the coefficient field, same origin) or a Python float."""
+    to = out.tensor
+    field = not isinstance(coeff, float)
+
+    def expect(lo, hi):
+        want = F.sentinel_slab(to, 2, lo, hi)
+        klo, khi = _k_range(lo, hi, origin, domain)
+        if khi > klo:
+            o = (origin[0], origin[1], 0)
+            c = F.host(coeff.tensor, 2, klo, khi) if field else coeff
+            C.hdiff(F.host(inp.tensor, 2, klo, khi), want, c, o, (origin[0], origin[1], klo - lo), o,
+                    (domain[0], domain[1], khi - klo), limiter=limiter, internal_f32=internal32, coeff_f32=coeff_f32,
+                    threads=F.oracle_threads())
+        return {"out": want}
+
+    F.check_slabs(what, {"out": to}, expect, axis=2, step=F.slab_step(to, 2))
+
+
+def _tridiag_fields(F, dom, dtype, seed, hint=None):
+    gen = _gen(seed)
+    ranges = {"inf": (-1, 1), "diag": (4, 5), "sup": (-1, 1), "rhs": (-10, 10), "out": None}
+    f = {n: _field(F, dom, dtype, (0, 0, 0), gen if r else None, *(r or (0, 1)), cls=hint[n] if hint else None)
+         for n, r in ranges.items()}
+    keep = {n: F.padded(f[n].tensor).clone() for n in ("sup", "rhs")}  # (the solve rewrites both in place)
+    return f, keep
+
+
+def _check_tridiag(F, C, what, f, keep, dom):
+    """J slabs: the oracle solves the slab's columns from the pristine sup / rhs; out, sup and rhs are compared whole."""
+    ni = dom[0]
+
+    def expect(lo, hi):
+        a = {n: F.host(F.padded(f[n].tensor), 1, lo, hi) for n in ("inf", "diag")}
+        a.update({n: F.host(keep[n], 1, lo, hi).copy(order="K") for n in ("sup", "rhs")})
+        a["out"] = F.sentinel_slab(f["out"].tensor, 1, lo, hi)
+        assert len({x.strides for x in a.values()}) == 1
+        C.tridiag(*[a[n][:ni] for n in ("inf", "diag", "sup", "rhs", "out")], (ni, hi - lo, dom[2]), threads=F.oracle_threads())
+        return a
+
+    outs = {n: f[n].tensor for n in ("out", "sup", "rhs")}
+    F.check_slabs(what, outs, expect, axis=1, step=F.slab_step(f["out"].tensor, 1))
+
+
+def test_fullsize_L1_lap5_f64_128x128x64_every_variant():
+    """BASELINE configs[0]'s shape through the C ABI: 64 lanes of 16 bytes (VEC 2, BLOCK 64), all four variants."""
+    import gpu_util as G
+
+    F, C = _fullsize()
+    dom, origin = (128, 128, 64), (1, 1, 0)
+    shape = (dom[0] + 2, dom[1] + 2, dom[2])
+    inp = _field(F, shape, np.float64, origin, _gen(11), -1.0, 1.0)
+    for variant in range(4):
+        out = _field(F, shape, np.float64, origin)
+        G.lap5(F.StorageField(inp), F.StorageField(out), origin, origin, dom, variant)
+        _check_lap5(F, C, f"lap5 f64 128x128x64 variant {variant}", inp, out, origin, dom, variant)
+
+
+def test_fullsize_L2_lap_cartesian_512cubed_headline():
+    """The headline launch through the API: 512^3 fp64, VEC 2, BLOCK 256, 32 768 workgroups; every point."""
+    F, C = _fullsize()
+    _, gtscript = _imports()
+    lap = gtscript.stencil(backend=BACKEND, definition=lap_cartesian, device_sync=False)
+    hint = lap.placement_hint()
+    dom, origin = (512, 512, 512), (1, 1, 0)
+    shape = (dom[0] + 2, dom[1] + 2, dom[2])
+    inp = _field(F, shape, np.float64, origin, _gen(1337), -1.0, 1.0, cls=hint["inp"])
+    out = _field(F, shape, np.float64, origin, cls=hint["out"])
+    lap.freeze(origin={"inp": origin, "out": origin}, domain=dom)(inp=inp, out=out)
+    _check_lap5(F, C, "lap_cartesian 512^3", inp, out, origin, dom)
+
+
+@pytest.mark.parametrize("use_kernel_library", [True, False], ids=["L3_kernel_library", "G1_generated"])
+def test_fullsize_lap_cartesian_512x512x128_four_rotating_pairs(use_kernel_library):
+    """BASELINE configs[1] as bench.py rotates it: four random (inp, out) pairs, three rounds of pair 0, 1, 2, 3; then every
+    point of every pair.  G1: the same through the code generator (use_kernel_library=False), what bench --full reports."""
+    F, C = _fullsize()
+    _, gtscript = _imports()
+    lap = gtscript.stencil(backend=BACKEND, definition=lap_cartesian, device_sync=False, use_kernel_library=use_kernel_library)
+    hint = lap.placement_hint()
+    dom, origin = (512, 512, 128), (1, 1, 0)
+    shape = (dom[0] + 2, dom[1] + 2, dom[2])
+    gen = _gen(2024)
+    pairs = [(_field(F, shape, np.float64, origin, gen, -1.0, 1.0, cls=hint["inp"]), _field(F, shape, np.float64, origin, cls=hint["out"]))
+             for _ in range(4)]
+    frozen = lap.freeze(origin={"inp": origin, "out": origin}, domain=dom)
+    for _ in range(3):
+        for inp, out in pairs:
+            frozen(inp=inp, out=out)
+    for n, (inp, out) in enumerate(pairs):
+        _check_lap5(F, C, f"lap_cartesian 512x512x128 pair {n} (kernel library {use_kernel_library})", inp, out, origin, dom)
+
+
+def test_fullsize_L4_lap5_f64_512cubed_off_the_aligned_column():
+    """aligned_index (0, 0, 0), origin (1, 1, 0): 513 columns from the aligned one, masked two-item lanes, 257 lanes in
+    320-wide workgroups."""
+    import gpu_util as G
+
+    F, C = _fullsize()
+    dom, origin = (512, 512, 512), (1, 1, 0)
+    shape = (dom[0] + 2, dom[1] + 2, dom[2])
+    inp = _field(F, shape, np.float64, (0, 0, 0), _gen(5), -1.0, 1.0)
+    out = _field(F, shape, np.float64, (0, 0, 0))
+    G.lap5(F.StorageField(inp), F.StorageField(out), origin, origin, dom, 0)
+    _check_lap5(F, C, "lap5 f64 512^3 from aligned_index (0, 0, 0)", inp, out, origin, dom)
+
+
+def test_fullsize_L5_lap5_f64_509x500x67_odd_width_and_the_remap_tail():
+    """An odd width (masked lanes); 63 x 67 = 4 221 workgroups, so the last 29 take the identity tail of
+    xcd_remap_grouped (runs of 8 XCDs x 4)."""
+    import gpu_util as G
+
+    F, C = _fullsize()
+    dom, origin = (509, 500, 67), (1, 1, 0)
+    shape = (dom[0] + 2, dom[1] + 2, dom[2])
+    inp = _field(F, shape, np.float64, origin, _gen(6), -1.0, 1.0)
+    out = _field(F, shape, np.float64, origin)
+    G.lap5(F.StorageField(inp), F.StorageField(out), origin, origin, dom, 2)
+    _check_lap5(F, C, "lap5 f64 509x500x67 variant 2", inp, out, origin, dom, 2)
+
+
+@pytest.mark.parametrize("literal32", [False, True])
+def test_fullsize_L6_lap5_f32_1024x512x64_wide_strip(literal32):
+    """float32, 1024 columns: VEC 4, BLOCK 256 -- the only lap5 strip no kernel test reaches; every variant, float64 and
+    float32 literals."""
+    import gpu_util as G
+    from gt4py_amd import _lib
+
+    F, C = _fullsize()
+    dom, origin = (1024, 512, 64), (1, 1, 0)
+    shape = (dom[0] + 2, dom[1] + 2, dom[2])
+    inp = _field(F, shape, np.float32, origin, _gen(7), -1.0, 1.0)
+    for variant in range(4):
+        out = _field(F, shape, np.float32, origin)
+        G.lap5(F.StorageField(inp), F.StorageField(out), origin, origin, dom, variant, _lib.LAP_LITERAL_F32 if literal32 else 0)
+        _check_lap5(F, C, f"lap5 f32 1024x512x64 variant {variant} literal32={literal32}", inp, out, origin, dom, variant, literal32)
+
+
+@pytest.mark.parametrize("use_kernel_library", [True, False], ids=["H1_kernel_library", "G2_generated"])
+def test_fullsize_hdiff_limiter_field_f32_1024x1024x80(use_kernel_library):
+    """BASELINE configs[2] through the API: one pass on uniform data, one on data quantized to multiples of 1/8 (equal
+    neighbours: limiter ties, exact zeros of either sign).  G2: the generated kernel bench --full reports."""
+    from gt4py_amd.cartesian.backend import hip_templates
+
+    F, C = _fullsize()
+    _, gtscript = _imports()
+    hd = gtscript.stencil(backend=BACKEND, definition=hip_templates.hdiff_limiter_field, dtypes={"T": np.float32}, device_sync=False,
+                          use_kernel_library=use_kernel_library)
+    hint = hd.placement_hint()
+    dom, origin = (1024, 1024, 80), (2, 2, 0)
+    shape = (dom[0] + 4, dom[1] + 4, dom[2])
+    frozen = hd.freeze(origin={k: origin for k in ("in_field", "out_field", "coeff")}, domain=dom)
+    gen = _gen(2024)
+    for quantum in (0.0, 1.0 / 8):
+        inp = _field(F, shape, np.float32, origin, gen, 0.0, 10.0, quantum, cls=hint["in_field"])
+        coeff = _field(F, shape, np.float32, origin, gen, 0.0, 0.05, cls=hint["coeff"])
+        out = _field(F, shape, np.float32, origin, cls=hint["out_field"])
+        frozen(in_field=inp, out_field=out, coeff=coeff)
+        _check_hdiff(F, C, f"hdiff_limiter_field f32 1024^2x80 quantum {quantum} (kernel library {use_kernel_library})", inp, out,
+                     coeff, origin, dom)
+        del inp, coeff, out
+
+
+def test_fullsize_H2_hdiff_f32_1024x1024x80_float32_internals():
+    """HDIFF_INTERNAL_F32 with a coefficient field: the W = PW = float shared-rows kernel."""
+    import gpu_util as G
+    from gt4py_amd import _lib
+
+    F, C = _fullsize()
+    dom, origin = (1024, 1024, 80), (2, 2, 0)
+    shape = (dom[0] + 4, dom[1] + 4, dom[2])
+    gen = _gen(21)
+    inp = _field(F, shape, np.float32, origin, gen, 0.0, 10.0)
+    coeff = _field(F, shape, np.float32, origin, gen, 0.0, 0.05)
+    out = _field(F, shape, np.float32, origin)
+    G.hdiff(F.StorageField(inp), F.StorageField(out), F.StorageField(coeff), origin, origin, origin, dom,
+            _lib.HDIFF_LIMITER | _lib.HDIFF_INTERNAL_F32)
+    _check_hdiff(F, C, "hdiff f32 1024^2x80 float32 internals", inp, out, coeff, origin, dom, internal32=True)
+
+
+@pytest.mark.parametrize("internal32,coeff_f32", [(False, True), (True, True), (True, False)])
+def test_fullsize_H3_hdiff_f32_1024x1024x80_scalar_coefficient_no_limiter(internal32, coeff_f32):
+    """A scalar coefficient (COEFF_FIELD = false), no limiter, in the three (W, PW) combinations a float32 field can take
+    with a scalar: (double, double) with the scalar rounded through float, (float, float), (float, double)."""
+    import gpu_util as G
+    from gt4py_amd import _lib
+
+    F, C = _fullsize()
+    dom, origin = (1024, 1024, 80), (2, 2, 0)
+    shape = (dom[0] + 4, dom[1] + 4, dom[2])
+    inp = _field(F, shape, np.float32, origin, _gen(22), 0.0, 10.0)
+    out = _field(F, shape, np.float32, origin)
+    weight = 0.0310000001
+    flags = (_lib.HDIFF_INTERNAL_F32 if internal32 else 0) | (_lib.HDIFF_COEFF_F32 if coeff_f32 else 0)
+    G.hdiff(F.StorageField(inp), F.StorageField(out), weight, origin, origin, None, dom, flags)
+    _check_hdiff(F, C, f"hdiff f32 1024^2x80 scalar internal32={internal32} coeff_f32={coeff_f32}", inp, out, weight, origin, dom,
+                 limiter=False, internal32=internal32, coeff_f32=coeff_f32)
+
+
+@pytest.mark.parametrize("dom", [(512, 1024, 80), (2048, 2048, 80)], ids=["H4_configs4_share", "H5_configs4_whole"])
+def test_fullsize_hdiff_f64_field_limiter(dom):
+    """H4: BASELINE configs[4]'s per-rank share (bench's fp64 hdiff figure); H5: configs[4]'s whole 2048 x 2048 x 80 grid on one
+    device (2.7 GB per field), compared in K slabs."""
+    import gpu_util as G
+    from gt4py_amd import _lib
+
+    F, C = _fullsize()
+    origin = (2, 2, 0)
+    shape = (dom[0] + 4, dom[1] + 4, dom[2])
+    gen = _gen(23)
+    inp = _field(F, shape, np.float64, origin, gen, 0.0, 10.0)
+    coeff = _field(F, shape, np.float64, origin, gen, 0.0, 0.05)
+    out = _field(F, shape, np.float64, origin)
+    G.hdiff(F.StorageField(inp), F.StorageField(out), F.StorageField(coeff), origin, origin, origin, dom, _lib.HDIFF_LIMITER)
+    _check_hdiff(F, C, f"hdiff f64 {dom}", inp, out, coeff, origin, dom)
+
+
+def test_fullsize_H6_hdiff_f32_1021x1019x80_lead_and_tails():
+    """aligned_index (0, 0, 0), origin (2, 2, 0): lead = 2 for float32 lanes, a tail strip, idle waves behind the barrier, a
+    groups_j tail; quantized data."""
+    import gpu_util as G
+    from gt4py_amd import _lib
+
+    F, C = _fullsize()
+    dom, origin = (1021, 1019, 80), (2, 2, 0)
+    shape = (dom[0] + 4, dom[1] + 4, dom[2])
+    gen = _gen(24)
+    inp = _field(F, shape, np.float32, (0, 0, 0), gen, 0.0, 10.0, 1.0 / 8)
+    coeff = _field(F, shape, np.float32, (0, 0, 0), gen, 0.0, 0.05)
+    out = _field(F, shape, np.float32, (0, 0, 0))
+    G.hdiff(F.StorageField(inp), F.StorageField(out), F.StorageField(coeff), origin, origin, origin, dom, _lib.HDIFF_LIMITER)
+    _check_hdiff(F, C, "hdiff f32 1021x1019x80 from aligned_index (0, 0, 0)", inp, out, coeff, origin, dom)
+
+
+@pytest.mark.parametrize("use_kernel_library", [True, False], ids=["T1_kernel_library", "G3_generated"])
+def test_fullsize_tridiagonal_solver_f64_1024x1024x160(use_kernel_library):
+    """BASELINE configs[3] through the API: tridiag_pipe_kernel<double, 104, 40, 4>; every point of out, sup and rhs.  G3: the
+    generated column kernel."""
+    from gt4py_amd.cartesian.backend import hip_templates
+
+    F, C = _fullsize()
+    _, gtscript = _imports()
+    tri = gtscript.stencil(backend=BACKEND, definition=hip_templates.tridiagonal_solver, dtypes={"T": np.float64}, device_sync=False,
+                           use_kernel_library=use_kernel_library)
+    dom = (1024, 1024, 160)
+    f, keep = _tridiag_fields(F, dom, np.float64, 31, tri.placement_hint())
+    tri.freeze(origin={n: (0, 0, 0) for n in f}, domain=dom)(**f)
+    _check_tridiag(F, C, f"tridiagonal_solver f64 1024^2x160 (kernel library {use_kernel_library})", f, keep, dom)
+
+
+@pytest.mark.parametrize("dtype,dom", [(np.float32, (1024, 1024, 160)), (np.float64, (1024, 1024, 60)), (np.float64, (1023, 1021, 130)),
+                                       (np.float32, (1024, 1024, 24))],
+                         ids=["T2_f32_pipe_32_40_8", "T3_f64_pipe_16_40_8", "T3_f64_pipe_80_40_8", "T4_f32_shallow_vec2"])
+def test_fullsize_tridiag_abi(dtype, dom):
+    """The other on-chip stack instantiations: <float, 32, 40, 8>, <double, 16, 40, 8>, <double, 80, 40, 8>, and the
+    register-only tridiag_kernel<float, 2, 8> of shallow columns."""
+    import gpu_util as G
+
+    F, C = _fullsize()
+    f, keep = _tridiag_fields(F, dom, dtype, 32)
+    names = ("inf", "diag", "sup", "rhs", "out")
+    G.tridiag(*[F.StorageField(f[n]) for n in names], {n: (0, 0, 0) for n in names}, dom)
+    _check_tridiag(F, C, f"tridiag {np.dtype(dtype).name} {dom}", f, keep, dom)
+
+
+def test_fullsize_G4_generated_vertical_advection_1024x1024x160():
+    """The generated vertical advection at bench size: EVERY column against ``ref_numpy.vadv`` bit for bit, in J slabs of 8
+    rows that a pool of oracle_threads() workers computes ahead of the comparison, the whole of utens_stage (its untouched
+    last column and level and the row padding included).  Complements test_vertical_advection_at_the_bench_size (6 columns
+    bit for bit, the residual of every column)."""
+    import concurrent.futures
+
+    import torch
+
+    import bench
+    from oracle import ref_numpy as R
+
+    F, _ = _fullsize()
+    _, gtscript = _imports()
+    st = gtscript.stencil(backend=BACKEND, definition=bench._vertical_advection_dycore, externals={"BET_M": 0.5, "BET_P": 0.5},
+                          device_sync=False)
+    hint = st.placement_hint()
+    names = ("utens_stage", "u_stage", "wcon", "u_pos", "utens")
+    dom = (1024, 1024, 160)
+    shape = (dom[0] + 1, dom[1], dom[2] + 1)
+    gen = _gen(77)
+    f = {n: _field(F, shape, np.float64, (0, 0, 0), gen, -1.0, 1.0, cls=hint[n]) for n in names}
+    keep = F.padded(f["utens_stage"].tensor).clone()
+    dtr = 3.0 / 20.0
+    st.freeze(origin={n: (0, 0, 0) for n in names}, domain=dom)(**f, dtr_stage=dtr)
+    torch.cuda.synchronize()
+    step = 8  # (per worker: 5 input slabs + 11 temporaries of 1024 x 8 x 160 float64, about 170 MB)
+
+    def slab(lo):
+        a = {n: F.host(F.padded(f[n].tensor), 1, lo, lo + step) for n in names[1:]}
+        a["utens_stage"] = F.host(keep, 1, lo, lo + step).copy(order="K")
+        R.vadv(*[a[n] for n in names], dtr, domain=(dom[0], step, dom[2]))
+        return lo, a["utens_stage"]
+
+    starts = range(0, dom[1], step)
+    with concurrent.futures.ThreadPoolExecutor(F.oracle_threads()) as pool:
+        ahead = pool.map(slab, starts)  # (in order)
+
+        def expect(lo, hi):
+            lo_, want = next(ahead)
+            assert (lo_, hi - lo) == (lo, step)
+            return {"utens_stage": want}
+
+        F.check_slabs("generated vertical advection 1024^2x160", {"utens_stage": f["utens_stage"].tensor}, expect, axis=1, step=step,
+                      starts=starts)

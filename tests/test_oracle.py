@@ -226,3 +226,168 @@ def test_c_restatement_is_clean_under_address_and_undefined_behaviour_sanitizers
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0 and "clean under the sanitizers" in run.stdout, (run.stdout + run.stderr)[-2000:]
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+
+
+# ---- every entry point of the C restatement, pinned bit for bit ---------------------------------------------------------------
+# (tests/fullsize_util.py compares the full-size GPU results with these entry points: a full-size test is only as good as
+# its oracle.  Bit patterns are compared -- np.array_equal holds -0.0 equal to +0.0 -- and half of the inputs are quantized to
+# multiples of 1/8, which makes the flux limiter and the Laplacian produce exact zeros of either sign.)
+LAP_VARIANTS = ["notebook", "docs", "suite", "avg"]
+
+
+def _c_oracle():
+    from oracle import cpu_ifirst as C
+
+    if not C.available():
+        pytest.skip("oracle/_build/libcpu_ifirst.so not built (run __graft_entry__.build())")
+    return C
+
+
+def _inputs(rng, shape, dtype, quantized, lo=-1.0, hi=1.0):
+    a = rng.uniform(lo, hi, shape)
+    if quantized:
+        a = np.floor(a * 8) / 8
+    return np.asfortranarray(a.astype(dtype))
+
+
+def _lap5_f32_tree(inp, variant, W):
+    """The expression trees of test_gpu_kernels.py::test_lap5_f32_parity: W = dtype of the literals' promotion, the bracket
+    sums in float32."""
+    c = inp[1:-1, 1:-1]
+    w, e, s, n = inp[:-2, 1:-1], inp[2:, 1:-1], inp[1:-1, :-2], inp[1:-1, 2:]
+    if variant == 0:
+        r = ((((W(-4.0) * c.astype(W)) + w.astype(W)) + e.astype(W)) + s.astype(W)) + n.astype(W)
+    elif variant == 1:
+        r = (W(-4.0) * c.astype(W)) + (((e + w) + n) + s).astype(W)
+    elif variant == 2:
+        r = (W(4.0) * c.astype(W)) - (((e + w) + n) + s).astype(W)
+    else:
+        r = W(0.25) * (((n + s) + e) + w).astype(W)
+    return r.astype(np.float32)
+
+
+@pytest.mark.parametrize("quantized", [False, True])
+@pytest.mark.parametrize("dtype,literal32", [(np.float64, False), (np.float32, False), (np.float32, True)])
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+def test_c_lap5_every_variant_and_precision_is_pinned(variant, dtype, literal32, quantized):
+    from fullsize_util import assert_bitwise
+
+    C = _c_oracle()
+    rng = np.random.default_rng(100 + variant)
+    inp = _inputs(rng, (37, 23, 5), dtype, quantized)
+    got = np.asfortranarray(np.full(inp.shape, -7.0, dtype))
+    want = np.full(inp.shape, -7.0, dtype)
+    if dtype == np.float64:
+        R.laplacian(inp, want, variant=LAP_VARIANTS[variant])
+    else:
+        want[1:-1, 1:-1] = _lap5_f32_tree(inp, variant, np.float32 if literal32 else np.float64)
+        if literal32:  # float32 literals: the numpy restatement's own float32 arithmetic is the same tree
+            again = np.full(inp.shape, -7.0, dtype)
+            R.laplacian(inp, again, variant=LAP_VARIANTS[variant])
+            assert_bitwise(again, want, "ref_numpy vs the float32 tree")
+    C.lap5(inp, got, (1, 1, 0), (1, 1, 0), (35, 21, 5), variant=variant, literal32=literal32, threads=2)
+    assert_bitwise(got, want, f"lap5 v{variant} {np.dtype(dtype).name} literal32={literal32}")
+    # a smaller domain with an origin: nothing outside is written
+    got2 = np.asfortranarray(np.full(inp.shape, -7.0, dtype))
+    want2 = np.full(inp.shape, -7.0, dtype)
+    want2[3:3 + 20, 2:2 + 9, 1:4] = want[3:3 + 20, 2:2 + 9, 1:4]
+    C.lap5(inp, got2, (3, 2, 1), (3, 2, 1), (20, 9, 3), variant=variant, literal32=literal32, threads=2)
+    assert_bitwise(got2, want2, "sub-domain")
+
+
+def test_c_lap5_rejects_an_unknown_variant():
+    C = _c_oracle()
+    a = np.asfortranarray(np.zeros((5, 5, 1)))
+    with pytest.raises(ValueError, match="variant"):
+        C.lap5(a, a.copy(order="F"), (1, 1, 0), (1, 1, 0), (3, 3, 1), variant=4)
+
+
+@pytest.mark.parametrize("quantized", [False, True])
+@pytest.mark.parametrize("limiter", [True, False])
+@pytest.mark.parametrize("coeff", ["field", "scalar64", "scalar32"])
+@pytest.mark.parametrize("dtype,internal32", [(np.float64, False), (np.float32, False), (np.float32, True)])
+def test_c_hdiff_every_precision_and_coefficient_is_pinned(dtype, internal32, coeff, limiter, quantized):
+    """The four (W, PW) combinations csrc/hdiff.hip.h:hdiff_run dispatches to -- f64; f32 with W = PW = double; f32 with
+    W = PW = float (a field or a float32 scalar); f32 with W = float, PW = double (a float64 scalar) -- each with a field or a
+    scalar coefficient (a float32 scalar is rounded through float: HDIFF_COEFF_F32), limiter on and off."""
+    from fullsize_util import assert_bitwise
+
+    C = _c_oracle()
+    rng = np.random.default_rng(7)
+    inp = _inputs(rng, (41, 29, 4), dtype, quantized, 0.0, 10.0)
+    cf = np.asfortranarray(rng.uniform(0, 0.5, inp.shape).astype(dtype))
+    if coeff == "field":
+        c = cf
+    else:
+        c = np.float64(0.3100000001) if coeff == "scalar64" else np.float32(0.31)
+    want = np.full(inp.shape, -7.0, dtype)
+    R.hdiff(inp, want, c, limiter=limiter, literal_float_precision=32 if internal32 else 64)
+    got = np.asfortranarray(np.full(inp.shape, -7.0, dtype))
+    C.hdiff(inp, got, c, (2, 2, 0), (2, 2, 0), (2, 2, 0), (37, 25, 4), limiter=limiter, internal_f32=internal32,
+            coeff_f32=coeff == "scalar32", threads=2)
+    assert_bitwise(got, want, f"hdiff {np.dtype(dtype).name} internal32={internal32} {coeff} limiter={limiter}")
+    if quantized and limiter:  # the case exists for its ties: the limiter fires and exact zeros come out
+        assert (want[2:-2, 2:-2] == 0).any() or (want[2:-2, 2:-2] == inp[2:-2, 2:-2]).any()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_c_tridiag_is_pinned_for_both_dtypes(dtype):
+    from fullsize_util import assert_bitwise
+
+    C = _c_oracle()
+    rng = np.random.default_rng(31)
+    shape = (19, 7, 45)
+    inf, diag = (np.asfortranarray(rng.uniform(a, b, shape).astype(dtype)) for a, b in ((-1, 1), (4, 5)))
+    sup, rhs = (np.asfortranarray(rng.uniform(a, b, shape).astype(dtype)) for a, b in ((-1, 1), (-10, 10)))
+    s1, r1, o1 = sup.copy(), rhs.copy(), np.zeros(shape, dtype)
+    s2, r2, o2 = (np.asfortranarray(x.copy()) for x in (sup, rhs, np.zeros(shape, dtype)))
+    R.tridiag(inf, diag, s1, r1, o1)
+    C.tridiag(inf, diag, s2, r2, o2, shape, threads=2)
+    for name, g, w in (("out", o2, o1), ("sup", s2, s1), ("rhs", r2, r1)):
+        assert_bitwise(g, w, f"tridiag {np.dtype(dtype).name} {name}")
+
+
+# ---- the slab-wise bitwise comparison of the full-size GPU tests (tests/fullsize_util.py) ---------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_fullsize_helper_reports_one_ulp_and_a_signed_zero(dtype):
+    """Every full-size GPU case goes through fullsize_util.check_slabs: one ulp at the last point of the last (short) slab
+    and a +0.0 -> -0.0 flip must each fail it, with the point's index in array coordinates."""
+    import torch
+
+    from fullsize_util import check_slabs, host, padded
+
+    rng = np.random.default_rng(3)
+    want = rng.uniform(-1, 1, (13, 7, 10)).astype(dtype)
+    want[5, 3, 9] = 0.0
+
+    def dev(a):  # an I-contiguous tensor with padded rows, like a storage
+        base = torch.zeros((a.shape[2], a.shape[1], 16), dtype=torch.from_numpy(a).dtype)
+        t = base.permute(2, 1, 0)[: a.shape[0]]
+        t.copy_(torch.from_numpy(a))
+        return t
+
+    def expect_from(a):
+        full = host(padded(dev(a)), 2, 0, a.shape[2])  # (the padding: zeros, as in dev())
+        return lambda lo, hi: {"out": full[:, :, lo:hi]}
+
+    check_slabs("identical", {"out": dev(want)}, expect_from(want), axis=2, step=3)  # slabs of 3, 3, 3, 1 levels
+    ulp = want.copy()
+    ulp[12, 6, 9] = np.nextafter(ulp[12, 6, 9], np.inf, dtype=dtype)
+    with pytest.raises(AssertionError) as e:
+        check_slabs("one ulp", {"out": dev(ulp)}, expect_from(want), axis=2, step=3)
+    msg = str(e.value)
+    assert "1 mismatching point" in msg and "(12, 6, 9)" in msg and "not only sign-of-zero" in msg, msg
+    neg = want.copy()
+    neg[5, 3, 9] = -0.0
+    with pytest.raises(AssertionError) as e:
+        check_slabs("signed zero", {"out": dev(neg)}, expect_from(want), axis=2, step=3)
+    msg = str(e.value)
+    assert "1 mismatching point" in msg and "(5, 3, 9)" in msg and "every one of them a sign-of-zero" in msg, msg
+    # a write into the padding after the last column of a row is seen too
+    t = dev(want)
+    padded(t)[14, 2, 4] = 1.0
+    with pytest.raises(AssertionError, match=r"\(14, 2, 4\)"):
+        check_slabs("padding", {"out": t}, expect_from(want), axis=2, step=3)
+    # slabs along J, a selection of them
+    check_slabs("J", {"out": dev(want)}, lambda lo, hi: {"out": expect_from(want)(0, 10)["out"][:, lo:hi]}, axis=1, step=2,
+                starts=[0, 6])
