@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_tridiag_f32",
     "gt4mi_halo_pack",
     "gt4mi_halo_unpack",
+    "gt4mi_halo_fill",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -74,7 +75,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_memory_write_probe",
 )
 
-GT4MI_ABI_VERSION = 7
+GT4MI_ABI_VERSION = 8
 
 # gt4mi_status
 OK = 0
@@ -91,6 +92,9 @@ LAP_LITERAL_F32 = 1
 PLAN_SCHEDULE, PLAN_INTERIOR_WG_PER_CU, PLAN_DEFER_JOIN, PLAN_EDGE_COLUMNS, PLAN_TRANSPORT, PLAN_DIRECT_TIMEOUT_MS, PLAN_DIRECT_FENCED = 0, 1, 2, 3, 4, 5, 6
 TRANSPORT_RCCL, TRANSPORT_DIRECT = 0, 1
 SCHEDULE_JOIN, SCHEDULE_CHAIN, SCHEDULE_SWAP, SCHEDULE_SWAP_PACKED, SCHEDULE_INLINE = 0, 1, 2, 3, 4
+# gt4mi_halo_fill: modes, sides
+HALO_NONE, HALO_PERIODIC, HALO_ZERO_GRADIENT, HALO_SYMMETRIC, HALO_REFLECT, HALO_CONSTANT = 0, 1, 2, 3, 4, 5
+HALO_I_LO, HALO_I_HI, HALO_J_LO, HALO_J_HI, HALO_ALL_SIDES, HALO_DRY_RUN = 1, 2, 4, 8, 15, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -190,6 +194,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_halo_pack.argtypes = [FP, DOM, DOM, P, I, P]
     lib.gt4mi_halo_unpack.restype = I
     lib.gt4mi_halo_unpack.argtypes = [FP, DOM, DOM, P, I, P]
+    lib.gt4mi_halo_fill.restype = I
+    lib.gt4mi_halo_fill.argtypes = [FP, I, DOM, DOM, I, I, I, P, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

@@ -10,6 +10,7 @@
 #include "comm.hip.h"
 #include "common.hip.h"
 #include "halo.hip.h"
+#include "halo_fill.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -466,6 +467,12 @@ int gt4mi_halo_unpack(const gt4mi_field* field, const int64_t lo[3], const int64
     if (elem_size == 8) return gt4mi::halo_copy<uint64_t, false>(field, lo, extent, b, s);
     if (elem_size == 4) return gt4mi::halo_copy<uint32_t, false>(field, lo, extent, b, s);
     return gt4mi::fail(GT4MI_ERR_UNSUPPORTED, "halo_unpack: element size %d", elem_size);
+}
+
+int gt4mi_halo_fill(const gt4mi_field* fields, int nfields, const int64_t domain[3], const int64_t halo[4], int mode_i,
+                    int mode_j, int sides, const void* value, int elem_size, void* stream, int* launches) {
+    return gt4mi::halo_fill(fields, nfields, domain, halo, mode_i, mode_j, sides, value, elem_size,
+                            static_cast<hipStream_t>(stream), launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

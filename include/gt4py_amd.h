@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define GT4MI_ABI_VERSION 7 /* 7: gt4mi_memory_write_probe (which memory group an allocation lives in); 6: GT4MI_PLAN_DIRECT_FENCED (release / acquire fences around the flags of the direct transport); 5: GT4MI_ERR_TIMEOUT (a direct-transport wait that runs out fails the plan, hard), GT4MI_PLAN_DIRECT_TIMEOUT_MS; 4: gt4mi_dist_lap5_f32, the direct transport (gt4mi_halo_plan_direct_*, GT4MI_PLAN_TRANSPORT), gt4mi_comm_create_local, schedules 2-4 */
+#define GT4MI_ABI_VERSION 8 /* 8: gt4mi_halo_fill (boundary conditions on the I/J ghost cells, one launch); 7: gt4mi_memory_write_probe (which memory group an allocation lives in); 6: GT4MI_PLAN_DIRECT_FENCED (release / acquire fences around the flags of the direct transport); 5: GT4MI_ERR_TIMEOUT (a direct-transport wait that runs out fails the plan, hard), GT4MI_PLAN_DIRECT_TIMEOUT_MS; 4: gt4mi_dist_lap5_f32, the direct transport (gt4mi_halo_plan_direct_*, GT4MI_PLAN_TRANSPORT), gt4mi_comm_create_local, schedules 2-4 */
 
 typedef enum gt4mi_status {
     GT4MI_OK = 0,
@@ -157,6 +157,37 @@ int gt4mi_halo_pack(const gt4mi_field* field, const int64_t lo[3], const int64_t
                     void* buffer, int elem_size, void* stream);
 int gt4mi_halo_unpack(const gt4mi_field* field, const int64_t lo[3], const int64_t extent[3],
                       const void* buffer, int elem_size, void* stream);
+
+/* ---- boundary-condition halo fill (ABI 8; NEW: no reference counterpart -- gt4py leaves boundary conditions to array slicing on
+ * its numpy / cupy storages) --------------------------------------------------------------------------------------------------
+ * Fills the I/J ghost cells of `nfields` fields (each with its own pointer, strides and origin; all of item size `elem_size` =
+ * 1, 2, 4 or 8) from their own compute domain [origin, origin + domain), in ONE kernel launch per 8 fields, on `stream`, without
+ * synchronisation or allocation.  Bit patterns are moved, nothing is computed: bool and integer fields work, NaN payloads and
+ * the sign of zero survive.  K is never extended; a Field[IJ] is domain[2] = 1 with K stride 0; a field whose I or J stride
+ * is 0 is refused.
+ *   halo     {lo_i, hi_i, lo_j, hi_j} >= 0, inside every array: lo <= origin, origin + domain + hi <= shape.
+ *   mode_i, mode_j   per axis; the index (relative to the domain, n cells) a ghost cell at distance d >= 1 takes its value from:
+ *              GT4MI_HALO_NONE           axis not touched
+ *              GT4MI_HALO_PERIODIC       low: n - d      high: d - 1       (numpy.pad "wrap";      widths <= n)
+ *              GT4MI_HALO_ZERO_GRADIENT  low: 0          high: n - 1       (numpy.pad "edge")
+ *              GT4MI_HALO_SYMMETRIC      low: d - 1      high: n - d       (numpy.pad "symmetric"; widths <= n)
+ *              GT4MI_HALO_REFLECT        low: d          high: n - 1 - d   (numpy.pad "reflect";   widths <= n - 1)
+ *              GT4MI_HALO_CONSTANT       *value (one item of elem_size bytes for the call)         (numpy.pad "constant")
+ *            A width beyond the bound of its mode is GT4MI_ERR_INVALID_ARGUMENT (numpy.pad iterates there; this does not).
+ *   sides    bit mask of GT4MI_HALO_I_LO | _I_HI | _J_LO | _J_HI: a decomposed caller fills the sides without a neighbour.
+ *            With GT4MI_HALO_DRY_RUN every check runs and *launches is set, nothing is enqueued.
+ * The result is "the I sides first, then the J sides over the whole padded I range [origin - lo_i, origin + domain + hi_i)",
+ * which is how numpy.pad treats axes: a corner cell is written iff its J side is selected and mode_j != NONE; it holds *value
+ * for mode_j CONSTANT, else the cell (map_i(i), map_j(j)) (or *value for mode_i CONSTANT) where its I side is selected and
+ * mode_i != NONE, else the CURRENT content of (i, map_j(j)): the ghost column as the caller left it, e.g. a halo exchange that
+ * ran just before.  No other byte of the arrays changes.  The fields of one call must not overlap one another.
+ * Every check runs before the first launch.  *launches (may be NULL) = the kernels the call enqueued. */
+enum { GT4MI_HALO_NONE = 0, GT4MI_HALO_PERIODIC = 1, GT4MI_HALO_ZERO_GRADIENT = 2, GT4MI_HALO_SYMMETRIC = 3, GT4MI_HALO_REFLECT = 4,
+       GT4MI_HALO_CONSTANT = 5 };
+enum { GT4MI_HALO_I_LO = 1, GT4MI_HALO_I_HI = 2, GT4MI_HALO_J_LO = 4, GT4MI_HALO_J_HI = 8, GT4MI_HALO_ALL_SIDES = 15,
+       GT4MI_HALO_DRY_RUN = 256 };
+int gt4mi_halo_fill(const gt4mi_field* fields, int nfields, const int64_t domain[3], const int64_t halo[4], int mode_i,
+                    int mode_j, int sides, const void* value, int elem_size, void* stream, int* launches);
 
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
