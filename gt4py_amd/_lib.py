@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_halo_pack",
     "gt4mi_halo_unpack",
     "gt4mi_halo_fill",
+    "gt4mi_field_stats",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -95,6 +96,9 @@ SCHEDULE_JOIN, SCHEDULE_CHAIN, SCHEDULE_SWAP, SCHEDULE_SWAP_PACKED, SCHEDULE_INL
 # gt4mi_halo_fill: modes, sides
 HALO_NONE, HALO_PERIODIC, HALO_ZERO_GRADIENT, HALO_SYMMETRIC, HALO_REFLECT, HALO_CONSTANT = 0, 1, 2, 3, 4, 5
 HALO_I_LO, HALO_I_HI, HALO_J_LO, HALO_J_HI, HALO_ALL_SIDES, HALO_DRY_RUN = 1, 2, 4, 8, 15, 256
+# gt4mi_field_stats: slots of a result row, flags
+STATS_COUNT, STATS_NONFINITE, STATS_SUM, STATS_SUM_ABS, STATS_SUM_SQ, STATS_MIN, STATS_MAX, STATS_DOT, STATS_SLOTS = range(9)
+STATS_DRY_RUN = 1
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -196,6 +200,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_halo_unpack.argtypes = [FP, DOM, DOM, P, I, P]
     lib.gt4mi_halo_fill.restype = I
     lib.gt4mi_halo_fill.argtypes = [FP, I, DOM, DOM, I, I, I, P, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_field_stats.restype = I
+    lib.gt4mi_field_stats.argtypes = [FP, FP, I, DOM, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64),
+                                      ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

@@ -11,6 +11,7 @@
 #include "common.hip.h"
 #include "halo.hip.h"
 #include "halo_fill.hip.h"
+#include "field_stats.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -473,6 +474,13 @@ int gt4mi_halo_fill(const gt4mi_field* fields, int nfields, const int64_t domain
                     int mode_j, int sides, const void* value, int elem_size, void* stream, int* launches) {
     return gt4mi::halo_fill(fields, nfields, domain, halo, mode_i, mode_j, sides, value, elem_size,
                             static_cast<hipStream_t>(stream), launches);
+}
+
+int gt4mi_field_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int elem_size,
+                      void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
+                      int64_t* workspace_needed, int* launches) {
+    return gt4mi::field_stats(fields, others, nfields, domain, elem_size, workspace, workspace_bytes, result, flags,
+                              static_cast<hipStream_t>(stream), workspace_needed, launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

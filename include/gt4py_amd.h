@@ -189,6 +189,36 @@ enum { GT4MI_HALO_I_LO = 1, GT4MI_HALO_I_HI = 2, GT4MI_HALO_J_LO = 4, GT4MI_HALO
 int gt4mi_halo_fill(const gt4mi_field* fields, int nfields, const int64_t domain[3], const int64_t halo[4], int mode_i,
                     int mode_j, int sides, const void* value, int elem_size, void* stream, int* launches);
 
+/* ---- field statistics (NEW: no reference counterpart -- gt4py leaves reductions to numpy / cupy on its numpy / cupy storages) ------
+ * One pass over the compute domain [origin, origin + domain) of `nfields` entries, 8 per launch, plus ONE finishing launch, on
+ * `stream`, without synchronisation or allocation.  Entry n is fields[n] and, where `others` is not NULL and others[n].data is not
+ * NULL, a second field others[n] of the same item size (`elem_size` = 4: float32, 8: float64).  x = a, or a - b rounded once in
+ * float64; ALL arithmetic is float64.  result[n * 8 + slot] (device memory, float64):
+ *   GT4MI_STATS_COUNT      number of domain points                      GT4MI_STATS_NONFINITE  points where x is NaN or +-Inf
+ *   GT4MI_STATS_SUM        sum of x            GT4MI_STATS_SUM_ABS  sum of |x|            GT4MI_STATS_SUM_SQ  sum of x * x
+ *   GT4MI_STATS_MIN / _MAX min / max of x: NaN if any x is NaN (as numpy.min; payload and sign unspecified), min(-0, +0) = -0 and
+ *                          max(-0, +0) = +0, so they do not depend on the order
+ *   GT4MI_STATS_DOT        sum of a * b with a second field, else 0
+ * THE ORDER OF THE ADDITIONS IS PART OF THE CONTRACT: it is a function of `domain` alone (csrc/field_stats.hip.h states it,
+ * tests/stats_ref.py restates it in numpy) -- not of pointers, strides, padding, alignment, the number of entries in the call or
+ * anything about the device.  The same domain data gives the same bits, always.
+ * A second field may have byte stride 0 along an axis: a lower-dimensional weight (an IJ cell-area field against an IJK field
+ * for sum a * area), exempt from the shape check on that axis; `fields` may not.  With a weight the slots other than _DOT still
+ * describe a - b: for sum a * w next to the statistics of `a` itself pass `a` twice, once alone and once with w (two entries, one
+ * launch).
+ *   workspace   device memory for the tiles' partial results, 8-byte aligned, *workspace_needed bytes (a function of nfields and
+ *               domain; at most nfields * 256 KiB); `result` and `workspace` must not overlap the fields or one another
+ *   flags       GT4MI_STATS_DRY_RUN: every check runs, *workspace_needed and *launches are set, nothing is enqueued; workspace and
+ *               result may then be NULL (which is how to ask for the size)
+ * Every check runs before the first launch; a refused call enqueues nothing.  *launches (may be NULL) = the kernels the call
+ * enqueues: ceil(nfields / 8) + 1. */
+enum { GT4MI_STATS_COUNT = 0, GT4MI_STATS_NONFINITE = 1, GT4MI_STATS_SUM = 2, GT4MI_STATS_SUM_ABS = 3, GT4MI_STATS_SUM_SQ = 4,
+       GT4MI_STATS_MIN = 5, GT4MI_STATS_MAX = 6, GT4MI_STATS_DOT = 7, GT4MI_STATS_SLOTS = 8 };
+enum { GT4MI_STATS_DRY_RUN = 1 };
+int gt4mi_field_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int elem_size,
+                      void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
+                      int64_t* workspace_needed, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
