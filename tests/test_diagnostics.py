@@ -14,6 +14,8 @@ from gt4py_amd import _lib, diagnostics
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 U = 2.0 ** -53
+# domain -> (rows, rows per wave, tiles, tiles per finish leaf, finish leaves)
+SEVERAL_ROWS_PER_WAVE = {(5, 130, 130): (16900, 2, 2113, 17, 125), (3, 257, 129): (33153, 3, 2763, 22, 126)}
 
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
@@ -118,7 +120,7 @@ def test_dry_run_reports_workspace_and_launches():
         rc, msg, launches, needed = _call(many, nfields=n, workspace=None, result=None)  # asking for the size
         assert rc == 0 and launches == want and needed == n * NEEDED, (n, msg)
     # the workspace follows the tile partition of the restatement, a function of the domain alone, at most 4096 tiles
-    for domain in ((512, 512, 128), (1024, 1024, 80), (17, 33, 5), (3, 70000, 3)):
+    for domain in ((512, 512, 128), (1024, 1024, 80), (17, 33, 5), (3, 70000, 3)) + tuple(SEVERAL_ROWS_PER_WAVE):
         big = ctypes.byref(_field(shape=domain, strides=(8, 8 * domain[0], 8 * domain[0] * domain[1]), origin=(0, 0, 0)))
         rc, msg, launches, needed = _call(big, domain=domain, workspace=None, result=None)
         tiles = R.geometry(domain)[2]
@@ -141,6 +143,21 @@ def test_the_kernels_are_in_the_resource_log_and_use_no_scratch():
 
 # ---- the restatement against exact arithmetic -------------------------------------------------------------------------------
 DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2), (700, 5, 3), (8, 300, 70)]
+DOMAINS += list(SEVERAL_ROWS_PER_WAVE)
+
+
+def test_geometry_of_the_domains_with_several_rows_per_wave():
+    """What tests/test_gpu_diagnostics.py compares bit for bit beyond one row per wave; the C entry's workspace (64 bytes per tile)
+    pins the same partition on the library's side (test_dry_run_reports_workspace_and_launches)."""
+    for domain, want in SEVERAL_ROWS_PER_WAVE.items():
+        rows, rw, tiles, chunks, per_leaf, leaves = R.geometry(domain)
+        assert (rows, rw, tiles, per_leaf, leaves) == want and chunks == 1, (domain, R.geometry(domain))
+        assert rw > 1 and per_leaf > 16 and rows % (R.WAVES * rw) != 0  # a last tile whose last waves have fewer rows, or none
+        level, odd = leaves, []
+        while level > 1:
+            odd.append(level % 2 == 1)
+            level = (level + 1) // 2
+        assert any(odd), (domain, leaves)  # an odd number of leaves somewhere on the way up: one is carried unchanged
 
 
 def _exact_int(a, b=None):

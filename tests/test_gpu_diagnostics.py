@@ -17,7 +17,7 @@ import stats_ref as R  # noqa: E402
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
 DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2)]  # test_gpu_kernels.py's
-DOMAINS += [(128, 128, 64), (700, 5, 3)]  # (700 columns: more than the 256 a wave covers at once)
+DOMAINS += [(128, 128, 64), (700, 5, 3)]  # (700 columns: more than the 256 a wave covers at once; all of them: one row per wave)
 LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
 U = 2.0 ** -53
 
@@ -79,6 +79,38 @@ def test_every_slot_bit_for_bit_against_the_restatement(dtype, halo):
                 assert R.same_bits(got[n], want[n]), f"{domain} {dtype.__name__} {layout} halo {halo} {what}: {got[n]} != {want[n]}"
             torch.cuda.synchronize()
             assert all(torch.equal(_bits(d._flat), x) for d, x in zip((da, db, dw), before)), "a field buffer changed"
+
+
+# domain -> (rows, rows per wave, tiles, tiles per finish leaf, finish leaves): 2 and 3 rows per wave, 17 and 22 tiles per leaf, an odd
+# number of leaves on the way up (125; 126 -> 63), a last tile whose last waves have fewer rows than the others
+SEVERAL_ROWS_PER_WAVE = {(5, 130, 130): (16900, 2, 2113, 17, 125), (3, 257, 129): (33153, 3, 2763, 22, 126)}
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("halo", [0, 2])
+def test_every_slot_bit_for_bit_with_several_rows_per_wave(dtype, halo):
+    """The order of the additions beyond one row per wave -- a lane's chain over its wave's rows, leaves of more than 16 tiles,
+    an odd leaf carried up the halving tree -- on data whose sums depend on that order; single field, pair, pair with an IJ
+    weight.  The geometry is asserted: a change of the constants must not move these cases back to one row per wave."""
+    from gt4py_amd import diagnostics
+
+    rng = np.random.default_rng(50 + halo)
+    for domain, geometry in SEVERAL_ROWS_PER_WAVE.items():
+        rows, rw, tiles, _, per_leaf, leaves = R.geometry(domain)
+        assert (rows, rw, tiles, per_leaf, leaves) == geometry and rw > 1, R.geometry(domain)
+        a, b = _data(rng, domain, dtype), _data(rng, domain, dtype)
+        w = rng.uniform(0.5, 2.0, domain[:2] + (1,)).astype(dtype)
+        want = [R.stats(a), R.stats(a, b), R.stats(a, w)]
+        assert len({x.tobytes() for x in want}) == 3
+        for layout in ("ifirst", "kfirst"):
+            arrays = [_wrap(_device(x, layout, halo)) for x in (a, b, w)]
+            weight = arrays[2][:, :, 0]  # Field[IJ] against Field[IJK]; (the frozen call holds its arrays weakly: keep it)
+            frozen = diagnostics.FieldStats([arrays[0]] * 3, others=[None, arrays[1], weight], halo=halo)
+            assert frozen.domain == domain and frozen.launches == 2
+            assert frozen._workspace_bytes == 3 * tiles * 64  # the library derived the same partition: 64 bytes per tile and entry
+            got = _rows(frozen)
+            for n, what in enumerate(("field", "pair", "weight")):
+                assert R.same_bits(got[n], want[n]), f"{domain} {dtype.__name__} {layout} halo {halo} {what}: {got[n]} != {want[n]}"
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

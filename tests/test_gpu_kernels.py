@@ -10,6 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import edge_values as E  # noqa: E402
 from oracle import ref_numpy as R  # noqa: E402  (oracle = checker only)
 
 DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2)]
@@ -17,10 +18,8 @@ LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
 
 
 def _eq(got, want, what=""):
-    if not np.array_equal(got, want, equal_nan=True):
-        diff = np.nanmax(np.abs(got.astype(np.float64) - want.astype(np.float64)))
-        nbad = int((~((got == want) | (np.isnan(got) & np.isnan(want)))).sum())
-        raise AssertionError(f"{what}: {nbad} mismatching elements, max abs diff {diff:.3e}")
+    """Bit for bit (tests/edge_values.py): the sign of a zero counts, NaN matches NaN; the report counts the mismatches by class."""
+    E.same_bits(got, want, what)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -214,7 +213,7 @@ def test_hdiff_plane_is_identity():
     d_in = G.DevArray(plane, "ifirst", align_index=(2, 2, 0))
     d_out = G.DevArray(np.zeros_like(plane), "ifirst", align_index=(2, 2, 0))
     G.hdiff(d_in, d_out, 0.4, (2, 2, 0), (2, 2, 0), None, (32, 24, 3), _lib.HDIFF_LIMITER)
-    assert np.array_equal(d_out.get()[2:-2, 2:-2], plane[2:-2, 2:-2])
+    E.same_bits(d_out.get()[2:-2, 2:-2], plane[2:-2, 2:-2], "hdiff of a plane")
 
 
 def test_hdiff_nan_and_inf_propagate_like_numpy():
@@ -412,7 +411,7 @@ def test_hdiff_ring_equals_the_whole_domain_kernel_on_the_ring(domain, widths, d
         mask = _ring_mask(shape, (2, 2, 0), domain, (0, 0, 0, 0), widths)
         want = np.where(mask[:, :, None], want_full, sentinel)
         got = d_o.get()
-        assert np.array_equal(got, want), (flags, np.argwhere(got != want)[:5])
+        E.same_bits(got, want, f"hdiff ring {domain} {widths} {layout} flags {flags}")
 
 
 @pytest.mark.parametrize("layout", ["ifirst", "ifirst_unaligned", "jfirst"])
@@ -439,7 +438,7 @@ def test_lap5_ring_equals_the_whole_domain_kernel_on_the_ring(domain, outer, inn
     mask = _ring_mask(shape, (H, H, 0), domain, outer, inner)
     want = np.where(mask[:, :, None], want_full, sentinel)
     got = d_o.get()
-    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+    E.same_bits(got, want, f"lap5 ring {domain} {outer} {inner} {layout} v{variant}")
 
 
 @pytest.mark.parametrize("domain", [(512, 9, 3), (511, 6, 2), (513, 5, 2), (1030, 5, 2), (126, 20, 4), (640, 4, 2)])
