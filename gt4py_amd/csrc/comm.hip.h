@@ -320,24 +320,88 @@ inline int first_phase(const gt4mi_halo_plan* plan) {
     return 2;
 }
 
-// Pack the faces of the first non-empty phase only (they depend on nothing but the field itself,
-// so a caller can enqueue this ahead of its interior kernel).
 inline int direct_push(gt4mi_halo_plan* plan, const gt4mi_field* field, int phase, hipStream_t s);    // direct.hip.h
 inline int direct_unpack(gt4mi_halo_plan* plan, const gt4mi_field* field, int phase, hipStream_t s);
 inline int direct_failed(const gt4mi_halo_plan* plan);
 
+// How a fused distributed step is laid out on the two streams, and how far the interior kernel is throttled while the
+// exchange runs next to it: the plan's options (gt4mi_halo_plan_set_option), else the entry point's default -- measured on
+// the 1-GPU self-loop, profiles/r3_dist_*_timeline*.txt.
+inline int plan_schedule(const gt4mi_halo_plan* plan, int fallback) {
+    return plan->schedule >= 0 ? plan->schedule : fallback;
+}
+inline int plan_edge_columns(const gt4mi_halo_plan* plan, int fallback) {
+    return plan->edge_columns >= 0 ? plan->edge_columns : fallback;
+}
+inline int plan_interior_wg_per_cu(const gt4mi_halo_plan* plan, int fallback) {
+    return plan->interior_wg_per_cu >= 0 ? plan->interior_wg_per_cu : fallback;
+}
+
+// ---- the plan's event pair: the ONLY code that records or waits for `ready` / `done` ----
+// The side stream starts behind everything the caller's stream holds so far (in two halves for gt4mi_halo_exchange_fork / _begin).
+inline int record_ready(gt4mi_halo_plan* plan, hipStream_t main_stream) {
+    GT4MI_HIP_CHECK(hipEventRecord(plan->ready, main_stream));
+    return GT4MI_OK;
+}
+inline int side_waits_ready(gt4mi_halo_plan* plan) {
+    GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
+    return GT4MI_OK;
+}
+inline int fork_side(gt4mi_halo_plan* plan, hipStream_t main_stream) {
+    if (int rc = record_ready(plan, main_stream)) return rc;
+    return side_waits_ready(plan);
+}
+// What the side stream holds so far is what a later join waits for.
+inline int mark_done(gt4mi_halo_plan* plan) {
+    GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
+    plan->done_recorded = true;
+    return GT4MI_OK;
+}
+inline int wait_done(gt4mi_halo_plan* plan, hipStream_t main_stream) {
+    GT4MI_HIP_CHECK(hipStreamWaitEvent(main_stream, plan->done, 0));
+    return GT4MI_OK;
+}
+// The caller's stream waits for the side stream (gt4mi_halo_exchange_end).
+inline int join_side_now(gt4mi_halo_plan* plan, hipStream_t main_stream) {
+    if (int rc = direct_failed(plan)) return rc;  // a wait of an EARLIER exchange ran out of time: say so now
+    if (!plan->done_recorded) return GT4MI_OK;    // nothing was ever put in flight on the side stream
+    return wait_done(plan, main_stream);
+}
+// ... unless the plan leaves the join to the caller's gt4mi_halo_exchange_end (GT4MI_PLAN_DEFER_JOIN)
+inline int join_side(gt4mi_halo_plan* plan, hipStream_t main_stream) {
+    return plan->defer_join ? GT4MI_OK : join_side_now(plan, main_stream);
+}
+
+// Direct transport: `launch(&launched)` carries the push of an exchange's first phase.  The push reads the exchange counter, so
+// it is advanced first -- and taken back when nothing was launched: the counters then still agree with the neighbours'.
+// `whole_exchange`: the launch unpacks as well, nothing is left for halo_exchange_on.
+template <typename Launch>
+inline int direct_first_push(gt4mi_halo_plan* plan, bool whole_exchange, bool* launched, Launch&& launch) {
+    *launched = false;
+    ++plan->direct.step;
+    const int rc = launch(launched);
+    if (rc != GT4MI_OK || !*launched) {
+        *launched = false;
+        --plan->direct.step;
+        return rc;
+    }
+    plan->direct.first_pushed = !whole_exchange;
+    return GT4MI_OK;
+}
+
+// Pack the faces of the first non-empty phase only (they depend on nothing but the field itself,
+// so a caller can enqueue this ahead of its interior kernel).
 inline int halo_pack_first(gt4mi_halo_plan* plan, const gt4mi_field* field, hipStream_t s) {
     const int p = first_phase(plan);
     if (p > 1) return GT4MI_OK;
     if (plan->transport == GT4MI_TRANSPORT_DIRECT) {  // the pack IS the transfer
         if (int rc = direct_failed(plan)) return rc;
-        ++plan->direct.step;  // (the push reads it)
-        if (int rc = direct_push(plan, field, p, s)) {
-            --plan->direct.step;  // nothing was launched: the counters still agree with the neighbours'
+        bool pushed = false;
+        return direct_first_push(plan, /*whole_exchange=*/false, &pushed, [&](bool* launched) {
+            const int rc = direct_push(plan, field, p, s);
+            *launched = rc == GT4MI_OK;
             return rc;
-        }
-        plan->direct.first_pushed = true;
-        return GT4MI_OK;
+        });
     }
     return plan_copy<true>(plan, field, plan->sends[p], s);
 }

@@ -21,21 +21,7 @@
 #include "lap5_edge.hip.h"
 #include "rtc.hip.h"
 #include "tridiag.hip.h"
-
-namespace gt4mi {
-// How a fused distributed step is laid out on the two streams, and how far the interior kernel is throttled while the
-// exchange runs next to it: the plan's options (gt4mi_halo_plan_set_option), else the entry point's default -- measured on
-// the 1-GPU self-loop, profiles/r3_dist_*_timeline*.txt.
-inline int plan_schedule(const gt4mi_halo_plan* plan, int fallback) {
-    return plan->schedule >= 0 ? plan->schedule : fallback;
-}
-inline int plan_edge_columns(const gt4mi_halo_plan* plan, int fallback) {
-    return plan->edge_columns >= 0 ? plan->edge_columns : fallback;
-}
-inline int plan_interior_wg_per_cu(const gt4mi_halo_plan* plan, int fallback) {
-    return plan->interior_wg_per_cu >= 0 ? plan->interior_wg_per_cu : fallback;
-}
-}  // namespace gt4mi
+#include "dist_step.hip.h"
 
 namespace {
 
@@ -84,273 +70,6 @@ struct Timer {
         return ev[0] != nullptr;
     }
 };
-
-}  // namespace
-
-namespace {
-template <typename T>
-int dist_hdiff(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* in_field, const gt4mi_field* out_field,
-               const gt4mi_field* coeff, double coeff_scalar, int flags, int sides, void* main_stream) {
-    if (plan == nullptr || in_field == nullptr || out_field == nullptr || domain == nullptr)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_hdiff: null argument");
-    if (plan->elem_size != (int)sizeof(T))
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_hdiff: the plan moves %d-byte items, the fields hold %d-byte items",
-                           plan->elem_size, (int)sizeof(T));
-    hipStream_t ms = static_cast<hipStream_t>(main_stream);
-    if (int rc = gt4mi::direct_failed(plan)) return rc;
-    if (int rc = gt4mi::ensure_concurrent_stream(plan, ms)) return rc;
-    const int64_t di = domain[0], dj = domain[1], dk = domain[2];
-    constexpr int64_t H = 2;  // the stencil's reach
-    // W / E: the ring takes a box EW >= 2 columns wide (whole cache lines, J-march strips; hdiff_ring.hip.h) off the interior
-    // kernel -- even, so that both parts keep their 16-byte alignment; only where the interior keeps at least as much
-    int64_t EW = gt4mi::plan_edge_columns(plan, 16);
-    EW = EW < H ? H : EW - EW % 2;
-    if (di < 4 * EW) EW = H;
-    int64_t lo_i = (sides & 1) ? EW : 0, hi_i = (sides & 2) ? EW : 0, lo_j = (sides & 4) ? H : 0, hi_j = (sides & 8) ? H : 0;
-    lo_i = lo_i < di ? lo_i : di;
-    hi_i = hi_i < di - lo_i ? hi_i : di - lo_i;
-    lo_j = lo_j < dj ? lo_j : dj;
-    hi_j = hi_j < dj - lo_j ? hi_j : dj - lo_j;
-    // refuse what the ring would refuse BEFORE anything is enqueued (bounds, aliases): an empty ring validates only
-    const int none[4] = {0, 0, 0, 0};
-    if (int rc = gt4mi::hdiff_ring_run<T>(domain, in_field, out_field, coeff, coeff_scalar, flags, none, ms)) return rc;
-    const int widths[4] = {(int)lo_i, (int)hi_i, (int)lo_j, (int)hi_j};
-    auto interior = [&](hipStream_t st) -> int {
-        if (!(di - lo_i - hi_i > 0 && dj - lo_j - hi_j > 0 && dk > 0)) return GT4MI_OK;
-        gt4mi_field a = *in_field, b = *out_field, c;
-        a.origin[0] += lo_i; a.origin[1] += lo_j;
-        b.origin[0] += lo_i; b.origin[1] += lo_j;
-        if (coeff) {
-            c = *coeff;
-            c.origin[0] += lo_i; c.origin[1] += lo_j;
-        }
-        const int64_t sub[3] = {di - lo_i - hi_i, dj - lo_j - hi_j, dk};
-        // 2 of 4 workgroups per CU: the send/recv kernel next to it takes 59 us instead of 190 (3 of 4: 77;
-        // profiles/r3_dist_hdiff_timeline_by_schedule_and_throttle.txt, r3_dist_hdiff_edge_width_sweep.txt)
-        gt4mi::ScopedLaunchLds throttle(gt4mi::lds_for_workgroups_per_cu(gt4mi::plan_interior_wg_per_cu(plan, 2)));
-        return gt4mi::hdiff_run<T>(sub, &a, &b, coeff ? &c : nullptr, coeff_scalar, flags, st);
-    };
-    const int schedule = gt4mi::plan_schedule(plan, GT4MI_SCHEDULE_CHAIN);
-    if (schedule == GT4MI_SCHEDULE_INLINE) {  // one stream, no event (see dist_lap5)
-        if (int rc = gt4mi::halo_pack_first(plan, in_field, ms)) return rc;
-        if (int rc = interior(ms)) return rc;
-        if (int rc = gt4mi::halo_exchange_on(plan, in_field, ms, /*first_pack_done=*/true)) return rc;
-        return gt4mi::hdiff_ring_run<T>(domain, in_field, out_field, coeff, coeff_scalar, flags, widths, ms);
-    }
-    if (schedule == GT4MI_SCHEDULE_SWAP || schedule == GT4MI_SCHEDULE_SWAP_PACKED) {
-        // Schedules "swap" / "swap-packed" (see gt4mi_dist_lap5_f64): the chain pack -> send/recv -> unpack -> ring back to back
-        // on the CALLER's stream, the interior kernel on the side stream -- forked off before the pack, or after it so that the
-        // send/recv kernel starts ahead of the interior's ramp-up; the caller's stream joins the interior at the end.
-        if (schedule == GT4MI_SCHEDULE_SWAP_PACKED) {
-            if (int rc = gt4mi::halo_pack_first(plan, in_field, ms)) return rc;
-            GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-            GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-            if (int rc = gt4mi::halo_exchange_on(plan, in_field, ms, /*first_pack_done=*/true)) return rc;
-            if (int rc = interior(plan->stream)) return rc;
-        } else {
-            GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-            GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-            if (int rc = interior(plan->stream)) return rc;
-            if (int rc = gt4mi::halo_exchange_on(plan, in_field, ms)) return rc;
-        }
-        GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-        if (int rc = gt4mi::hdiff_ring_run<T>(domain, in_field, out_field, coeff, coeff_scalar, flags, widths, ms)) return rc;
-        if (!plan->defer_join) GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-        return GT4MI_OK;
-    }
-    if (schedule == GT4MI_SCHEDULE_CHAIN) {
-        // Schedule "chain": the main stream carries NOTHING but the interior kernel; pack -> send/recv -> unpack -> ring run
-        // in order on the side stream (the ring writes out_field's ring, the interior its interior).  No cross-stream wait
-        // lies on the critical path: the join after the interior is already satisfied when the chain fits under it, and
-        // back-to-back applies run their interiors back to back (profiles/r3_dist_hdiff_timeline_*.txt).
-        GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-        GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-        if (int rc = interior(ms)) return rc;
-        if (int rc = gt4mi::halo_exchange_on(plan, in_field, plan->stream)) return rc;
-        if (int rc = gt4mi::hdiff_ring_run<T>(domain, in_field, out_field, coeff, coeff_scalar, flags, widths, plan->stream)) return rc;
-        GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-        if (!plan->defer_join) GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-        return GT4MI_OK;
-    }
-    // Schedule "join": 1. pack the first faces on the main stream, ahead of the interior kernel (alone: ~5 us; next to it: 20+)
-    if (int rc = gt4mi::halo_pack_first(plan, in_field, ms)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-    // 2. main stream: the interior, which reads no ghost cell
-    if (int rc = interior(ms)) return rc;
-    // 3. side stream: send / receive / unpack (and the second phase of a two-phase plan) next to the interior kernel
-    if (int rc = gt4mi::halo_exchange_on(plan, in_field, plan->stream, /*first_pack_done=*/true)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-    // 4. main stream: join, then the ring that reads the ghost cells -- one launch for all four boxes
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-    return gt4mi::hdiff_ring_run<T>(domain, in_field, out_field, coeff, coeff_scalar, flags, widths, ms);
-}
-// One distributed apply of a 5-point stencil (gt4mi_dist_lap5_f64 / _f32): T the fields' type, W the type its literals have.
-template <typename T, typename W>
-int dist_lap5(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* inp, const gt4mi_field* out, int variant,
-              int sides, void* main_stream) {
-    if (plan == nullptr || inp == nullptr || out == nullptr || domain == nullptr)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5: null argument");
-    if (plan->elem_size != (int)sizeof(T))
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5: the plan moves %d-byte items, the fields hold %d-byte items",
-                           plan->elem_size, (int)sizeof(T));
-    hipStream_t ms = static_cast<hipStream_t>(main_stream);
-    if (int rc = gt4mi::direct_failed(plan)) return rc;
-    if (int rc = gt4mi::ensure_concurrent_stream(plan, ms)) return rc;
-    const int64_t di = domain[0], dj = domain[1], dk = domain[2];
-    // W / E: the ring takes a box EW columns wide off the interior kernel (whole cache lines; and the interior then starts
-    // on a 16-byte boundary -- one column in, it ran on 8-byte lanes at 85 us instead of 51 for the 128 x 256 x 512 share)
-    int64_t EW = gt4mi::plan_edge_columns(plan, 16);
-    EW = EW < 1 ? 1 : (EW > 16 ? 16 : EW);
-    if (EW > 1) EW -= EW % (int64_t)(16 / sizeof(T));  // whole 16-byte lanes: the interior kernel keeps its alignment
-    if (EW < 1) EW = 1;
-    if (di < 16 * EW) EW = di >= 64 ? (EW < 8 ? EW : 8) : 1;  // narrow local domains keep most of their columns in the interior
-    // Round 4: where the plan and the layout allow it the unpack and the ring are ONE kernel of wave-sized units that read the
-    // receive buffers themselves (lap5_edge.hip.h); the interior then keeps every column but the first / last one (masked
-    // 16-byte lanes: lap5_launch_variant) instead of giving 8-16 columns to a ring of 64-byte pieces.
-    bool edge_units = false;
-    {
-        gt4mi::View<T> vi, vo;
-        gt4mi::EdgeFaces g;
-        gt4mi::EdgeCopies cp;
-        int ph = 0;
-        if (int rc = gt4mi::lap5_edge_prepare<T>(plan, domain, inp, out, sides, &vi, &vo, &g, &cp, &ph, &edge_units)) return rc;
-    }
-    if (edge_units) EW = 16 / (int64_t)sizeof(T);  // one 16-byte lane: what a column unit computes (lap5_edge.hip.h)
-    const int64_t lo_i = (sides & 1) ? EW : 0, hi_i = (sides & 2) ? EW : 0;
-    const int64_t lo_j = (sides & 4) ? 1 : 0, hi_j = (sides & 8) ? 1 : 0;
-    auto run = [&](int64_t si, int64_t sj, int64_t ei, int64_t ej, hipStream_t st) -> int {
-        if (ei <= 0 || ej <= 0 || dk <= 0) return GT4MI_OK;
-        gt4mi_field a = *inp, b = *out;
-        a.origin[0] += si; a.origin[1] += sj;
-        b.origin[0] += si; b.origin[1] += sj;
-        const int64_t d[3] = {ei, ej, dk};
-        return gt4mi::lap5_run<T, W>(d, &a, &b, variant, st);
-    };
-    const int outer[4] = {0, 0, 0, 0};
-    const int inner[4] = {(int)(lo_i <= di ? lo_i : di), (int)(hi_i && di - hi_i >= lo_i ? hi_i : 0), (int)lo_j,
-                          (int)(hi_j && dj - 1 >= lo_j ? 1 : 0)};
-    auto interior = [&](hipStream_t st) -> int {
-        gt4mi::ScopedLaunchLds throttle(gt4mi::lds_for_workgroups_per_cu(gt4mi::plan_interior_wg_per_cu(plan, 0)));
-        return run(lo_i, lo_j, di - lo_i - hi_i, dj - lo_j - hi_j, st);
-    };
-    // what follows the pack(s) on stream `st`: the rest of the exchange and the points that read ghost cells
-    auto exchange_and_ring = [&](hipStream_t st, bool first_pack_done) -> int {
-        if (edge_units) {
-            if (int rc = gt4mi::halo_exchange_on(plan, inp, st, first_pack_done, /*skip_last_unpack=*/true)) return rc;
-            bool done = false;
-            if (int rc = gt4mi::lap5_edge_run<T, W>(plan, domain, inp, out, variant, sides, st, &done)) return rc;
-            if (done) return GT4MI_OK;
-            plan->direct.broken = plan->transport == GT4MI_TRANSPORT_DIRECT ? "the edge units of a fused step could not be launched" : nullptr;
-            return gt4mi::fail(GT4MI_ERR_HIP, "dist_lap5: the edge units qualified before the exchange and no longer do");
-        }
-        if (int rc = gt4mi::halo_exchange_on(plan, inp, st, first_pack_done)) return rc;
-        return gt4mi::lap5_ring_run<T, W>(domain, inp, out, variant, outer, inner, st);
-    };
-    // default: the fastest on every share of 8 ranks measured (1 x 8, 2 x 4, 4 x 2) -- "swap" with RCCL,
-    // "inline" when the pack kernel is the transfer (direct transport)
-    const int schedule = gt4mi::plan_schedule(plan, plan->transport == GT4MI_TRANSPORT_DIRECT ? GT4MI_SCHEDULE_INLINE : GT4MI_SCHEDULE_SWAP);
-    if (schedule == GT4MI_SCHEDULE_INLINE) {
-        // ONE stream, no event: pack (with the direct transport: the faces are on their way when it ends), the interior kernel,
-        // then whatever is left of the exchange (direct: the unpack, whose data arrived long ago) and the ring
-        if (int rc = gt4mi::lap5_ring_run<T, W>(domain, inp, out, variant, outer, outer, ms)) return rc;  // validates only
-        bool fused = false;
-        const int p0 = gt4mi::first_phase(plan);
-        if (edge_units && plan->transport == GT4MI_TRANSPORT_DIRECT && p0 < 2) {
-            // ONE launch: push | interior | copies and edge units (lap5_step_kernel)
-            bool done = false;
-            ++plan->direct.step;  // (what halo_pack_first does on this transport; the launch reads it)
-            const int rc = gt4mi::lap5_step_run<T, W>(plan, domain, inp, out, variant, sides, ms, &done);
-            if (rc || !done) --plan->direct.step;
-            if (rc) return rc;
-            if (done) {
-                plan->direct.first_pushed = false;  // this exchange is complete
-                return GT4MI_OK;
-            }
-        }
-        if (!edge_units && plan->transport == GT4MI_TRANSPORT_DIRECT && p0 < 2) {
-            // ... and with the direct transport the push rides in the interior's launch (lap5_push.hip.h): 8-9 us off the step
-            gt4mi_field a = *inp, b = *out;
-            a.origin[0] += lo_i; a.origin[1] += lo_j;
-            b.origin[0] += lo_i; b.origin[1] += lo_j;
-            const int64_t sub[3] = {di - lo_i - hi_i, dj - lo_j - hi_j, dk};
-            ++plan->direct.step;  // (what halo_pack_first does on this transport)
-            if (int rc = gt4mi::lap5_interior_with_push<T, W>(plan, sub, &a, &b, variant, inp, p0, ms, &fused)) {
-                --plan->direct.step;
-                return rc;
-            }
-            if (fused) plan->direct.first_pushed = true;
-            else --plan->direct.step;
-        }
-        if (!fused) {
-            if (int rc = gt4mi::halo_pack_first(plan, inp, ms)) return rc;
-            if (int rc = interior(ms)) return rc;
-        }
-        return exchange_and_ring(ms, /*first_pack_done=*/true);
-    }
-    if (schedule == GT4MI_SCHEDULE_SWAP || schedule == GT4MI_SCHEDULE_SWAP_PACKED) {
-        // the CALLER's stream carries the chain pack -> send/recv -> unpack -> ring (no cross-stream wait inside it, and it
-        // starts at once); the interior kernel runs beside it on the side stream; the caller joins the interior at the end
-        if (int rc = gt4mi::lap5_ring_run<T, W>(domain, inp, out, variant, outer, outer, ms)) return rc;  // validates only
-        if (schedule == GT4MI_SCHEDULE_SWAP_PACKED) {
-            // ... and the interior kernel forks off AFTER the pack: the send/recv kernel gets a head start on the interior's
-            // ramp-up and the pack of strided I faces (8-10 us next to the interior) runs alone
-            if (int rc = gt4mi::halo_pack_first(plan, inp, ms)) return rc;
-            GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-            GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-            if (int rc = exchange_and_ring(ms, /*first_pack_done=*/true)) return rc;
-            if (int rc = interior(plan->stream)) return rc;
-            GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-            plan->done_recorded = true;
-        } else {
-            GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-            GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-            if (int rc = interior(plan->stream)) return rc;
-            GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-            plan->done_recorded = true;
-            if (int rc = exchange_and_ring(ms, /*first_pack_done=*/false)) return rc;
-        }
-        return plan->defer_join ? GT4MI_OK : gt4mi_halo_exchange_end(plan, main_stream);
-    }
-    if (schedule == GT4MI_SCHEDULE_CHAIN) {
-        // the main stream carries the interior kernel only; pack -> send/recv -> unpack -> ring in order on the side stream
-        // (see dist_hdiff)
-        if (int rc = gt4mi::lap5_ring_run<T, W>(domain, inp, out, variant, outer, outer, ms)) return rc;  // validates only
-        GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-        GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-        if (int rc = interior(ms)) return rc;
-        if (int rc = exchange_and_ring(plan->stream, /*first_pack_done=*/false)) return rc;
-        GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-        return plan->defer_join ? GT4MI_OK : gt4mi_halo_exchange_end(plan, main_stream);
-    }
-    // 1. pack the first faces ON THE MAIN STREAM, ahead of the interior kernel: alone it takes ~5 us;
-    //    launched next to the interior kernel's thousands of workgroups it took 22 us and delayed the
-    //    whole exchange past the end of the interior kernel (profiles/r1_dist_step_timeline.txt).
-    //    The side stream then only waits for this pack (and whatever preceded it).
-    if (int rc = gt4mi::halo_pack_first(plan, inp, ms)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-    // 2. main stream: interior, independent of the ghost cells in flight
-    if (int rc = interior(ms)) return rc;
-    // 3. side stream: RCCL send/recv + unpack (+ second phase), concurrent with the interior kernel
-    if (int rc = gt4mi::halo_exchange_on(plan, inp, plan->stream, /*first_pack_done=*/true, /*skip_last_unpack=*/edge_units)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-    plan->done_recorded = true;
-    // 4. main stream: join, then the points that read ghost cells -- ONE launch (lap5_edge.hip.h: the unpack rides along;
-    //    else lap5_ring.hip.h)
-    if (int rc = gt4mi_halo_exchange_end(plan, main_stream)) return rc;
-    if (edge_units) {
-        bool done = false;
-        if (int rc = gt4mi::lap5_edge_run<T, W>(plan, domain, inp, out, variant, sides, ms, &done)) return rc;
-        if (done) return GT4MI_OK;
-        return gt4mi::fail(GT4MI_ERR_HIP, "dist_lap5: the edge units qualified before the exchange and no longer do");
-    }
-    return gt4mi::lap5_ring_run<T, W>(domain, inp, out, variant, outer, inner, ms);
-}
 
 }  // namespace
 
@@ -717,7 +436,7 @@ int gt4mi_halo_exchange_fork(gt4mi_halo_plan* plan, void* main_stream) {
     // first use with this stream: make sure the side stream does not share its hardware queue (one-off,
     // synchronising probe) -- otherwise the "overlapped" exchange simply queues behind the interior kernel
     if (int rc = gt4mi::ensure_concurrent_stream(plan, static_cast<hipStream_t>(main_stream))) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->ready, static_cast<hipStream_t>(main_stream)));
+    if (int rc = gt4mi::record_ready(plan, static_cast<hipStream_t>(main_stream))) return rc;
     plan->forked = true;
     return GT4MI_OK;
 }
@@ -726,180 +445,51 @@ int gt4mi_halo_exchange_begin(gt4mi_halo_plan* plan, const gt4mi_field* field, v
     if (plan == nullptr || field == nullptr) return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "halo_exchange_begin: null argument");
     if (!plan->forked)
         if (int rc = gt4mi::ensure_concurrent_stream(plan, static_cast<hipStream_t>(main_stream))) return rc;
-    if (!plan->forked) GT4MI_HIP_CHECK(hipEventRecord(plan->ready, static_cast<hipStream_t>(main_stream)));
+    if (!plan->forked)
+        if (int rc = gt4mi::record_ready(plan, static_cast<hipStream_t>(main_stream))) return rc;
     plan->forked = false;
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
+    if (int rc = gt4mi::side_waits_ready(plan)) return rc;
     if (int rc = gt4mi::halo_exchange_on(plan, field, plan->stream)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
+    if (int rc = gt4mi::mark_done(plan)) return rc;
     plan->primed = true;
     return GT4MI_OK;
 }
 
 int gt4mi_halo_exchange_end(gt4mi_halo_plan* plan, void* main_stream) {
     if (plan == nullptr) return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "halo_exchange_end: null plan");
-    if (int rc = gt4mi::direct_failed(plan)) return rc;  // a wait of an EARLIER exchange ran out of time: say so now
-    if (!plan->done_recorded) return GT4MI_OK;  // nothing was ever put in flight on the side stream
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(static_cast<hipStream_t>(main_stream), plan->done, 0));
-    return GT4MI_OK;
+    return gt4mi::join_side_now(plan, static_cast<hipStream_t>(main_stream));
 }
 
 int gt4mi_dist_lap5_f64(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* inp,
                         const gt4mi_field* out, int variant, int sides, void* main_stream) {
-    return dist_lap5<double, double>(plan, domain, inp, out, variant, sides, main_stream);
+    return gt4mi::dist_lap5<double, double>(plan, domain, inp, out, variant, sides, main_stream);
 }
 
 int gt4mi_dist_lap5_query(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* inp, const gt4mi_field* out, int sides,
                           int* edge_units) {
     if (plan == nullptr || inp == nullptr || out == nullptr || domain == nullptr || edge_units == nullptr)
         return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5_query: null argument");
-    gt4mi::EdgeFaces g;
-    gt4mi::EdgeCopies cp;
-    int phase = 0;
     bool ok = false;
-    int rc;
-    if (plan->elem_size == 8) {
-        gt4mi::View<double> vi, vo;
-        rc = gt4mi::lap5_edge_prepare<double>(plan, domain, inp, out, sides, &vi, &vo, &g, &cp, &phase, &ok);
-    } else {
-        gt4mi::View<float> vi, vo;
-        rc = gt4mi::lap5_edge_prepare<float>(plan, domain, inp, out, sides, &vi, &vo, &g, &cp, &phase, &ok);
-    }
+    const int rc = plan->elem_size == 8 ? gt4mi::lap5_edge_units_qualify<double>(plan, domain, inp, out, sides, &ok)
+                                        : gt4mi::lap5_edge_units_qualify<float>(plan, domain, inp, out, sides, &ok);
     *edge_units = ok ? 1 : 0;
     return rc;
 }
 
 int gt4mi_dist_lap5_f32(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* inp,
                         const gt4mi_field* out, int variant, int flags, int sides, void* main_stream) {
-    if (flags & GT4MI_LAP_LITERAL_F32) return dist_lap5<float, float>(plan, domain, inp, out, variant, sides, main_stream);
-    return dist_lap5<float, double>(plan, domain, inp, out, variant, sides, main_stream);
+    if (flags & GT4MI_LAP_LITERAL_F32) return gt4mi::dist_lap5<float, float>(plan, domain, inp, out, variant, sides, main_stream);
+    return gt4mi::dist_lap5<float, double>(plan, domain, inp, out, variant, sides, main_stream);
 }
 
 int gt4mi_dist_lap5_f64_wide(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* inp,
                              const gt4mi_field* out, int variant, int sides, int halo, int phase, void* main_stream) {
-    if (plan == nullptr || inp == nullptr || out == nullptr || domain == nullptr)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5_wide: null argument");
-    if (halo < 1 || phase < 0 || phase >= halo)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5_wide: need halo >= 1 and 0 <= phase < halo");
-    if (!plan->primed)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT,
-                           "dist_lap5_wide: the ghost cells of the first input were never exchanged "
-                           "(call gt4mi_halo_exchange_begin on it once before the first step)");
-    hipStream_t ms = static_cast<hipStream_t>(main_stream);
-    const int64_t di = domain[0], dj = domain[1], dk = domain[2], H = halo;
-    const bool w = sides & 1, e = sides & 2, s = sides & 4, n = sides & 8;
-    if ((w || e) && di < 2 * H) return gt4mi::fail(GT4MI_ERR_UNSUPPORTED, "dist_lap5_wide: local I extent smaller than 2*halo");
-    if ((s || n) && dj < 2 * H) return gt4mi::fail(GT4MI_ERR_UNSUPPORTED, "dist_lap5_wide: local J extent smaller than 2*halo");
-    // region [i0, i1) x [j0, j1) relative to the local compute-domain origin
-    auto run = [&](int64_t i0, int64_t i1, int64_t j0, int64_t j1) -> int {
-        if (i1 <= i0 || j1 <= j0 || dk <= 0) return GT4MI_OK;
-        gt4mi_field a = *inp, b = *out;
-        a.origin[0] += i0; a.origin[1] += j0;
-        b.origin[0] += i0; b.origin[1] += j0;
-        const int64_t d[3] = {i1 - i0, j1 - j0, dk};
-        return gt4mi::lap5_run<double, double>(d, &a, &b, variant, ms);
-    };
-    if (phase == 0) {
-        if (!(plan->probed && plan->probed_main == ms)) {
-            // the probe synchronises: keep the exchange in flight ordered before it
-            GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-            if (int rc = gt4mi::ensure_concurrent_stream(plan, ms)) return rc;
-            GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-        }
-        // join the exchange that delivered `inp`'s ghost cells (started `halo` steps ago)
-        GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-    }
-    const int64_t ext = H - 1 - phase;  // how far this step still reaches into the ghost region
-    if (ext > 0) {
-        // redundant-compute step: one launch over the domain grown by `ext` towards every neighbour;
-        // its ghost results are valid inputs for the next step, no communication
-        return run(w ? -ext : 0, di + (e ? ext : 0), s ? -ext : 0, dj + (n ? ext : 0));
-    }
-    // last step of the cycle: `out`'s faces (H deep) are what the neighbours need next
-    const int64_t lo_i = w ? H : 0, hi_i = e ? H : 0, lo_j = s ? H : 0, hi_j = n ? H : 0;
-    {  // the H-deep ring of `out` in ONE launch (lap5_ring.hip.h)
-        const int outer[4] = {0, 0, 0, 0};
-        const int inner[4] = {(int)lo_i, (int)hi_i, (int)lo_j, (int)hi_j};
-        if (int rc = gt4mi::lap5_ring_run<double, double>(domain, inp, out, variant, outer, inner, ms)) return rc;
-    }
-    // pack on the main stream (before the interior kernel floods the CUs), then fork
-    if (int rc = gt4mi::halo_pack_first(plan, out, ms)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-    // interior on the main stream, RCCL send/recv + unpack of `out`'s ghost cells next to it; nobody
-    // waits for them until phase 0 of the next cycle (where `out` is the input)
-    if (int rc = run(lo_i, di - hi_i, lo_j, dj - hi_j)) return rc;
-    if (int rc = gt4mi::halo_exchange_on(plan, out, plan->stream, /*first_pack_done=*/true)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-    return GT4MI_OK;
+    return gt4mi::dist_lap5_wide(plan, domain, inp, out, variant, sides, halo, phase, main_stream);
 }
 
 int gt4mi_dist_lap5_f64_skewed(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* field_a,
                                const gt4mi_field* field_b, int variant, int sides, int halo, void* main_stream) {
-    if (plan == nullptr || field_a == nullptr || field_b == nullptr || domain == nullptr)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5_skewed: null argument");
-    if (halo < 1) return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT, "dist_lap5_skewed: need halo >= 1");
-    if (!plan->primed)
-        return gt4mi::fail(GT4MI_ERR_INVALID_ARGUMENT,
-                           "dist_lap5_skewed: the ghost cells of the first input were never exchanged "
-                           "(call gt4mi_halo_exchange_begin on it once before the first cycle)");
-    hipStream_t ms = static_cast<hipStream_t>(main_stream);
-    const int64_t di = domain[0], dj = domain[1], dk = domain[2];
-    const int H = halo;
-    const bool w = sides & 1, e = sides & 2, s = sides & 4, n = sides & 8;
-    // the band of step 1 reaches 2H - 1 points into the domain from every side that has a neighbour
-    if ((w || e) && di < (int64_t)(2 * H - 1) * ((w ? 1 : 0) + (e ? 1 : 0)))
-        return gt4mi::fail(GT4MI_ERR_UNSUPPORTED, "dist_lap5_skewed: local I extent too small for a ghost depth of %d", H);
-    if ((s || n) && dj < (int64_t)(2 * H - 1) * ((s ? 1 : 0) + (n ? 1 : 0)))
-        return gt4mi::fail(GT4MI_ERR_UNSUPPORTED, "dist_lap5_skewed: local J extent too small for a ghost depth of %d", H);
-    if (!(plan->probed && plan->probed_main == ms)) {
-        // the probe synchronises: keep the exchange in flight ordered before it
-        GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-        if (int rc = gt4mi::ensure_concurrent_stream(plan, ms)) return rc;
-        GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-    }
-    // join the exchange that delivered field_a's ghost cells (started by the previous cycle)
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(ms, plan->done, 0));
-    auto src_of = [&](int step) { return (step % 2 == 1) ? field_a : field_b; };  // step 1 reads a, writes b
-    auto dst_of = [&](int step) { return (step % 2 == 1) ? field_b : field_a; };
-    // 1. the bands, outermost first: step st on [-(H - st), 2H - st) points from every side with a neighbour
-    for (int st = 1; st <= H; ++st) {
-        const int g = H - st, d = 2 * H - st;
-        const int outer[4] = {w ? g : 0, e ? g : 0, s ? g : 0, n ? g : 0};
-        const int inner[4] = {w ? d : 0, e ? d : 0, s ? d : 0, n ? d : 0};
-        if (int rc = gt4mi::lap5_ring_run<double, double>(domain, src_of(st), dst_of(st), variant, outer, inner, ms)) return rc;
-    }
-    // 2. the H-deep faces of the result are final: pack them on the main stream (before the interior kernels flood the
-    //    device), then the side stream sends / receives / unpacks next to ALL H interior kernels
-    const gt4mi_field* result = dst_of(H);
-    // (chain schedule: the pack runs on the side stream as well, next to the first interior kernel)
-    const bool pack_on_side = gt4mi::plan_schedule(plan, GT4MI_SCHEDULE_JOIN) == GT4MI_SCHEDULE_CHAIN;
-    if (!pack_on_side)
-        if (int rc = gt4mi::halo_pack_first(plan, result, ms)) return rc;
-    GT4MI_HIP_CHECK(hipEventRecord(plan->ready, ms));
-    GT4MI_HIP_CHECK(hipStreamWaitEvent(plan->stream, plan->ready, 0));
-    // 3. the interiors: step st on the domain shrunk by 2H - st
-    for (int st = 1; st <= H; ++st) {
-        const int64_t d = 2 * H - st;
-        const int64_t i0 = w ? d : 0, i1 = di - (e ? d : 0), j0 = s ? d : 0, j1 = dj - (n ? d : 0);
-        if (i1 > i0 && j1 > j0 && dk > 0) {
-            gt4mi_field a = *src_of(st), b = *dst_of(st);
-            a.origin[0] += i0; a.origin[1] += j0;
-            b.origin[0] += i0; b.origin[1] += j0;
-            const int64_t sub[3] = {i1 - i0, j1 - j0, dk};
-            gt4mi::ScopedLaunchLds throttle(gt4mi::lds_for_workgroups_per_cu(gt4mi::plan_interior_wg_per_cu(plan, 0)));
-            if (int rc = gt4mi::lap5_run<double, double>(sub, &a, &b, variant, ms)) return rc;
-        }
-        if (st == 1) {  // enqueued after the first interior launch so that the device has work while the host talks to RCCL
-            if (int rc = gt4mi::halo_exchange_on(plan, result, plan->stream, /*first_pack_done=*/!pack_on_side)) return rc;
-            GT4MI_HIP_CHECK(hipEventRecord(plan->done, plan->stream));
-        plan->done_recorded = true;
-        }
-    }
-    return GT4MI_OK;
+    return gt4mi::dist_lap5_skewed(plan, domain, field_a, field_b, variant, sides, halo, main_stream);
 }
 
 int gt4mi_dist_lap5_f64_pipelined(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* inp,
@@ -907,17 +497,16 @@ int gt4mi_dist_lap5_f64_pipelined(gt4mi_halo_plan* plan, const int64_t domain[3]
     return gt4mi_dist_lap5_f64_wide(plan, domain, inp, out, variant, sides, 1, 0, main_stream);
 }
 
-
 int gt4mi_dist_hdiff_f64(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* in_field,
                          const gt4mi_field* out_field, const gt4mi_field* coeff, double coeff_scalar, int flags, int sides,
                          void* main_stream) {
-    return dist_hdiff<double>(plan, domain, in_field, out_field, coeff, coeff_scalar, flags, sides, main_stream);
+    return gt4mi::dist_hdiff<double>(plan, domain, in_field, out_field, coeff, coeff_scalar, flags, sides, main_stream);
 }
 
 int gt4mi_dist_hdiff_f32(gt4mi_halo_plan* plan, const int64_t domain[3], const gt4mi_field* in_field,
                          const gt4mi_field* out_field, const gt4mi_field* coeff, double coeff_scalar, int flags, int sides,
                          void* main_stream) {
-    return dist_hdiff<float>(plan, domain, in_field, out_field, coeff, coeff_scalar, flags, sides, main_stream);
+    return gt4mi::dist_hdiff<float>(plan, domain, in_field, out_field, coeff, coeff_scalar, flags, sides, main_stream);
 }
 
 int gt4mi_stream_copy(const void* src, void* dst, size_t nbytes, void* stream) {
