@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_halo_unpack",
     "gt4mi_halo_fill",
     "gt4mi_field_stats",
+    "gt4mi_field_copy",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -99,6 +100,9 @@ HALO_I_LO, HALO_I_HI, HALO_J_LO, HALO_J_HI, HALO_ALL_SIDES, HALO_DRY_RUN = 1, 2,
 # gt4mi_field_stats: slots of a result row, flags
 STATS_COUNT, STATS_NONFINITE, STATS_SUM, STATS_SUM_ABS, STATS_SUM_SQ, STATS_MIN, STATS_MAX, STATS_DOT, STATS_SLOTS = range(9)
 STATS_DRY_RUN = 1
+# gt4mi_field_copy: paths, flags
+COPY_PATH_ROWS, COPY_PATH_TILES, COPY_PATH_ITEMS = 0, 1, 2
+COPY_CONVERT, COPY_DRY_RUN = 1, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -203,6 +207,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_field_stats.restype = I
     lib.gt4mi_field_stats.argtypes = [FP, FP, I, DOM, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64),
                                       ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_field_copy.restype = I
+    lib.gt4mi_field_copy.argtypes = [FP, FP, I, DOM, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

@@ -12,6 +12,7 @@
 #include "halo.hip.h"
 #include "halo_fill.hip.h"
 #include "field_stats.hip.h"
+#include "field_copy.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -200,6 +201,12 @@ int gt4mi_field_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
                       int64_t* workspace_needed, int* launches) {
     return gt4mi::field_stats(fields, others, nfields, domain, elem_size, workspace, workspace_bytes, result, flags,
                               static_cast<hipStream_t>(stream), workspace_needed, launches);
+}
+
+int gt4mi_field_copy(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const int64_t extent[3], int dst_elem_size,
+                     int src_elem_size, int flags, void* stream, int* paths, int* launches) {
+    return gt4mi::field_copy(dst, src, nfields, extent, dst_elem_size, src_elem_size, flags, static_cast<hipStream_t>(stream), paths,
+                             launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

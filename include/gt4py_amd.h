@@ -219,6 +219,28 @@ int gt4mi_field_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
                       void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
                       int64_t* workspace_needed, int* launches);
 
+/* ---- layout-converting field copy (NEW entry, additive: the ABI version stays 8.  Replaces what the reference does with numpy /
+ * cupy slicing on its numpy / cupy storages and with `cp.asarray` (storage/cartesian/utils.py:187-189): moving a field between two
+ * layouts, a storage and a dense buffer in numpy's C order among them) ------------------------------------------------------------
+ * Copies the box [origin, origin + extent) of src[n] to the box [origin, origin + extent) of dst[n] (each side of each pair with its
+ * own pointer, byte strides and origin, any layout) for `nfields` pairs, in ONE kernel launch per 8 pairs, on `stream`, without
+ * synchronisation or allocation.  Items of equal size (1, 2, 4 or 8 bytes) are moved as bit patterns: bool and integer fields work,
+ * NaN payloads and the sign of zero survive.  With GT4MI_COPY_CONVERT the sizes may be 8 -> 4 (float64 -> float32, ONE rounding to
+ * nearest even) or 4 -> 8 (float32 -> float64, exact); a NaN stays a NaN of the same sign, its payload is unspecified.
+ * The library picks a path per pair from strides and alignment (csrc/field_copy.hip.h) and reports it in paths[n] (may be NULL):
+ *   GT4MI_COPY_PATH_ROWS    both sides have unit item stride along the same axis (of extent > 1): rows, 16-byte lanes where both allow
+ *   GT4MI_COPY_PATH_TILES   unit item stride along different axes: a transpose, tiles through on-chip memory, coalesced on both sides
+ *   GT4MI_COPY_PATH_ITEMS   anything else: a side without unit stride on an axis of extent > 1, a broadcast src
+ * A src stride of 0 is allowed and broadcasts; a dst stride of 0 on an axis of extent > 1 is GT4MI_ERR_INVALID_ARGUMENT.  The bytes
+ * of a dst box (first to last item) must meet neither those of any src box nor of another dst box of the call
+ * (GT4MI_ERR_UNSUPPORTED).  No byte outside the dst boxes changes.  An extent with a zero entry is GT4MI_OK, nothing enqueued.
+ * Every check runs before the first launch; a refused call enqueues nothing.  With GT4MI_COPY_DRY_RUN the checks run, paths and
+ * *launches are set and no device is touched.  *launches (may be NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_COPY_PATH_ROWS = 0, GT4MI_COPY_PATH_TILES = 1, GT4MI_COPY_PATH_ITEMS = 2 };
+enum { GT4MI_COPY_CONVERT = 1, GT4MI_COPY_DRY_RUN = 256 };
+int gt4mi_field_copy(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const int64_t extent[3],
+                     int dst_elem_size, int src_elem_size, int flags, void* stream, int* paths, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
