@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_halo_unpack",
     "gt4mi_halo_fill",
     "gt4mi_field_stats",
+    "gt4mi_level_stats",
     "gt4mi_field_copy",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
@@ -100,6 +101,8 @@ HALO_I_LO, HALO_I_HI, HALO_J_LO, HALO_J_HI, HALO_ALL_SIDES, HALO_DRY_RUN = 1, 2,
 # gt4mi_field_stats: slots of a result row, flags
 STATS_COUNT, STATS_NONFINITE, STATS_SUM, STATS_SUM_ABS, STATS_SUM_SQ, STATS_MIN, STATS_MAX, STATS_DOT, STATS_SLOTS = range(9)
 STATS_DRY_RUN = 1
+# gt4mi_level_stats: the row after the eight slots, rows of a result block, tiles per level at most (part of the bit contract)
+LEVEL_STATS_MEAN, LEVEL_STATS_ROWS, LEVEL_STATS_MAX_TILES = 8, 9, 32
 # gt4mi_field_copy: paths, flags
 COPY_PATH_ROWS, COPY_PATH_TILES, COPY_PATH_ITEMS = 0, 1, 2
 COPY_CONVERT, COPY_DRY_RUN = 1, 256
@@ -204,9 +207,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_halo_unpack.argtypes = [FP, DOM, DOM, P, I, P]
     lib.gt4mi_halo_fill.restype = I
     lib.gt4mi_halo_fill.argtypes = [FP, I, DOM, DOM, I, I, I, P, I, P, ctypes.POINTER(ctypes.c_int)]
-    lib.gt4mi_field_stats.restype = I
-    lib.gt4mi_field_stats.argtypes = [FP, FP, I, DOM, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64),
-                                      ctypes.POINTER(ctypes.c_int)]
+    for name in ("gt4mi_field_stats", "gt4mi_level_stats"):
+        f = getattr(lib, name)
+        f.restype = I
+        f.argtypes = [FP, FP, I, DOM, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_field_copy.restype = I
     lib.gt4mi_field_copy.argtypes = [FP, FP, I, DOM, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I

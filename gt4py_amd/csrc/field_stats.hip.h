@@ -152,9 +152,9 @@ __device__ __forceinline__ void stats_load(const T* row, int64_t si, bool vec, i
 
 // everything one wave adds: its rows, chunk by chunk, STATS_BATCH chunks in flight
 template <typename T, bool PAIR>
-__device__ __forceinline__ void stats_wave(const StatsArgs& g, const StatsEntry& f, int64_t row0, int nrows, int lane, StatsAcc& s) {
-    const int chunks = (g.ni + STATS_CHUNK - 1) / STATS_CHUNK;
-    int k = (int)(row0 / g.nj), j = (int)(row0 - (int64_t)k * g.nj), c = 0;
+__device__ __forceinline__ void stats_wave(int ni, int nj, const StatsEntry& f, int64_t row0, int nrows, int lane, StatsAcc& s) {
+    const int chunks = (ni + STATS_CHUNK - 1) / STATS_CHUNK;
+    int k = (int)(row0 / nj), j = (int)(row0 - (int64_t)k * nj), c = 0;
     const T* const A = reinterpret_cast<const T*>(f.a);
     const T* const B = reinterpret_cast<const T*>(f.b);
     for (int64_t left = (int64_t)nrows * chunks; left > 0; left -= STATS_BATCH) {
@@ -165,14 +165,14 @@ __device__ __forceinline__ void stats_wave(const StatsArgs& g, const StatsEntry&
             nvalid[u] = 0;
             if (u < left) {
                 const int i0 = c * STATS_CHUNK + lane * STATS_GROUP;
-                const int n = g.ni - i0;
+                const int n = ni - i0;
                 nvalid[u] = n < 0 ? 0 : (n > STATS_GROUP ? STATS_GROUP : n);
                 stats_load<T>(A + (int64_t)j * f.aj + (int64_t)k * f.ak, f.ai, (f.vec & 1) != 0, i0, nvalid[u], va[u]);
                 if constexpr (PAIR)
                     stats_load<T>(B + (int64_t)j * f.bj + (int64_t)k * f.bk, f.bi, (f.vec & 2) != 0, i0, nvalid[u], vb[u]);
                 if (++c == chunks) {
                     c = 0;
-                    if (++j == g.nj) j = 0, ++k;
+                    if (++j == nj) j = 0, ++k;
                 }
             }
         }
@@ -190,6 +190,36 @@ __device__ __forceinline__ void stats_wave(const StatsArgs& g, const StatsEntry&
     }
 }
 
+__device__ __forceinline__ void stats_init(StatsAcc& s) {
+    s.sum = s.sum_abs = s.sum_sq = s.dot = 0.0;
+    s.mn = __builtin_inf();
+    s.mx = -__builtin_inf();
+    s.count = s.nonfinite = 0u;
+}
+
+// the end of a lane's chain (a NaN item makes min and max NaN), then the butterfly over the 64 lanes
+__device__ __forceinline__ void stats_butterfly(StatsAcc& s) {
+    if (s.sum_abs != s.sum_abs) s.mn = s.mx = __builtin_nan("");
+#pragma unroll
+    for (int step = 1; step < 64; step <<= 1) {
+        s.sum = s.sum + __shfl_xor(s.sum, step, 64);
+        s.sum_abs = s.sum_abs + __shfl_xor(s.sum_abs, step, 64);
+        s.sum_sq = s.sum_sq + __shfl_xor(s.sum_sq, step, 64);
+        s.dot = s.dot + __shfl_xor(s.dot, step, 64);
+        s.mn = stats_min(s.mn, __shfl_xor(s.mn, step, 64));
+        s.mx = stats_max(s.mx, __shfl_xor(s.mx, step, 64));
+        s.count += (unsigned)__shfl_xor((int)s.count, step, 64);
+        s.nonfinite += (unsigned)__shfl_xor((int)s.nonfinite, step, 64);
+    }
+}
+
+// a wave's eight values into its row of the workgroup's LDS block (every lane holds them after the butterfly)
+__device__ __forceinline__ void stats_wave_values(const StatsAcc& s, double* w) {
+    w[STATS_COUNT] = (double)s.count, w[STATS_NONFINITE] = (double)s.nonfinite;
+    w[STATS_SUM] = s.sum, w[STATS_SUM_ABS] = s.sum_abs, w[STATS_SUM_SQ] = s.sum_sq;
+    w[STATS_MIN] = s.mn, w[STATS_MAX] = s.mx, w[STATS_DOT] = s.dot;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(64 * STATS_WAVES)
 field_stats_kernel(const StatsArgs g) {
@@ -204,31 +234,11 @@ field_stats_kernel(const StatsArgs g) {
     const int64_t rest = g.rows - row0;
     const int nrows = rest <= 0 ? 0 : (rest < g.rows_per_wave ? (int)rest : g.rows_per_wave);
     StatsAcc s;
-    s.sum = s.sum_abs = s.sum_sq = s.dot = 0.0;
-    s.mn = __builtin_inf();
-    s.mx = -__builtin_inf();
-    s.count = s.nonfinite = 0u;
-    if (f.b != nullptr) stats_wave<T, true>(g, f, row0, nrows, lane, s);
-    else stats_wave<T, false>(g, f, row0, nrows, lane, s);
-    if (s.sum_abs != s.sum_abs) s.mn = s.mx = __builtin_nan("");
-    // the butterfly over the lanes
-#pragma unroll
-    for (int step = 1; step < 64; step <<= 1) {
-        s.sum = s.sum + __shfl_xor(s.sum, step, 64);
-        s.sum_abs = s.sum_abs + __shfl_xor(s.sum_abs, step, 64);
-        s.sum_sq = s.sum_sq + __shfl_xor(s.sum_sq, step, 64);
-        s.dot = s.dot + __shfl_xor(s.dot, step, 64);
-        s.mn = stats_min(s.mn, __shfl_xor(s.mn, step, 64));
-        s.mx = stats_max(s.mx, __shfl_xor(s.mx, step, 64));
-        s.count += (unsigned)__shfl_xor((int)s.count, step, 64);
-        s.nonfinite += (unsigned)__shfl_xor((int)s.nonfinite, step, 64);
-    }
-    if (lane == 0) {
-        double* const w = wave_values[wave];
-        w[STATS_COUNT] = (double)s.count, w[STATS_NONFINITE] = (double)s.nonfinite;
-        w[STATS_SUM] = s.sum, w[STATS_SUM_ABS] = s.sum_abs, w[STATS_SUM_SQ] = s.sum_sq;
-        w[STATS_MIN] = s.mn, w[STATS_MAX] = s.mx, w[STATS_DOT] = s.dot;
-    }
+    stats_init(s);
+    if (f.b != nullptr) stats_wave<T, true>(g.ni, g.nj, f, row0, nrows, lane, s);
+    else stats_wave<T, false>(g.ni, g.nj, f, row0, nrows, lane, s);
+    stats_butterfly(s);
+    if (lane == 0) stats_wave_values(s, wave_values[wave]);
     __syncthreads();
     if (threadIdx.x < (unsigned)STATS_SLOTS) {  // the four waves, left to right; 8 lanes store the tile's 64 bytes
         const int slot = (int)threadIdx.x;

@@ -12,6 +12,7 @@
 #include "halo.hip.h"
 #include "halo_fill.hip.h"
 #include "field_stats.hip.h"
+#include "level_stats.hip.h"
 #include "field_copy.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
@@ -200,6 +201,13 @@ int gt4mi_field_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
                       void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
                       int64_t* workspace_needed, int* launches) {
     return gt4mi::field_stats(fields, others, nfields, domain, elem_size, workspace, workspace_bytes, result, flags,
+                              static_cast<hipStream_t>(stream), workspace_needed, launches);
+}
+
+int gt4mi_level_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int elem_size,
+                      void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream, int64_t* workspace_needed,
+                      int* launches) {
+    return gt4mi::level_stats(fields, others, nfields, domain, elem_size, workspace, workspace_bytes, result, flags,
                               static_cast<hipStream_t>(stream), workspace_needed, launches);
 }
 

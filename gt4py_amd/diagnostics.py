@@ -16,6 +16,18 @@ launch, a second small launch combines the tiles' partial results; nothing is al
 All arithmetic is float64 (float32 fields are widened first).  THE ORDER OF THE ADDITIONS IS PART OF THE CONTRACT: it depends on
 the domain ``(ni, nj, nk)`` alone -- not on addresses, strides, padding, how many fields share the call, or the device -- so the
 same domain data gives the same bits, always.  Results of a decomposed run are joined with :func:`merge`.
+
+PER LEVEL (``gt4mi_level_stats``, csrc/level_stats.hip.h): the same eight values and the mean for every level ``k`` of the
+domain, one pass again, left on the device as contiguous ``Field[K, float64]`` profiles that a stencil can read in the same
+stream -- what GTScript, which has no reduction over I and J, cannot express:
+
+    watch = diagnostics.LevelStats([u], halo=2)
+    watch()                                                 # enqueued, no synchronisation
+    anomaly(u, watch.profile("mean"), out)                  # m: Field[K, np.float64]; out = u - m
+    p, = watch.get()                                        # a Profile: p.max_abs[k], p.first_nonfinite, p[k] (a Stats)
+
+The order of the additions of a level depends on ``(ni, nj)`` alone: the same plane gives the same bits whatever ``nk`` is and
+whichever level it is.  Profiles of a decomposed run are joined with :func:`merge_profiles`.
 """
 
 from __future__ import annotations
@@ -23,7 +35,7 @@ from __future__ import annotations
 import ctypes
 import math
 import weakref
-from typing import Any, List, NamedTuple, Optional, Sequence
+from typing import Any, List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
@@ -111,16 +123,17 @@ def merge(stats: Sequence[Stats]) -> Stats:
     return out
 
 
-def _native(fields, others, n: int, domain, itemsize: int, workspace, workspace_bytes: int, result, flags: int, stream):
+def _native(fields, others, n: int, domain, itemsize: int, workspace, workspace_bytes: int, result, flags: int, stream,
+            entry: str = "gt4mi_field_stats"):
     """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
     library's message.  Returns (workspace bytes needed, kernels enqueued)."""
     needed, launches = ctypes.c_int64(0), ctypes.c_int(0)
-    rc = _lib.load().gt4mi_field_stats(fields, others, n, domain, itemsize, workspace, workspace_bytes, result, flags, stream,
-                                       ctypes.byref(needed), ctypes.byref(launches))
+    rc = getattr(_lib.load(), entry)(fields, others, n, domain, itemsize, workspace, workspace_bytes, result, flags, stream,
+                                     ctypes.byref(needed), ctypes.byref(launches))
     if rc != _lib.OK:
         message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
         if rc == _lib.ERR_HIP:
-            raise _lib.NativeError("gt4mi_field_stats", rc, message)
+            raise _lib.NativeError(entry, rc, message)
         raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
     return needed.value, launches.value
 
@@ -256,5 +269,249 @@ def field_stats(*fields, other=None, origin: Optional[Sequence[int]] = None, dom
     else:
         others = None if other is None else [other] * len(fields)
     frozen = FieldStats(fields, others=others, origin=origin, domain=domain, halo=halo)
+    frozen()
+    return frozen.get()
+
+
+# ---- per level: K profiles ---------------------------------------------------------------------------------------------------
+#: the rows of a LevelStats result block, in order: the fields of Stats, then the mean
+PROFILE_ROWS = Stats._fields + ("mean",)
+
+
+class Profile:
+    """The per-level values of one entry: numpy arrays of length ``nk`` for ``count``, ``nonfinite`` (int64), ``sum``,
+    ``sum_abs``, ``sum_sq``, ``min``, ``max``, ``dot`` and ``mean`` (float64), with the NaN and signed-zero rules of
+    :class:`Stats` level by level.  ``profile[k]`` is the :class:`Stats` of level ``k``; index 0 is the first level of the
+    domain (``origin[2]``)."""
+
+    __slots__ = PROFILE_ROWS
+
+    def __init__(self, count, nonfinite, sum, sum_abs, sum_sq, min, max, dot, mean=None):  # noqa: A002 - the names of Stats
+        self.count, self.nonfinite = (np.array(v, dtype=np.int64, ndmin=1) for v in (count, nonfinite))
+        self.sum, self.sum_abs, self.sum_sq, self.min, self.max, self.dot = (
+            np.array(v, dtype=np.float64, ndmin=1) for v in (sum, sum_abs, sum_sq, min, max, dot))
+        if mean is None:
+            with np.errstate(all="ignore"):
+                mean = self.sum / self.count  # one IEEE division per level, as the kernel's
+        self.mean = np.array(mean, dtype=np.float64, ndmin=1)
+        if any(getattr(self, name).shape != self.count.shape or self.count.ndim != 1 for name in PROFILE_ROWS):
+            raise ValueError("the rows of a Profile are one-dimensional and of one length")
+
+    @classmethod
+    def from_rows(cls, rows) -> "Profile":
+        """From one ``(9, nk)`` block of a :class:`LevelStats` result."""
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[0] != _lib.LEVEL_STATS_ROWS:
+            raise ValueError(f"a result block has shape (9, nk), not {rows.shape}")
+        return cls(*rows[:_lib.STATS_SLOTS], mean=rows[_lib.LEVEL_STATS_MEAN])
+
+    @property
+    def nk(self) -> int:
+        return len(self.count)
+
+    def __len__(self) -> int:
+        return self.nk
+
+    def __getitem__(self, k: int) -> Stats:
+        k = int(k)
+        return Stats(int(self.count[k]), int(self.nonfinite[k]), float(self.sum[k]), float(self.sum_abs[k]), float(self.sum_sq[k]),
+                     float(self.min[k]), float(self.max[k]), float(self.dot[k]))
+
+    @property
+    def norm2(self) -> np.ndarray:
+        with np.errstate(all="ignore"):
+            return np.sqrt(self.sum_sq)
+
+    @property
+    def max_abs(self) -> np.ndarray:
+        """max |x| per level (the vertical CFL limit differs from level to level); NaN where the level holds a NaN."""
+        return np.maximum(np.abs(self.min), np.abs(self.max))  # (numpy's maximum hands a NaN on)
+
+    @property
+    def all_finite(self) -> np.ndarray:
+        return self.nonfinite == 0
+
+    @property
+    def first_nonfinite(self) -> Optional[int]:
+        """The lowest level index with a NaN or +-Inf item, or ``None``."""
+        bad = np.flatnonzero(self.nonfinite)
+        return int(bad[0]) if bad.size else None
+
+    def total(self) -> Stats:
+        """The levels joined left to right as :func:`merge` does: exact counts and extremes, sums added in level order.  NOT
+        the bits of :func:`field_stats` over the whole domain, whose additions are ordered by the whole domain."""
+        return merge([self[k] for k in range(self.nk)])
+
+    def __eq__(self, other) -> bool:
+        """Bit for bit, NaN equal to NaN."""
+        if not isinstance(other, Profile):
+            return NotImplemented
+        return all(np.array_equal(getattr(self, n), getattr(other, n), equal_nan=True)
+                   and np.array_equal(np.signbit(getattr(self, n)), np.signbit(getattr(other, n))) for n in PROFILE_ROWS)
+
+    __hash__ = None  # type: ignore[assignment]
+
+    def __repr__(self) -> str:
+        return f"Profile(nk={self.nk}, first_nonfinite={self.first_nonfinite})"
+
+
+def merge_profiles(parts: Sequence[Profile]) -> Profile:
+    """Join the per-rank profiles of a decomposed run on the host, level by level, IN THE ORDER GIVEN.  K is never split, so all
+    parts have the same ``nk`` (``ValueError`` otherwise).  As with :func:`merge`: counts add exactly, ``min`` / ``max`` are
+    joined exactly (NaN if any is NaN, -0 below +0), the sums are added left to right in float64 -- reproducible for a fixed
+    process grid and rank order, NOT bit for bit what one undecomposed call gives.  ``mean`` is recomputed from the joined
+    ``sum`` and ``count``.  No collective is made here; gather first, in rank order."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_profiles needs at least one Profile")
+    for p in parts:
+        if not isinstance(p, Profile):
+            raise TypeError(f"merge_profiles joins Profile records, not {type(p).__name__}")
+        if p.nk != parts[0].nk:
+            raise ValueError(f"the parts of a decomposed run share their levels: nk = {parts[0].nk} and {p.nk} differ")
+    levels = [merge([p[k] for p in parts]) for k in range(parts[0].nk)]
+    return Profile(*(np.array([getattr(s, name) for s in levels]) for name in Stats._fields))
+
+
+class LevelStats:
+    """The frozen form of :func:`level_stats`, with the arguments and defaults of :class:`FieldStats`; ``origin[2]`` /
+    ``domain[2]`` select the levels, profile index 0 is level ``origin[2]``, and IJ fields give ``nk = 1``.  Arguments are
+    checked (through the library's dry run), the descriptors, the workspace and the result buffer built ONCE; ``__call__()``
+    makes only the ctypes call, on the stream that is current THEN, and does not synchronise; :meth:`get` synchronises that
+    stream and returns one :class:`Profile` per entry.
+
+    ``result`` is a float64 :class:`DeviceArray` of shape ``(n, 9, nk)`` (rows in the order of :data:`PROFILE_ROWS`);
+    :meth:`profile` hands out one contiguous row of it, which a stencil takes as ``Field[K, np.float64]`` in the same stream
+    with no synchronisation in between.  Every call overwrites it.
+
+    The object holds raw pointers and weak references to the CALLER's objects, as :class:`FieldStats` does: it refuses to run
+    once one of them has died."""
+
+    def __init__(self, fields: Sequence[Any], *, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
+                 domain: Optional[Sequence[int]] = None, halo=0):
+        fields = list(fields)
+        arrays = [as_device_array(f) for f in fields]
+        if not arrays:
+            raise ValueError("level_stats needs at least one field")
+        if others is None:
+            others = [None] * len(fields)
+        others = list(others)
+        if len(others) != len(fields):
+            raise ValueError(f"others must have one entry (or None) per field: {len(others)} for {len(fields)} fields")
+        other_arrays = [None if o is None else as_device_array(o) for o in others]
+        first = arrays[0]
+        every = arrays + [o for o in other_arrays if o is not None]
+        for a in every:
+            if a.dtype not in (np.dtype("float32"), np.dtype("float64")):
+                raise TypeError(f"level_stats takes float32 or float64 fields, not {a.dtype}")
+            if a.dtype != first.dtype:
+                raise TypeError(f"the fields of one call share a dtype: {first.dtype} and {a.dtype} differ")
+            if a.ndim not in (2, 3):
+                raise ValueError(f"level_stats takes IJ or IJK fields, not a field of {a.ndim} dimension(s)")
+        h = _halo4(halo)
+        if origin is None:
+            origin = (h[0], h[2], 0)
+        origin = tuple(int(o) for o in origin)
+        origin = origin + (0,) * (3 - len(origin))
+        if len(origin) != 3:
+            raise ValueError(f"origin must have at most three entries, not {origin}")
+        shape3 = tuple(first.shape) + (1,) * (3 - first.ndim)
+        if domain is None:
+            domain = (shape3[0] - origin[0] - h[1], shape3[1] - origin[1] - h[3], shape3[2] - origin[2])
+            if min(domain) < 1:
+                raise ValueError(f"halo {h} and origin {origin} leave no domain in a field of shape {first.shape}")
+        domain = tuple(int(d) for d in domain)
+        domain = domain + (1,) * (3 - len(domain))
+        if len(domain) != 3:
+            raise ValueError(f"domain must have at most three entries, not {domain}")
+        self.origin, self.domain = origin, domain
+        self._itemsize = first.itemsize
+        self._n = len(arrays)
+
+        def describe(a, weight):
+            shape = tuple(a.shape) + (1,) * (3 - a.ndim)
+            strides = tuple(a.strides) + (0,) * (3 - a.ndim)
+            # a broadcast axis of a weight (stride 0) has no origin of its own
+            org = tuple(0 if weight and s == 0 else o for o, s in zip(origin, strides))
+            return _lib.Field.make(a.ptr, shape, strides, org)
+
+        self._fields = (_lib.Field * self._n)()
+        self._others = (_lib.Field * self._n)()  # (data == NULL: no second field)
+        for n, (a, o) in enumerate(zip(arrays, other_arrays)):
+            self._fields[n] = describe(a, False)
+            if o is not None:
+                self._others[n] = describe(o, True)
+        self._domain3 = _lib.domain3(domain)
+        # every check of the library, nothing enqueued; also: the workspace the call needs and how many kernels it makes
+        needed, self.launches = _native(self._fields, self._others, self._n, self._domain3, self._itemsize, None, 0, None,
+                                        _lib.STATS_DRY_RUN, None, "gt4mi_level_stats")
+        # (last: none of the checks above needs a device)
+        for a in every:
+            if not a.tensor.is_cuda:
+                raise TypeError("level_stats works on device fields; a host array was passed")
+        import torch
+
+        self._workspace = torch.empty(needed // 8, dtype=torch.float64, device=first.tensor.device)
+        self.result = DeviceArray(torch.zeros((self._n, _lib.LEVEL_STATS_ROWS, domain[2]), dtype=torch.float64,
+                                              device=first.tensor.device))
+        self._workspace_bytes = needed
+        # the buffers against the fields (overlap, alignment): the dry run once more, now with them
+        _native(self._fields, self._others, self._n, self._domain3, self._itemsize, self._workspace.data_ptr(), needed,
+                self.result.ptr, _lib.STATS_DRY_RUN, None, "gt4mi_level_stats")
+        # what must stay alive is what the CALLER holds (see HaloFill)
+        self._refs, self._held = [], []
+        for f in fields + [o for o in others if o is not None]:
+            try:
+                self._refs.append(weakref.ref(f))
+            except TypeError:
+                self._held.append(f)
+        self._current_stream = torch.cuda.current_stream
+        self._stream = None
+        self._lib = _lib.load()
+
+    @property
+    def nk(self) -> int:
+        return self.domain[2]
+
+    def __call__(self) -> None:
+        if any(r() is None for r in self._refs):
+            raise RuntimeError("LevelStats: an array this call was bound to no longer exists; build a new LevelStats")
+        self._stream = self._current_stream()
+        rc = self._lib.gt4mi_level_stats(self._fields, self._others, self._n, self._domain3, self._itemsize,
+                                         self._workspace.data_ptr(), self._workspace_bytes, self.result.ptr, 0,
+                                         self._stream.cuda_stream, None, None)
+        if rc != _lib.OK:
+            _lib.check("gt4mi_level_stats", rc)
+
+    def profile(self, name: str, entry: int = 0) -> DeviceArray:
+        """The contiguous ``(nk,)`` device view of one row of ``result``: ``name`` is a field of :class:`Stats` or ``"mean"``.
+        It holds what the LAST call left there, in stream order: pass it to a stencil as ``Field[K, np.float64]`` on the
+        stream of that call and no synchronisation is needed."""
+        if name not in PROFILE_ROWS:
+            raise ValueError(f"no profile {name!r}: the rows are {', '.join(PROFILE_ROWS)}")
+        entry = int(entry)
+        if not 0 <= entry < self._n:
+            raise IndexError(f"entry {entry} of {self._n}")
+        return self.result[entry, PROFILE_ROWS.index(name)]
+
+    def get(self) -> List[Profile]:
+        """Synchronise the stream of the last call and return its results (``RuntimeError`` before the first call)."""
+        if self._stream is None:
+            raise RuntimeError("LevelStats.get: the object has not been called yet")
+        self._stream.synchronize()
+        return [Profile.from_rows(block) for block in self.result.tensor.cpu().numpy()]
+
+
+def level_stats(*fields, other: Union[None, Any, Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
+                domain: Optional[Sequence[int]] = None, halo=0) -> List[Profile]:
+    """Per-level statistics of ``fields`` over their compute domain, one :class:`Profile` each: the synchronous one-shot form,
+    with the arguments of :func:`field_stats`.  One pass (per 8 fields) and one finishing launch on the current stream, then a
+    synchronisation of that stream.  With an IJ area weight as ``other``, ``dot`` is the area-weighted level sum.  In a time
+    loop build a :class:`LevelStats` once instead and read it a step late."""
+    if isinstance(other, (list, tuple)):
+        others = list(other)
+    else:
+        others = None if other is None else [other] * len(fields)
+    frozen = LevelStats(fields, others=others, origin=origin, domain=domain, halo=halo)
     frozen()
     return frozen.get()

@@ -219,6 +219,36 @@ int gt4mi_field_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
                       void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
                       int64_t* workspace_needed, int* launches);
 
+/* ---- per-level statistics, K profiles (NEW entry, additive: the ABI version stays 8; no reference counterpart -- GTScript has no
+ * reduction over I and J, gt4py leaves `field.sum(axis=(0, 1))` to numpy / cupy on its numpy / cupy storages) --------------------------
+ * gt4mi_field_stats for EVERY LEVEL k of the domain at once: the eight GT4MI_STATS_* slots over the plane (ni, nj) of level k, with
+ * their meaning, NaN rules and signed-zero rules, plus the horizontal mean.  One pass over the field (8 entries per launch) plus ONE
+ * finishing launch, on `stream`, without synchronisation or allocation.  Arguments, entries (a second field, which may be a
+ * broadcast weight such as an IJ cell area), flags and checks are those of gt4mi_field_stats.
+ *   workspace   partial[((entry * nk + k) * TL + t) * 8 + slot], *workspace_needed = nfields * nk * TL * 64 bytes
+ *   result      result[(entry * 9 + row) * nk + k] (device memory, float64; nfields * 9 * nk * 8 bytes): rows 0-7 are the slots, row
+ *               GT4MI_LEVEL_STATS_MEAN = SUM / COUNT (one IEEE division).  Slot-major: every profile is a contiguous run of nk
+ *               doubles that a later kernel on the same stream can read as a K field.
+ * THE ORDER OF THE ADDITIONS OF A LEVEL IS PART OF THE CONTRACT: it is a function of (ni, nj) alone (csrc/level_stats.hip.h states
+ * it, tests/level_stats_ref.py restates it in numpy) -- not of nk or of which level it is, of pointers, strides, padding, alignment,
+ * the number of entries in the call or anything about the device:
+ *   rows    RW = ceil(nj / (4 * LT)) rows (one j each) per wave, LT = GT4MI_LEVEL_STATS_MAX_TILES; TL = ceil(nj / (4 * RW)) tiles of 4
+ *           waves per level; wave w of tile t takes the rows [(4 t + w) RW, (4 t + w + 1) RW) that exist
+ *   lane, wave, tile   as gt4mi_field_stats: lane l adds the columns with (i mod 256) div 4 == l from +0.0 in (row, i) order, a
+ *           butterfly over the 64 lanes, the four waves left to right
+ *   finish  the TL tile values of a level are halved level by level, new[i] = old[2i] (+) old[2i + 1], an odd last one carried up
+ * The same plane gives the same bits, always; they are NOT the bits gt4mi_field_stats gives for that plane as a domain of its own.
+ * A level of more than 2^40 points, and nk * TL of more than 2^24, are GT4MI_ERR_UNSUPPORTED.
+ * Every check runs before the first launch; a refused call enqueues nothing.  *launches (may be NULL) = the kernels the call
+ * enqueues: ceil(nfields / 8) + 1. */
+#ifndef GT4MI_LEVEL_STATS_MAX_TILES
+#define GT4MI_LEVEL_STATS_MAX_TILES 32 /* part of the bit contract; a build-time define only so that it could be measured */
+#endif
+enum { GT4MI_LEVEL_STATS_MEAN = 8, GT4MI_LEVEL_STATS_ROWS = 9 };
+int gt4mi_level_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int elem_size,
+                      void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
+                      int64_t* workspace_needed, int* launches);
+
 /* ---- layout-converting field copy (NEW entry, additive: the ABI version stays 8.  Replaces what the reference does with numpy /
  * cupy slicing on its numpy / cupy storages and with `cp.asarray` (storage/cartesian/utils.py:187-189): moving a field between two
  * layouts, a storage and a dense buffer in numpy's C order among them) ------------------------------------------------------------
