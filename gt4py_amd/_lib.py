@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_field_stats",
     "gt4mi_level_stats",
     "gt4mi_field_copy",
+    "gt4mi_vertical_remap",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -106,6 +107,8 @@ LEVEL_STATS_MEAN, LEVEL_STATS_ROWS, LEVEL_STATS_MAX_TILES = 8, 9, 32
 # gt4mi_field_copy: paths, flags
 COPY_PATH_ROWS, COPY_PATH_TILES, COPY_PATH_ITEMS = 0, 1, 2
 COPY_CONVERT, COPY_DRY_RUN = 1, 256
+# gt4mi_vertical_remap: methods, flags
+REMAP_PCM, REMAP_PLM, REMAP_DRY_RUN = 0, 1, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -213,6 +216,8 @@ def _declare(lib: ctypes.CDLL) -> None:
         f.argtypes = [FP, FP, I, DOM, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_field_copy.restype = I
     lib.gt4mi_field_copy.argtypes = [FP, FP, I, DOM, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_vertical_remap.restype = I
+    lib.gt4mi_vertical_remap.argtypes = [FP, FP, I, FP, FP, DOM, ctypes.c_int64, ctypes.c_int64, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

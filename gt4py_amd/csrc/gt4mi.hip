@@ -14,6 +14,7 @@
 #include "field_stats.hip.h"
 #include "level_stats.hip.h"
 #include "field_copy.hip.h"
+#include "vertical_remap.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -215,6 +216,13 @@ int gt4mi_field_copy(const gt4mi_field* dst, const gt4mi_field* src, int nfields
                      int src_elem_size, int flags, void* stream, int* paths, int* launches) {
     return gt4mi::field_copy(dst, src, nfields, extent, dst_elem_size, src_elem_size, flags, static_cast<hipStream_t>(stream), paths,
                              launches);
+}
+
+int gt4mi_vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_edges,
+                         const gt4mi_field* dst_edges, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
+                         int edge_elem_size, int method, int flags, void* stream, int* launches) {
+    return gt4mi::vertical_remap(dst, src, nfields, src_edges, dst_edges, extent_ij, ns, nd, elem_size, edge_elem_size, method, flags,
+                                 static_cast<hipStream_t>(stream), launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

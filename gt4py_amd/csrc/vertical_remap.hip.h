@@ -1,0 +1,274 @@
+// Conservative vertical remapping: the cell means of up to 8 fields on the source levels of every column (i, j) become cell
+// means on the target levels of that column, ONE launch, the geometry of a column computed once for all its fields.
+//
+// NEW component, no reference counterpart: gt4py.cartesian leaves remapping to user stencils (a FORWARD sweep that carries a
+// run-time source index, a `while` over the overlapping source cells, a read at a run-time K index), one field per call.
+//
+// THE ARITHMETIC CONTRACT (include/gt4py_amd.h states it, tests/vertical_remap_ref.py restates it in plain Python).  All
+// arithmetic is float64, one rounding per operation, no FMA (-ffp-contract=off and the pragma of common.hip.h); float32 items
+// are widened exactly on load and the result is rounded once on store.  Per column: source edges zs[0..ns], target edges
+// zd[0..nd], source means q[0..ns-1].  The first source cell reaches to -inf, the last to +inf.  A source index k is kept
+// across the target cells of the column and only grows.  For target cell m, lo = zd[m], hi = zd[m+1], d = hi - lo:
+//   advance   while k < ns-1 and not (zs[k+1] > lo): k += 1
+//   terms     l = lo if k == 0 else (zs[k] if zs[k] > lo else lo);  r = hi if k == ns-1 else (zs[k+1] if zs[k+1] < hi else hi)
+//             w = (r - l) / d;  t = w * v_k;  the first term IS the accumulator (a lone -0.0 survives), later ones are added
+//             stop after the term with k == ns-1 or zs[k+1] >= hi, else k += 1
+//   out[m]    the accumulator (the weights carry 1/d)
+//   pcm       v_k = q[k]
+//   plm       v_k = q[k] + s[k] * (0.5 * (xl + xr) - 0.5),  h = zs[k+1] - zs[k],  xl = (l - zs[k]) / h,  xr = (r - zs[k]) / h
+//             s[0] = s[ns-1] = 0; else dl = q[k] - q[k-1], dr = q[k+1] - q[k]; if dl * dr > 0:
+//             g = (q[k+1] - q[k-1]) / (0.5 h[k-1] + h[k] + 0.5 h[k+1]) * h[k] (left to right), a = |g|, then a = 2|dl| if
+//             2|dl| < a, then a = 2|dr| if 2|dr| < a, s[k] = copysign(a, g); else s[k] = 0
+//
+// WHY THE LOOPS END WHATEVER THE DATA HOLDS: the loop over m counts to nd.  `step()` is the only place where k changes, it
+// adds 1, and both inner loops run it only under k < ns - 1: the advance loop tests that first, the term loop leaves at
+// k >= ns - 1 before it could step.  So a column makes at most ns - 1 steps and ns + nd - 1 terms; NaN, repeated or
+// non-monotone edges change which comparisons hold, never these counters.  Every K index of a load is k - 1 ... k + 2 guarded
+// against ns by the same integers, every K index of a store is m < nd: no address depends on the data.
+//
+// ONE THREAD PER COLUMN, lanes along I (the contiguous axis of the storage layout), a workgroup is 64 columns along I by 4
+// along J.  The lanes of a wave are at the same target level m (the stores of out[m] are one row) but at different source
+// levels k: the loads of q[k] touch a few rows per instruction.  Each lane reads every source item once, in order, one level
+// ahead of its use.  q[k-1], q[k], q[k+1], s[k] and the accumulator of every entry live in registers; the field loop is inside
+// the overlap loop.  No LDS, no workspace, no scratch, no atomics, no ordering between workgroups: the host refuses a call in
+// which a dst box meets a src box, an edge field or another dst box.
+#pragma once
+
+#include "common.hip.h"
+#include "field_copy.hip.h"
+
+namespace gt4mi {
+
+constexpr int REMAP_MAX_FIELDS = 8;
+constexpr int REMAP_TILE_I = 64, REMAP_TILE_J = 4;
+
+struct RemapEntry {
+    char* dst;        // first item of the box
+    const char* src;
+    int64_t d[3], s[3];  // strides in ITEMS
+};
+
+struct RemapEdges {
+    const char* p;  // edge 0 of the box's first column
+    int64_t s[3];   // strides in ITEMS; 0 along I / J broadcasts
+};
+
+struct RemapArgs {
+    RemapEntry e[REMAP_MAX_FIELDS];
+    RemapEdges zs, zd;
+    int ni, nj, ns, nd, nf;
+    unsigned tiles_i;
+};
+
+__device__ __forceinline__ double remap_slope(double qm, double qc, double qp, double hm, double hc, double hp) {
+    const double dl = qc - qm, dr = qp - qc;
+    if (!(dl * dr > 0.0)) return 0.0;
+    const double g = (qp - qm) / (0.5 * hm + hc + 0.5 * hp) * hc;
+    double a = fabs(g);
+    const double b = 2.0 * fabs(dl), c = 2.0 * fabs(dr);
+    if (b < a) a = b;
+    if (c < a) a = c;
+    return copysign(a, g);
+}
+
+// T: item type of the fields, E: of the edges, METHOD: GT4MI_REMAP_*, NF: entries the kernel has registers for (a.nf <= NF)
+template <typename T, typename E, int METHOD, int NF>
+__global__ void __launch_bounds__(REMAP_TILE_I * REMAP_TILE_J)
+vertical_remap_kernel(const RemapArgs a) {
+    constexpr bool PLM = METHOD == GT4MI_REMAP_PLM;
+    const unsigned tj = blockIdx.x / a.tiles_i, ti = blockIdx.x - tj * a.tiles_i;
+    const int64_t i = (int64_t)ti * REMAP_TILE_I + (threadIdx.x & 63u), j = (int64_t)tj * REMAP_TILE_J + (threadIdx.x >> 6);
+    if (i >= a.ni || j >= a.nj) return;
+    const int ns = a.ns, nd = a.nd, nf = a.nf;
+    const E* const zs = reinterpret_cast<const E*>(a.zs.p) + i * a.zs.s[0] + j * a.zs.s[1];
+    const E* const zd = reinterpret_cast<const E*>(a.zd.p) + i * a.zd.s[0] + j * a.zd.s[1];
+    const int64_t zsk = a.zs.s[2], zdk = a.zd.s[2];
+    const T* src[NF];
+    T* dst[NF];
+    double qm[NF], qc[NF], qp[NF], sl[NF], acc[NF];
+#pragma unroll
+    for (int n = 0; n < NF; ++n) {
+        qm[n] = qc[n] = qp[n] = sl[n] = acc[n] = 0.0;
+        src[n] = nullptr, dst[n] = nullptr;
+        if (n < nf) {
+            src[n] = reinterpret_cast<const T*>(a.e[n].src) + i * a.e[n].s[0] + j * a.e[n].s[1];
+            dst[n] = reinterpret_cast<T*>(a.e[n].dst) + i * a.e[n].d[0] + j * a.e[n].d[1];
+            qc[n] = (double)src[n][0];
+            if (ns > 1) qp[n] = (double)src[n][a.e[n].s[2]];
+        }
+    }
+    // source cell k = [zk, zk1), its neighbours' far edges zkm = zs[k-1] and zk2 = zs[k+2] where they exist
+    int k = 0;
+    double zkm = 0.0, zk = (double)zs[0], zk1 = (double)zs[zsk], zk2 = ns > 1 ? (double)zs[2 * zsk] : 0.0;
+
+    // the ONLY place where k changes; callers guarantee k < ns - 1 on entry
+    auto step = [&]() {
+        ++k;
+        zkm = zk, zk = zk1, zk1 = zk2;
+        if (k + 2 <= ns) zk2 = (double)zs[(int64_t)(k + 2) * zsk];
+        const bool inner = k < ns - 1;  // (k > 0 here)
+#pragma unroll
+        for (int n = 0; n < NF; ++n) {
+            if (n < nf) {
+                qm[n] = qc[n], qc[n] = qp[n];
+                if (inner) qp[n] = (double)src[n][(int64_t)(k + 1) * a.e[n].s[2]];
+                if constexpr (PLM) sl[n] = inner ? remap_slope(qm[n], qc[n], qp[n], zk - zkm, zk1 - zk, zk2 - zk1) : 0.0;
+            }
+        }
+    };
+
+    double hi = (double)zd[0];
+    for (int m = 0; m < nd; ++m) {
+        const double lo = hi;
+        hi = (double)zd[(int64_t)(m + 1) * zdk];
+        const double d = hi - lo;
+        while (k < ns - 1 && !(zk1 > lo)) step();
+        bool first = true;
+        for (;;) {
+            const double l = k == 0 ? lo : (zk > lo ? zk : lo);
+            const double r = k == ns - 1 ? hi : (zk1 < hi ? zk1 : hi);
+            const double w = (r - l) / d;
+            double c = 0.0;
+            if constexpr (PLM) {
+                const double h = zk1 - zk;
+                const double xl = (l - zk) / h, xr = (r - zk) / h;
+                c = 0.5 * (xl + xr) - 0.5;
+            }
+#pragma unroll
+            for (int n = 0; n < NF; ++n) {
+                if (n < nf) {
+                    const double v = PLM ? qc[n] + sl[n] * c : qc[n];
+                    const double t = w * v;
+                    acc[n] = first ? t : acc[n] + t;
+                }
+            }
+            first = false;
+            if (k >= ns - 1 || zk1 >= hi) break;
+            step();
+        }
+#pragma unroll
+        for (int n = 0; n < NF; ++n)
+            if (n < nf) dst[n][(int64_t)m * a.e[n].d[2]] = (T)acc[n];
+    }
+}
+
+inline int remap_check_field(const char* what, int n, const gt4mi_field& f, const int64_t extent[3], int elem_size, bool is_dst,
+                             bool is_edges) {
+    if (f.data == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: %s %d is null", what, n);
+    if (reinterpret_cast<uintptr_t>(f.data) % (uintptr_t)elem_size != 0)
+        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: %s %d is not aligned to its item size", what, n);
+    for (int ax = 0; ax < 3; ++ax) {
+        if (f.stride[ax] % elem_size != 0)
+            return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: %s %d: byte stride %lld along axis %d is not a multiple of the item size",
+                        what, n, (long long)f.stride[ax], ax);
+        if (is_dst && f.stride[ax] == 0 && extent[ax] > 1)
+            return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: dst %d has stride 0 along axis %d (only a src or an edge field may be broadcast)",
+                        n, ax);
+        if (is_edges && ax < 2 && f.stride[ax] == 0) continue;  // a Field[K] of edges: one item for every i / j, no shape to check
+        if (f.origin[ax] < 0)
+            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "vertical_remap: %s %d: negative origin %lld along axis %d", what, n,
+                        (long long)f.origin[ax], ax);
+        if (f.origin[ax] + extent[ax] > f.shape[ax])
+            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "vertical_remap: %s %d: origin %lld + extent %lld along axis %d is outside the array (shape %lld)",
+                        what, n, (long long)f.origin[ax], (long long)extent[ax], ax, (long long)f.shape[ax]);
+    }
+    return GT4MI_OK;
+}
+
+inline RemapEdges remap_edges(const gt4mi_field& f, int elem_size) {
+    RemapEdges e{};
+    e.p = static_cast<const char*>(f.data);
+    for (int ax = 0; ax < 3; ++ax) e.p += f.origin[ax] * f.stride[ax], e.s[ax] = f.stride[ax] / elem_size;
+    return e;
+}
+
+template <typename T, typename E, int METHOD>
+inline void remap_launch(const RemapArgs& a, int64_t blocks, hipStream_t stream) {
+    const dim3 grid((unsigned)blocks), block(REMAP_TILE_I * REMAP_TILE_J);
+    if (a.nf == 1) hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, 1>), grid, block, 0, stream, a);
+    else if (a.nf <= 4) hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, 4>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, 8>), grid, block, 0, stream, a);
+}
+
+template <typename T, typename E>
+inline void remap_launch_method(const RemapArgs& a, int64_t blocks, int method, hipStream_t stream) {
+    if (method == GT4MI_REMAP_PLM) remap_launch<T, E, GT4MI_REMAP_PLM>(a, blocks, stream);
+    else remap_launch<T, E, GT4MI_REMAP_PCM>(a, blocks, stream);
+}
+
+// every check, then (unless `flags` carries GT4MI_REMAP_DRY_RUN) the launches
+inline int vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_edges,
+                          const gt4mi_field* dst_edges, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
+                          int edge_elem_size, int method, int flags, hipStream_t stream, int* launches) {
+    if (launches) *launches = 0;
+    if (dst == nullptr || src == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: %s is null", dst == nullptr ? "dst" : "src");
+    if (src_edges == nullptr || dst_edges == nullptr)
+        return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: %s is null", src_edges == nullptr ? "src_edges" : "dst_edges");
+    if (extent_ij == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: extent_ij is null");
+    if (nfields < 1) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: nfields = %d, at least one pair is needed", nfields);
+    if (ns < 1 || nd < 1 || ns >= INT32_MAX - 2 || nd >= INT32_MAX - 2)
+        return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: ns = %lld source and nd = %lld target levels, at least one each is needed",
+                    (long long)ns, (long long)nd);
+    for (int ax = 0; ax < 2; ++ax)
+        if (extent_ij[ax] < 0 || extent_ij[ax] > INT32_MAX)
+            return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: invalid extent %lld along axis %d", (long long)extent_ij[ax], ax);
+    if (flags & ~GT4MI_REMAP_DRY_RUN) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: unknown bits in flags 0x%x", (unsigned)flags);
+    if (method != GT4MI_REMAP_PCM && method != GT4MI_REMAP_PLM)
+        return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: unknown method %d", method);
+    if (elem_size != 4 && elem_size != 8)
+        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: field item size %d is not supported (float32 or float64)", elem_size);
+    if (edge_elem_size != 4 && edge_elem_size != 8)
+        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: edge item size %d is not supported (float32 or float64)", edge_elem_size);
+    const int64_t d_ext[3] = {extent_ij[0], extent_ij[1], nd}, s_ext[3] = {extent_ij[0], extent_ij[1], ns};
+    const int64_t de_ext[3] = {extent_ij[0], extent_ij[1], nd + 1}, se_ext[3] = {extent_ij[0], extent_ij[1], ns + 1};
+    for (int n = 0; n < nfields; ++n) {
+        if (int rc = remap_check_field("dst", n, dst[n], d_ext, elem_size, true, false)) return rc;
+        if (int rc = remap_check_field("src", n, src[n], s_ext, elem_size, false, false)) return rc;
+    }
+    if (int rc = remap_check_field("src_edges", 0, *src_edges, se_ext, edge_elem_size, false, true)) return rc;
+    if (int rc = remap_check_field("dst_edges", 0, *dst_edges, de_ext, edge_elem_size, false, true)) return rc;
+    if (extent_ij[0] == 0 || extent_ij[1] == 0) return GT4MI_OK;
+    // no dst may meet any src, an edge field or another dst: what makes one launch without ordering between its threads correct
+    const ByteSpan se = field_copy_span(*src_edges, se_ext, edge_elem_size), de = field_copy_span(*dst_edges, de_ext, edge_elem_size);
+    for (int n = 0; n < nfields; ++n) {
+        const ByteSpan d = field_copy_span(dst[n], d_ext, elem_size);
+        if (spans_overlap(d, se)) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and src_edges overlap in memory", n);
+        if (spans_overlap(d, de)) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and dst_edges overlap in memory", n);
+        for (int m = 0; m < nfields; ++m) {
+            if (spans_overlap(d, field_copy_span(src[m], s_ext, elem_size)))
+                return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and src %d overlap in memory", n, m);
+            if (m > n && spans_overlap(d, field_copy_span(dst[m], d_ext, elem_size)))
+                return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and dst %d overlap in memory", n, m);
+        }
+    }
+    const int64_t tiles_i = cdiv(extent_ij[0], REMAP_TILE_I), blocks = tiles_i * cdiv(extent_ij[1], REMAP_TILE_J);
+    if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: too many columns for one launch");
+    if (launches) *launches = (int)cdiv(nfields, REMAP_MAX_FIELDS);
+    if (flags & GT4MI_REMAP_DRY_RUN) return GT4MI_OK;
+    RemapArgs a{};
+    a.zs = remap_edges(*src_edges, edge_elem_size), a.zd = remap_edges(*dst_edges, edge_elem_size);
+    a.ni = (int)extent_ij[0], a.nj = (int)extent_ij[1], a.ns = (int)ns, a.nd = (int)nd;
+    a.tiles_i = (unsigned)tiles_i;
+    for (int first = 0; first < nfields; first += REMAP_MAX_FIELDS) {
+        a.nf = nfields - first < REMAP_MAX_FIELDS ? nfields - first : REMAP_MAX_FIELDS;
+        for (int n = 0; n < REMAP_MAX_FIELDS; ++n) {
+            RemapEntry& e = a.e[n];
+            e = RemapEntry{};
+            if (n >= a.nf) continue;
+            const gt4mi_field &fd = dst[first + n], &fs = src[first + n];
+            e.dst = static_cast<char*>(fd.data), e.src = static_cast<const char*>(fs.data);
+            for (int ax = 0; ax < 3; ++ax) {
+                e.dst += fd.origin[ax] * fd.stride[ax], e.src += fs.origin[ax] * fs.stride[ax];
+                e.d[ax] = fd.stride[ax] / elem_size, e.s[ax] = fs.stride[ax] / elem_size;
+            }
+        }
+        if (elem_size == 8 && edge_elem_size == 8) remap_launch_method<double, double>(a, blocks, method, stream);
+        else if (elem_size == 8) remap_launch_method<double, float>(a, blocks, method, stream);
+        else if (edge_elem_size == 8) remap_launch_method<float, double>(a, blocks, method, stream);
+        else remap_launch_method<float, float>(a, blocks, method, stream);
+        GT4MI_HIP_CHECK(hipGetLastError());
+    }
+    return GT4MI_OK;
+}
+
+}  // namespace gt4mi

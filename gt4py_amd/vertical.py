@@ -1,0 +1,184 @@
+"""``gt4py_amd.vertical`` -- conservative remapping of columns from one set of levels to another, one kernel launch per 8 fields.
+
+A model on a Lagrangian or terrain-following vertical coordinate remaps its fields to fixed levels before output.  GTScript can
+write that (a FORWARD sweep that carries a run-time source index, a ``while`` over the overlapping source cells, a read at a
+run-time K index), but one field at a time; gt4py has no counterpart.  ``gt4mi_vertical_remap`` (csrc/vertical_remap.hip.h)
+computes the overlaps and weights of a column once and applies them to up to eight fields in the same launch, on the current
+stream, without synchronisation or allocation.
+
+    from gt4py_amd import transfer, vertical
+    vertical.remap_levels([u_p, v_p, t_p], [u, v, t], src_edges=z_model, dst_edges=z_fixed, method="plm")
+    to_levels = vertical.VerticalRemap([u_p, v_p, t_p], [u, v, t], src_edges=z_model, dst_edges=z_fixed)  # frozen
+    out = transfer.Download([u_p, v_p, t_p], dtype=np.float32)
+    for step in range(steps):
+        ...
+        if step % n == 0:
+            to_levels()          # enqueues; the download behind it on the same stream reads the remapped fields
+            pending = out()
+
+``src`` holds cell MEANS between the ``ns + 1`` edges of ``src_edges``, ``dst`` receives cell means between the ``nd + 1`` edges of
+``dst_edges``; edges increase with k (negate a coordinate that decreases).  An edge field is an IJK field, or a ``Field[K]`` that
+every column shares.  ``method`` is ``"pcm"`` (piecewise constant) or ``"plm"`` (piecewise linear with limited slopes: monotone).
+Both conserve the column integral when the outer edges of the two sets coincide; a target cell that reaches outside the source
+range sees the end cell's mean there.  The arithmetic -- float64 throughout, its order fixed -- is part of the contract
+(include/gt4py_amd.h): the same column gives the same bits whatever the layout, the position in the call or the device.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import weakref
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .boundary import _halo4
+from .storage.device_array import DeviceArray, as_device_array
+from .transfer import _as_list, _triple
+
+METHODS = {"pcm": _lib.REMAP_PCM, "plm": _lib.REMAP_PLM}
+_FLOATS = (np.dtype("float32"), np.dtype("float64"))
+
+
+def _native(dst, src, n: int, src_edges, dst_edges, extent_ij, ns: int, nd: int, size: int, edge_size: int, method: int, flags: int,
+            stream: Optional[int]) -> int:
+    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
+    library's message.  Returns the kernels enqueued."""
+    launches = ctypes.c_int(0)
+    rc = _lib.load().gt4mi_vertical_remap(dst, src, n, ctypes.byref(src_edges), ctypes.byref(dst_edges), extent_ij, ns, nd, size,
+                                          edge_size, method, flags, stream, ctypes.byref(launches))
+    if rc != _lib.OK:
+        message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
+        if rc == _lib.ERR_HIP:
+            raise _lib.NativeError("gt4mi_vertical_remap", rc, message)
+        raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+    return launches.value
+
+
+def _edge_field(a: DeviceArray, start) -> "_lib.Field":
+    if a.ndim == 1:  # Field[K]: every column reads the same items
+        return _lib.Field.make(a.ptr, (1, 1, a.shape[0]), (0, 0, a.strides[0]), (0, 0, start[2]))
+    return _lib.Field.make(a.ptr, a.shape, a.strides, start)
+
+
+class VerticalRemap:
+    """The frozen form of :func:`remap_levels` (what ``FrozenStencil`` is for stencils): arguments are checked (through the
+    library's dry run) and the native descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is
+    current THEN.
+
+    ``ns`` / ``nd`` are the source / target levels, ``extent`` the IJ box (the compute domain grown by the halo), ``launches`` the
+    kernels a call enqueues.  The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it
+    refuses to run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
+
+    def __init__(self, dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0, origin: Optional[Sequence[int]] = None):
+        dsts, srcs = _as_list(dst), _as_list(src)
+        if not dsts or not srcs:
+            raise ValueError("remap_levels needs at least one pair of fields")
+        if len(dsts) != len(srcs):
+            raise ValueError(f"remap_levels pairs fields one to one: {len(dsts)} destination(s) and {len(srcs)} source(s) were passed")
+        if method not in METHODS:
+            raise ValueError(f"method must be one of {sorted(METHODS)}, not {method!r}")
+        self.method = method
+        d_arrays = [as_device_array(f) for f in dsts]
+        s_arrays = [as_device_array(f) for f in srcs]
+        e_arrays = [as_device_array(src_edges), as_device_array(dst_edges)]
+        self._halo = _halo4(halo)
+        if min(self._halo) < 0:
+            raise ValueError(f"halo widths must not be negative: {self._halo}")
+        for a in d_arrays + s_arrays:
+            if a.ndim != 3:
+                raise ValueError(f"remap_levels takes IJK fields, not a field of {a.ndim} dimension(s)")
+        for name, a in zip(("src_edges", "dst_edges"), e_arrays):
+            if a.ndim not in (1, 3):
+                raise ValueError(f"{name} must be an IJK field or a Field[K], not a field of {a.ndim} dimension(s)")
+        dtype = d_arrays[0].dtype
+        for a in d_arrays + s_arrays:
+            if a.dtype != dtype:
+                raise TypeError(f"the fields of one call share a dtype: {dtype} and {a.dtype} differ")
+        if dtype not in _FLOATS:
+            raise TypeError(f"remap_levels takes float32 or float64 fields, not {dtype}")
+        if e_arrays[0].dtype != e_arrays[1].dtype:
+            raise TypeError(f"src_edges and dst_edges share a dtype: {e_arrays[0].dtype} and {e_arrays[1].dtype} differ")
+        if e_arrays[0].dtype not in _FLOATS:
+            raise TypeError(f"edge fields are float32 or float64, not {e_arrays[0].dtype}")
+        lo_i, hi_i, lo_j, hi_j = self._halo
+        origin = (lo_i, lo_j, 0) if origin is None else _triple(origin, "origin", 0)
+        self.origin = origin
+        # levels: what every src / dst has behind the origin; an edge field has one more
+        levels = []
+        for side, arrays, edges, name in (("sources", s_arrays, e_arrays[0], "src_edges"), ("destinations", d_arrays, e_arrays[1], "dst_edges")):
+            n = arrays[0].shape[2] - origin[2]
+            if n < 1:
+                raise ValueError(f"origin {origin} leaves no level in the {side} (shape {arrays[0].shape})")
+            for a in arrays:
+                if a.shape[2] - origin[2] != n:
+                    raise ValueError(f"the {side} of one call share their number of levels: {n} and {a.shape[2] - origin[2]} differ")
+            have = edges.shape[-1] - origin[2]
+            if have != n + 1:
+                raise ValueError(f"{name} has {have} edges along K, {n} levels need {n + 1}")
+            levels.append(n)
+        self.ns, self.nd = levels
+        # the common IJ compute domain: what every IJK array has left behind its origin and in front of its high ghost cells
+        rest = [tuple(s - o - h for s, o, h in zip(a.shape[:2], origin[:2], (hi_i, hi_j))) for a in d_arrays + s_arrays + e_arrays if a.ndim == 3]
+        domain = tuple(min(r[ax] for r in rest) for ax in range(2))
+        if min(domain) < 0:
+            raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in fields of shapes {[a.shape for a in d_arrays + s_arrays]}")
+        self.domain = domain
+        #: the IJ box that is remapped: the domain grown by the halo
+        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j)
+        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
+        self._n = len(d_arrays)
+        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
+        for table, arrays in ((self._dst, d_arrays), (self._src, s_arrays)):
+            for n, a in enumerate(arrays):
+                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, start)
+        self._src_edges, self._dst_edges = (_edge_field(a, start) for a in e_arrays)
+        self._extent2 = (ctypes.c_int64 * 2)(*self.extent)
+        self._size, self._edge_size, self._method = d_arrays[0].itemsize, e_arrays[0].itemsize, METHODS[method]
+        # every check of the library, nothing enqueued; also: how many kernels
+        self.launches = _native(self._dst, self._src, self._n, self._src_edges, self._dst_edges, self._extent2, self.ns, self.nd,
+                                self._size, self._edge_size, self._method, _lib.REMAP_DRY_RUN, None)
+        # (last: none of the checks above needs a device)
+        for a in d_arrays + s_arrays + e_arrays:
+            if not a.tensor.is_cuda:
+                raise TypeError("remap_levels works on device fields; a host array was passed")
+        # what must stay alive is what the CALLER holds (see boundary.HaloFill)
+        self._refs, self._held = [], []
+        for f in dsts + srcs + [src_edges, dst_edges]:
+            try:
+                self._refs.append(weakref.ref(f))
+            except TypeError:
+                self._held.append(f)
+        import torch
+
+        self._current_stream = torch.cuda.current_stream
+        self._lib = _lib.load()
+
+    def __call__(self) -> None:
+        if any(r() is None for r in self._refs):
+            raise RuntimeError("VerticalRemap: an array this call was bound to no longer exists; build a new VerticalRemap")
+        rc = self._lib.gt4mi_vertical_remap(self._dst, self._src, self._n, ctypes.byref(self._src_edges), ctypes.byref(self._dst_edges),
+                                            self._extent2, self.ns, self.nd, self._size, self._edge_size, self._method, 0,
+                                            self._current_stream().cuda_stream, None)
+        if rc != _lib.OK:
+            _lib.check("gt4mi_vertical_remap", rc)
+
+
+def remap_levels(dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0, origin: Optional[Sequence[int]] = None) -> None:
+    """Remap the cell means ``src`` between the edges ``src_edges`` to cell means ``dst`` between the edges ``dst_edges``, column
+    by column over the compute domain (plus ``halo`` ghost cells in I and J), in one kernel launch (per 8 pairs) on the current
+    stream.
+
+    ``dst``, ``src``  one field each or two sequences of equal length: IJK :class:`DeviceArray`\\ s of one dtype (float32 or
+                float64) or anything ``as_device_array`` accepts; every field may differ in address, strides and padding.  The
+                sources share their number of levels ``ns``, the destinations theirs ``nd``.
+    ``src_edges``, ``dst_edges``  ``ns + 1`` / ``nd + 1`` edges along K, increasing: IJK fields or ``Field[K]`` (shared by every
+                column), of one dtype (float32 or float64, not necessarily the fields').
+    ``method``  ``"pcm"`` or ``"plm"``.
+    ``halo``    an int, ``(hi, hj)`` or ``((lo_i, hi_i), (lo_j, hi_j))``, as for ``boundary.fill_halo``.
+    ``origin``  first compute-domain point of every IJK array, default ``(lo_i, lo_j, 0)``.
+
+    Raises ``ValueError`` / ``TypeError`` (with the library's message) before any GPU work.  For a time loop build a
+    :class:`VerticalRemap` once instead."""
+    VerticalRemap(dst, src, src_edges=src_edges, dst_edges=dst_edges, method=method, halo=halo, origin=origin)()

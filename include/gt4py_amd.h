@@ -271,6 +271,52 @@ enum { GT4MI_COPY_CONVERT = 1, GT4MI_COPY_DRY_RUN = 256 };
 int gt4mi_field_copy(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const int64_t extent[3],
                      int dst_elem_size, int src_elem_size, int flags, void* stream, int* paths, int* launches);
 
+/* ---- conservative vertical remapping (NEW entry, additive: the ABI version stays 8; no reference counterpart -- gt4py leaves remapping
+ * a column from one set of levels to another to user stencils: a FORWARD sweep with a carried run-time index, a `while` and a read at
+ * a run-time K index, one field per call) ---------------------------------------------------------------------------------------------
+ * Remaps the cell means src[n] on the source levels of every column (i, j) of the box to cell means dst[n] on the target levels of
+ * that column, for `nfields` pairs that share ONE pair of edge fields, in ONE kernel launch per 8 pairs, on `stream`, without
+ * synchronisation or allocation.  The box is [origin, origin + extent_ij) in I and J of every field; along K a src holds `ns` levels
+ * from its origin, a dst `nd`, src_edges `ns + 1` and dst_edges `nd + 1`.  `elem_size` (fields) and `edge_elem_size` (edge fields) are
+ * 4 (float32) or 8 (float64).  An edge field may have byte stride 0 along I and / or J: a Field[K] of fixed levels broadcasts without a
+ * copy and is exempt from the shape check on that axis.  A src stride of 0 broadcasts too; a dst stride of 0 on an extent above 1 is
+ * GT4MI_ERR_INVALID_ARGUMENT.
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/vertical_remap.hip.h states it again, tests/vertical_remap_ref.py restates it in plain
+ * Python).  All of it is float64, one IEEE rounding per operation, no FMA; float32 items are widened exactly on load and the result is
+ * rounded once on store.  Per column: source edges zs[0..ns], target edges zd[0..nd], both meant to increase strictly with k, source
+ * means q[0..ns-1], target means out[0..nd-1].  The first source cell extends to -inf and the last to +inf: a target cell that reaches
+ * outside the source range sees the end cell's mean there, the weights still sum to 1, nothing is extrapolated.  A source index k is
+ * kept across the target cells of the column and never decreases.  For target cell m, lo = zd[m], hi = zd[m+1], d = hi - lo:
+ *   1. advance: while k < ns-1 and not (zs[k+1] > lo): k += 1
+ *   2. for each overlapping k, in increasing order:
+ *        l = lo if k == 0    else max(lo, zs[k])     (max(a, b) = b if b > a else a)
+ *        r = hi if k == ns-1 else min(hi, zs[k+1])   (min(a, b) = b if b < a else a)
+ *        w = (r - l) / d, one IEEE division;  t = w * v_k
+ *        the first term initialises the accumulator (a lone -0.0 survives), later terms are added in this order
+ *        stop after the term for which k == ns-1 or zs[k+1] >= hi, otherwise k += 1
+ *   3. out[m] is the accumulator: no final division, the weights carry 1/d
+ *   GT4MI_REMAP_PCM (piecewise constant)        v_k = q[k]
+ *   GT4MI_REMAP_PLM (piecewise linear, limited) v_k = q[k] + s[k] * (0.5 * (xl + xr) - 0.5),  h[k] = zs[k+1] - zs[k],
+ *        xl = (l - zs[k]) / h[k],  xr = (r - zs[k]) / h[k];  the slope across the cell: s[0] = s[ns-1] = 0, and for 0 < k < ns-1 with
+ *        dl = q[k] - q[k-1], dr = q[k+1] - q[k]:  if dl * dr > 0 then g = (q[k+1] - q[k-1]) / (0.5 * h[k-1] + h[k] + 0.5 * h[k+1]) * h[k]
+ *        (left to right) and s[k] = copysign(min(|g|, 2|dl|, 2|dr|), g) (min as above, in this order), otherwise s[k] = 0
+ * With zd identical to zs, pcm returns q bit for bit; plm too, except that -0.0 comes back as +0.0 (q + s * 0.0) where the slope is not
+ * negative.  A column makes at most
+ * ns + nd - 1 terms.  k only grows and every step of either loop stops or increments k, so both loops are bounded by integer counters
+ * whatever the data holds: NaN, repeated and non-monotone edges give that column whatever IEEE arithmetic gives (0 / 0 = NaN for a
+ * target cell of zero thickness) and affect no other column.  Edges that DECREASE with k are out of scope: negate the coordinate.
+ * Refusals: null pointers, nfields < 1, ns < 1, nd < 1, an unknown method or flag (GT4MI_ERR_INVALID_ARGUMENT); an item size other
+ * than 4 or 8, a misaligned field (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS); the bytes of a
+ * dst box (first to last item) meeting those of any src box, of an edge field or of another dst box (GT4MI_ERR_UNSUPPORTED, the rule of
+ * gt4mi_field_copy).  No byte outside the dst boxes changes.  An extent with a zero entry is GT4MI_OK, nothing enqueued.
+ * Every check runs before the first launch; a refused call enqueues nothing.  With GT4MI_REMAP_DRY_RUN the checks run, *launches is
+ * set and no device is touched.  *launches (may be NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_REMAP_PCM = 0, GT4MI_REMAP_PLM = 1 };
+enum { GT4MI_REMAP_DRY_RUN = 256 };
+int gt4mi_vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_edges,
+                         const gt4mi_field* dst_edges, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
+                         int edge_elem_size, int method, int flags, void* stream, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
