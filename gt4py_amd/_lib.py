@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_level_stats",
     "gt4mi_field_copy",
     "gt4mi_vertical_remap",
+    "gt4mi_horizontal_interp",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -109,6 +110,9 @@ COPY_PATH_ROWS, COPY_PATH_TILES, COPY_PATH_ITEMS = 0, 1, 2
 COPY_CONVERT, COPY_DRY_RUN = 1, 256
 # gt4mi_vertical_remap: methods, flags
 REMAP_PCM, REMAP_PLM, REMAP_DRY_RUN = 0, 1, 256
+# gt4mi_horizontal_interp: methods, flags
+INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC, INTERP_CUBIC_MONOTONE = 0, 1, 2, 3
+INTERP_RELATIVE, INTERP_DRY_RUN = 1, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -218,6 +222,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_field_copy.argtypes = [FP, FP, I, DOM, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_vertical_remap.restype = I
     lib.gt4mi_vertical_remap.argtypes = [FP, FP, I, FP, FP, DOM, ctypes.c_int64, ctypes.c_int64, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_horizontal_interp.restype = I
+    lib.gt4mi_horizontal_interp.argtypes = [FP, FP, I, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

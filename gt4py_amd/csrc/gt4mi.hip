@@ -15,6 +15,7 @@
 #include "level_stats.hip.h"
 #include "field_copy.hip.h"
 #include "vertical_remap.hip.h"
+#include "horizontal_interp.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -223,6 +224,13 @@ int gt4mi_vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfi
                          int edge_elem_size, int method, int flags, void* stream, int* launches) {
     return gt4mi::vertical_remap(dst, src, nfields, src_edges, dst_edges, extent_ij, ns, nd, elem_size, edge_elem_size, method, flags,
                                  static_cast<hipStream_t>(stream), launches);
+}
+
+int gt4mi_horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* pos_i,
+                            const gt4mi_field* pos_j, const int64_t extent[3], const int64_t reach[4], int elem_size,
+                            int pos_elem_size, int method, int flags, void* stream, int* launches) {
+    return gt4mi::horizontal_interp(dst, src, nfields, pos_i, pos_j, extent, reach, elem_size, pos_elem_size, method, flags,
+                                    static_cast<hipStream_t>(stream), launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

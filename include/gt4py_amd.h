@@ -317,6 +317,53 @@ int gt4mi_vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfi
                          const gt4mi_field* dst_edges, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
                          int edge_elem_size, int method, int flags, void* stream, int* launches);
 
+/* ---- horizontal interpolation at run-time positions (NEW entry, additive: the ABI version stays 8; no reference counterpart -- GTScript
+ * takes compile-time horizontal offsets only, and gt4py leaves a gather at data-dependent I / J positions (semi-Lagrangian departure
+ * points, sampling on a rotated, shifted or nested grid) to fancy indexing on its numpy / cupy storages) --------------------------------
+ * For every point (i, j, k) of the box [origin, origin + extent) of every dst[n] -- the compute domain -- writes the value of src[n] at
+ * level k and the horizontal position (x_i, x_j) that pos_i / pos_j hold for that point, for `nfields` pairs that share ONE pair of
+ * position fields, in ONE kernel launch per 8 pairs, on `stream`, without synchronisation or allocation.  `elem_size` (fields) and
+ * `pos_elem_size` (position fields) are 4 (float32) or 8 (float64) and need not match.  A position field may have byte stride 0 along K:
+ * a Field[IJ] shared by every level broadcasts without a copy and is exempt from the shape check on that axis.
+ * Positions are in index units of the compute domain: 0.0 is domain point 0 (the origin of src[n]).  With GT4MI_INTERP_RELATIVE they are
+ * displacements: x = double(index) + p (what a stencil can produce: it has no I or J as a value).  The readable box of a src is the
+ * domain grown by `reach` = {lo_i, hi_i, lo_j, hi_j} ghost cells; it must fit the array (origin - lo >= 0, origin + extent + hi <= shape).
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/horizontal_interp.hip.h states it again, tests/horizontal_interp_ref.py restates it in
+ * plain Python).  All of it is float64, one IEEE rounding per operation, no FMA; float32 items and positions are widened exactly on load
+ * and the result is rounded once on store.  Per axis, with n domain points, xmin = -lo and xmax = n - 1 + hi as doubles:
+ *   1. p = the position item; in relative mode p = double(index) + p
+ *   2. x = xmin if p < xmin else (xmax if p > xmax else p): NaN passes through, +-inf clamps
+ *   3. b = xmin if x != x else (int64) floor(x), t = x - double(b) (x is finite or NaN, the conversion is always defined)
+ *   4. every index a method uses is clamped on its own to [xmin, xmax]: edge replication; b-1, b, b+1, b+2 for the cubics and b, b+1 for
+ *      linear are each clamped separately.  No address depends on the data beyond these integers.
+ *   GT4MI_INTERP_NEAREST         the index is floor(x + 0.5), clamped; the source item's bit pattern is moved (a NaN payload survives);
+ *                                a NaN position stores the canonical quiet NaN (0x7FC00000 / 0x7FF8000000000000)
+ *   GT4MI_INTERP_LINEAR          w0 = 1 - t, w1 = t per axis; at row b_j  r0 = w0i*v00 + w1i*v10, at row b_j + 1  r1 likewise;
+ *                                out = w0j*r0 + w1j*r1, each product rounded before its addition
+ *   GT4MI_INTERP_CUBIC           Lagrange on the nodes -1, 0, 1, 2; with a = t + 1, c = t - 1, d = t - 2:
+ *                                w_-1 = -(((t*c)*d) / 6.0), w_0 = ((a*c)*d) / 2.0, w_1 = -(((a*t)*d) / 2.0), w_2 = ((a*t)*c) / 6.0;
+ *                                the four row values r = ((w_-1*v_-1 + w_0*v_0) + w_1*v_1) + w_2*v_2 along I, the same expression
+ *                                along J over the four r gives out
+ *   GT4MI_INTERP_CUBIC_MONOTONE  the cubic out, then out = mn if out < mn else (mx if out > mx else out), mn = min(min(c00, c10),
+ *                                min(c01, c11)) and mx likewise over the four corner items at the clamped indices b, b+1 of each axis,
+ *                                min(a, b) = b if b < a else a, max(a, b) = b if b > a else a; a NaN out stays NaN
+ * Consequences: a weight of zero still multiplies (0 * inf = NaN at an integer position next to an infinity); -0.0 may come back as
+ * +0.0; a NaN position gives NaN in every field of that point and touches nothing else; the bits of a point do not depend on layout,
+ * strides, alignment, position in the call, number of fields in the call, Field[IJ] versus an IJK position field with the same items,
+ * or device.  Periodic wrap is not part of the kernel: fill the ghost cells with gt4mi_halo_fill first.
+ * Refusals: null pointers, nfields < 1, an unknown method or flag, a negative reach (GT4MI_ERR_INVALID_ARGUMENT); an item size other
+ * than 4 or 8, a misaligned field (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS); the bytes of a
+ * dst box (first to last item) meeting those of any src readable box, of a position field or of another dst box (GT4MI_ERR_UNSUPPORTED,
+ * the rule of gt4mi_field_copy); a dst stride of 0 on an extent above 1 (GT4MI_ERR_INVALID_ARGUMENT).  No byte outside the dst boxes
+ * changes.  An extent with a zero entry is GT4MI_OK, nothing enqueued.  Every check runs before the first launch; a refused call
+ * enqueues nothing.  With GT4MI_INTERP_DRY_RUN the checks run, *launches is set and no device is touched.  *launches (may be NULL) =
+ * the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_INTERP_NEAREST = 0, GT4MI_INTERP_LINEAR = 1, GT4MI_INTERP_CUBIC = 2, GT4MI_INTERP_CUBIC_MONOTONE = 3 };
+enum { GT4MI_INTERP_RELATIVE = 1, GT4MI_INTERP_DRY_RUN = 256 };
+int gt4mi_horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* pos_i,
+                            const gt4mi_field* pos_j, const int64_t extent[3], const int64_t reach[4], int elem_size,
+                            int pos_elem_size, int method, int flags, void* stream, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
