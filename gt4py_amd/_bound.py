@@ -1,0 +1,156 @@
+"""What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
+``vertical.VerticalRemap``, ``horizontal.HorizontalInterp``) share on the Python side: turning a refusal of the library into an
+exception, normalising halo / origin / domain / field lists, and binding a checked call to the caller's objects.  A new
+utility states what differs (its name in the messages, its extra fields) and takes the rest from here."""
+
+from __future__ import annotations
+
+import weakref
+from typing import NoReturn, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .storage.device_array import DeviceArray, as_device_array
+
+FLOATS = (np.dtype("float32"), np.dtype("float64"))
+
+
+def raise_refusal(func: str, rc: int) -> NoReturn:
+    """A non-zero status of entry ``func`` as an exception with the library's message: ``ValueError``, ``TypeError`` for what
+    no kernel handles (``ERR_UNSUPPORTED``), :class:`~gt4py_amd._lib.NativeError` for a HIP error."""
+    message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
+    if rc == _lib.ERR_HIP:
+        raise _lib.NativeError(func, rc, message)
+    raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+
+
+def _halo4(halo) -> Tuple[int, int, int, int]:
+    def integer(x):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"halo widths must be ints, not {type(x).__name__}")
+        return int(x)
+
+    if isinstance(halo, (int, np.integer)):
+        h = integer(halo)
+        return h, h, h, h
+    if not isinstance(halo, (tuple, list)) or len(halo) != 2:
+        raise ValueError(f"halo must be an int, (hi, hj) or ((lo_i, hi_i), (lo_j, hi_j)), not {halo!r}")
+    out = []
+    for axis in halo:
+        if isinstance(axis, (tuple, list)):
+            if len(axis) != 2:
+                raise ValueError(f"halo must be an int, (hi, hj) or ((lo_i, hi_i), (lo_j, hi_j)), not {halo!r}")
+            out += [integer(axis[0]), integer(axis[1])]
+        else:
+            out += [integer(axis)] * 2
+    return tuple(out)  # type: ignore[return-value]
+
+
+def _as_list(fields) -> list:
+    """One field or a sequence of fields (a tuple or list; an array is ONE field whatever its length)."""
+    return list(fields) if isinstance(fields, (tuple, list)) else [fields]
+
+
+def _triple(value, name: str, fill: int) -> Tuple[int, int, int]:
+    value = tuple(int(v) for v in value)
+    if len(value) > 3:
+        raise ValueError(f"{name} must have at most three entries, not {value}")
+    return value + (fill,) * (3 - len(value))  # type: ignore[return-value]
+
+
+def _shape3(a: DeviceArray) -> Tuple[int, ...]:
+    return tuple(a.shape) + (1,) * (3 - a.ndim)
+
+
+def _origin3(origin, halo4) -> Tuple[int, int, int]:
+    """``origin`` as three ints; by default the first point behind the low ghost cells."""
+    return (halo4[0], halo4[2], 0) if origin is None else _triple(origin, "origin", 0)
+
+
+def _box_of(first: DeviceArray, halo4, origin, domain, least: int):
+    """(origin, domain) of a call whose fields share both: ``domain`` defaults to what ``first`` has left behind ``origin`` and in
+    front of its high ghost cells, which must be at least ``least`` points along every axis."""
+    origin = _origin3(origin, halo4)
+    if domain is None:
+        domain = tuple(s - o - h for s, o, h in zip(_shape3(first), origin, (halo4[1], halo4[3], 0)))
+        if min(domain) < least:
+            raise ValueError(f"halo {halo4} and origin {origin} leave no domain in a field of shape {first.shape}")
+    return origin, _triple(domain, "domain", 1)
+
+
+def _pair_lists(who: str, dst, src, halo, method=None, methods=None, shared=()):
+    """The opening of a call on (dst, src) pairs, in the order the checks have always had: two lists of equal length, a known
+    ``method`` (where there are ``methods``), DeviceArrays of everything (``shared``: fields every pair reads), the halo.
+    Returns (dsts, srcs, dst arrays, src arrays, shared arrays, halo4)."""
+    dsts, srcs = _as_list(dst), _as_list(src)
+    if not dsts or not srcs:
+        raise ValueError(f"{who} needs at least one pair of fields")
+    if len(dsts) != len(srcs):
+        raise ValueError(f"{who} pairs fields one to one: {len(dsts)} destination(s) and {len(srcs)} source(s) were passed")
+    if methods is not None and method not in methods:
+        raise ValueError(f"method must be one of {sorted(methods)}, not {method!r}")
+    d_arrays = [as_device_array(f) for f in dsts]
+    s_arrays = [as_device_array(f) for f in srcs]
+    x_arrays = [as_device_array(f) for f in shared]
+    halo4 = _halo4(halo)
+    if min(halo4) < 0:
+        raise ValueError(f"halo widths must not be negative: {halo4}")
+    return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4
+
+
+def _float_pairs(who: str, dst, src, halo, method, methods, *, shared, names: Sequence[str], ndims: Tuple[int, int], kind: str, plural: str):
+    """:func:`_pair_lists` for IJK fields of ONE float dtype and two shared fields ``names`` (of ``ndims`` dimensions: IJK or a
+    ``kind``) of one float dtype of their own; ``plural`` is what the last message calls them."""
+    dsts, srcs, d_arrays, s_arrays, x_arrays, halo4 = _pair_lists(who, dst, src, halo, method, methods, shared)
+    for a in d_arrays + s_arrays:
+        if a.ndim != 3:
+            raise ValueError(f"{who} takes IJK fields, not a field of {a.ndim} dimension(s)")
+    for name, a in zip(names, x_arrays):
+        if a.ndim not in ndims:
+            raise ValueError(f"{name} must be an IJK field or a {kind}, not a field of {a.ndim} dimension(s)")
+    dtype = d_arrays[0].dtype
+    for a in d_arrays + s_arrays:
+        if a.dtype != dtype:
+            raise TypeError(f"the fields of one call share a dtype: {dtype} and {a.dtype} differ")
+    if dtype not in FLOATS:
+        raise TypeError(f"{who} takes float32 or float64 fields, not {dtype}")
+    if x_arrays[0].dtype != x_arrays[1].dtype:
+        raise TypeError(f"{names[0]} and {names[1]} share a dtype: {x_arrays[0].dtype} and {x_arrays[1].dtype} differ")
+    if x_arrays[0].dtype not in FLOATS:
+        raise TypeError(f"{plural} are float32 or float64, not {x_arrays[0].dtype}")
+    return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4
+
+
+def refuse_host_arrays(who: str, arrays) -> None:
+    for a in arrays:
+        if not a.tensor.is_cuda:
+            raise TypeError(f"{who} works on device fields; a host array was passed")
+
+
+class Bound:
+    """Base of the frozen calls: a constructor checks its arguments through the library's dry run, builds the native
+    descriptors and calls :meth:`_bind` last; ``__call__`` is :meth:`_check_alive` and the one ctypes call."""
+
+    def _bind(self, who: str, arrays, objects) -> None:
+        """``who``: the public function's name; ``arrays``: the DeviceArrays of the call; ``objects``: what the caller passed."""
+        refuse_host_arrays(who, arrays)  # (last: none of the checks before needs a device)
+        # what must stay alive is what the CALLER holds: for a torch tensor or another exporter `as_device_array` made a wrapper
+        # that dies with the constructor, so the weak reference goes to the object that was passed; one that cannot be weakly
+        # referenced is held instead
+        self._refs, self._held = [], []
+        for f in objects:
+            try:
+                self._refs.append(weakref.ref(f))
+            except TypeError:
+                self._held.append(f)
+        import torch
+
+        self._current_stream = torch.cuda.current_stream
+        self._lib = _lib.load()
+
+    def _check_alive(self) -> None:
+        for r in self._refs:  # (a plain loop: this runs in front of every call)
+            if r() is None:
+                name = type(self).__name__
+                raise RuntimeError(f"{name}: an array this call was bound to no longer exists; build a new {name}")

@@ -20,12 +20,12 @@ Bit patterns are moved, never computed: bool and integer fields work, NaN payloa
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Any, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
+from ._bound import Bound, _box_of, _halo4, _shape3, raise_refusal
 from .storage.device_array import DeviceArray, as_device_array
 
 I_LO, I_HI, J_LO, J_HI = _lib.HALO_I_LO, _lib.HALO_I_HI, _lib.HALO_J_LO, _lib.HALO_J_HI
@@ -60,28 +60,6 @@ def _mode_pair(mode) -> Tuple[int, int]:
     return MODES[pair[0]], MODES[pair[1]]
 
 
-def _halo4(halo) -> Tuple[int, int, int, int]:
-    def integer(x):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise TypeError(f"halo widths must be ints, not {type(x).__name__}")
-        return int(x)
-
-    if isinstance(halo, (int, np.integer)):
-        h = integer(halo)
-        return h, h, h, h
-    if not isinstance(halo, (tuple, list)) or len(halo) != 2:
-        raise ValueError(f"halo must be an int, (hi, hj) or ((lo_i, hi_i), (lo_j, hi_j)), not {halo!r}")
-    out = []
-    for axis in halo:
-        if isinstance(axis, (tuple, list)):
-            if len(axis) != 2:
-                raise ValueError(f"halo must be an int, (hi, hj) or ((lo_i, hi_i), (lo_j, hi_j)), not {halo!r}")
-            out += [integer(axis[0]), integer(axis[1])]
-        else:
-            out += [integer(axis)] * 2
-    return tuple(out)  # type: ignore[return-value]
-
-
 def _native(fields, nfields: int, domain, halo4, modes, sides: int, value, itemsize: int, stream: Optional[int]) -> int:
     """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for an item size no kernel moves)
     with the library's message.  Returns the number of kernels enqueued."""
@@ -89,14 +67,11 @@ def _native(fields, nfields: int, domain, halo4, modes, sides: int, value, items
     rc = _lib.load().gt4mi_halo_fill(fields, nfields, domain, halo4, modes[0], modes[1], sides, value, itemsize, stream,
                                      ctypes.byref(launches))
     if rc != _lib.OK:
-        message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
-        if rc == _lib.ERR_HIP:
-            raise _lib.NativeError("gt4mi_halo_fill", rc, message)
-        raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+        raise_refusal("gt4mi_halo_fill", rc)
     return launches.value
 
 
-class HaloFill:
+class HaloFill(Bound):
     """The frozen form of :func:`fill_halo` (what ``FrozenStencil`` is for stencils): arguments are checked and the native
     descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is current THEN.
 
@@ -123,21 +98,7 @@ class HaloFill:
             if a.itemsize != first.itemsize or (a.dtype != first.dtype and _lib.HALO_CONSTANT in self._modes):
                 raise TypeError(f"the fields of one call share an item size (and, for 'constant', a dtype): {first.dtype} and "
                                 f"{a.dtype} differ")
-        if origin is None:
-            origin = (self._halo[0], self._halo[2], 0)
-        origin = tuple(int(o) for o in origin)
-        origin = origin + (0,) * (3 - len(origin))
-        if len(origin) != 3:
-            raise ValueError(f"origin must have at most three entries, not {origin}")
-        shape3 = tuple(first.shape) + (1,) * (3 - first.ndim)
-        if domain is None:
-            domain = (shape3[0] - origin[0] - self._halo[1], shape3[1] - origin[1] - self._halo[3], shape3[2] - origin[2])
-            if min(domain) < 0:
-                raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in a field of shape {first.shape}")
-        domain = tuple(int(d) for d in domain)
-        domain = domain + (1,) * (3 - len(domain))
-        if len(domain) != 3:
-            raise ValueError(f"domain must have at most three entries, not {domain}")
+        origin, domain = _box_of(first, self._halo, origin, domain, 0)
         self.origin, self.domain = origin, domain
         self._itemsize = first.itemsize
         # the scalar of "constant": one item of the fields' dtype, passed as its bytes (a value the dtype cannot hold is refused)
@@ -151,33 +112,16 @@ class HaloFill:
         self._n = len(arrays)
         self._fields = (_lib.Field * self._n)()
         for n, a in enumerate(arrays):
-            self._fields[n] = _lib.Field.make(a.ptr, tuple(a.shape) + (1,) * (3 - a.ndim), tuple(a.strides) + (0,) * (3 - a.ndim),
-                                              origin)
+            self._fields[n] = _lib.Field.make(a.ptr, _shape3(a), tuple(a.strides) + (0,) * (3 - a.ndim), origin)
         self._domain3 = _lib.domain3(domain)
         self._halo4 = (ctypes.c_int64 * 4)(*self._halo)
         # every check of the library, nothing enqueued; also: how many kernels a call makes
         self.launches = _native(self._fields, self._n, self._domain3, self._halo4, self._modes, self._sides | _lib.HALO_DRY_RUN,
                                 self._value, self._itemsize, None)
-        # (last: none of the checks above needs a device)
-        for a in arrays:
-            if not a.tensor.is_cuda:
-                raise TypeError("fill_halo works on device fields; a host array was passed")
-        # what must stay alive is what the CALLER holds: for a torch tensor or another exporter `as_device_array` made a wrapper
-        # that dies with this constructor, so the weak reference goes to the object that was passed
-        self._refs, self._held = [], []
-        for f in fields:
-            try:
-                self._refs.append(weakref.ref(f))
-            except TypeError:
-                self._held.append(f)
-        import torch
-
-        self._current_stream = torch.cuda.current_stream
-        self._lib = _lib.load()
+        self._bind("fill_halo", arrays, fields)
 
     def __call__(self) -> None:
-        if any(r() is None for r in self._refs):
-            raise RuntimeError("HaloFill: an array this call was bound to no longer exists; build a new HaloFill")
+        self._check_alive()
         rc = self._lib.gt4mi_halo_fill(self._fields, self._n, self._domain3, self._halo4, self._modes[0], self._modes[1],
                                        self._sides, self._value, self._itemsize, self._current_stream().cuda_stream, None)
         if rc != _lib.OK:

@@ -37,6 +37,7 @@
 #pragma once
 
 #include "common.hip.h"
+#include "field_args.hip.h"
 #include "halo.hip.h"
 
 namespace gt4mi {
@@ -173,43 +174,7 @@ field_copy_kernel(const CopyArgs a) {
         if (first + (unsigned)u * 256u < total) dst[where[u]] = field_copy_item<D, S>(w[u]);
 }
 
-struct CopySide {
-    const char* what;  // "dst" / "src"
-    const gt4mi_field* f;
-    int elem;
-};
-
-// the byte range the box of a field touches
-inline ByteSpan field_copy_span(const gt4mi_field& f, const int64_t extent[3], int elem_size) {
-    int64_t lo = 0, hi = 0;
-    for (int ax = 0; ax < 3; ++ax) {
-        const int64_t x = f.origin[ax] * f.stride[ax], y = (f.origin[ax] + extent[ax] - 1) * f.stride[ax];
-        lo += x < y ? x : y;
-        hi += x < y ? y : x;
-    }
-    const uintptr_t base = reinterpret_cast<uintptr_t>(f.data);
-    return ByteSpan{base + (uintptr_t)lo, base + (uintptr_t)(hi + elem_size)};
-}
-
-inline int field_copy_check_side(const char* what, int n, const gt4mi_field& f, const int64_t extent[3], int elem_size, bool is_dst) {
-    if (f.data == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_copy: %s %d is null", what, n);
-    if (reinterpret_cast<uintptr_t>(f.data) % (uintptr_t)elem_size != 0)
-        return fail(GT4MI_ERR_UNSUPPORTED, "field_copy: %s %d is not aligned to its item size", what, n);
-    for (int ax = 0; ax < 3; ++ax) {
-        if (f.stride[ax] % elem_size != 0)
-            return fail(GT4MI_ERR_UNSUPPORTED, "field_copy: %s %d: byte stride %lld along axis %d is not a multiple of the item size",
-                        what, n, (long long)f.stride[ax], ax);
-        if (f.origin[ax] < 0)
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "field_copy: %s %d: negative origin %lld along axis %d", what, n,
-                        (long long)f.origin[ax], ax);
-        if (f.origin[ax] + extent[ax] > f.shape[ax])
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "field_copy: %s %d: origin %lld + extent %lld along axis %d is outside the array (shape %lld)",
-                        what, n, (long long)f.origin[ax], (long long)extent[ax], ax, (long long)f.shape[ax]);
-        if (is_dst && f.stride[ax] == 0 && extent[ax] > 1)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_copy: dst %d has stride 0 along axis %d (only a src may be broadcast)", n, ax);
-    }
-    return GT4MI_OK;
-}
+const BoxChecks FIELD_COPY_CHECKS = {"field_copy", "extent", "only a src may be broadcast", false, false};
 
 // the axis (of extent > 1) along which a side has unit item stride, -1 = none
 inline int field_copy_unit_axis(const gt4mi_field& f, const int64_t extent[3], int elem_size, int other = -1) {
@@ -222,16 +187,12 @@ inline int field_copy_unit_axis(const gt4mi_field& f, const int64_t extent[3], i
 // path of a pair and its descriptor
 inline int field_copy_plan(const gt4mi_field& dst, const gt4mi_field& src, const int64_t extent[3], int dsize, int ssize, CopyPair* out) {
     CopyPair p{};
-    p.dst = static_cast<char*>(dst.data);
-    p.src = static_cast<const char*>(src.data);
+    p.dst = origin_ptr(dst), p.src = origin_ptr(src);
     int64_t d[3], s[3];
+    item_strides(dst, dsize, d), item_strides(src, ssize, s);
     bool broadcast = false;
-    for (int ax = 0; ax < 3; ++ax) {
-        p.dst += dst.origin[ax] * dst.stride[ax];
-        p.src += src.origin[ax] * src.stride[ax];
-        d[ax] = dst.stride[ax] / dsize, s[ax] = src.stride[ax] / ssize;
+    for (int ax = 0; ax < 3; ++ax)
         if (extent[ax] > 1 && s[ax] == 0) broadcast = true;
-    }
     const int ua_src = field_copy_unit_axis(src, extent, ssize);
     const int ua_dst = field_copy_unit_axis(dst, extent, dsize, ua_src);
     int order[3] = {0, 1, 2};
@@ -305,21 +266,12 @@ inline int field_copy(const gt4mi_field* dst, const gt4mi_field* src, int nfield
             return fail(GT4MI_ERR_UNSUPPORTED, "field_copy: GT4MI_COPY_CONVERT converts float32 <-> float64 only, not item size %d to %d", ssize, dsize);
     }
     for (int n = 0; n < nfields; ++n) {
-        if (int rc = field_copy_check_side("dst", n, dst[n], extent, dsize, true)) return rc;
-        if (int rc = field_copy_check_side("src", n, src[n], extent, ssize, false)) return rc;
+        if (int rc = check_box_field(FIELD_COPY_CHECKS, "dst", n, dst[n], extent, dsize, true)) return rc;
+        if (int rc = check_box_field(FIELD_COPY_CHECKS, "src", n, src[n], extent, ssize, false)) return rc;
     }
     const bool empty = extent[0] == 0 || extent[1] == 0 || extent[2] == 0;
     if (!empty) {
-        // no dst may meet any src or another dst: what makes one launch without ordering between its workgroups correct
-        for (int n = 0; n < nfields; ++n) {
-            const ByteSpan d = field_copy_span(dst[n], extent, dsize);
-            for (int m = 0; m < nfields; ++m) {
-                if (spans_overlap(d, field_copy_span(src[m], extent, ssize)))
-                    return fail(GT4MI_ERR_UNSUPPORTED, "field_copy: dst %d and src %d overlap in memory", n, m);
-                if (m > n && spans_overlap(d, field_copy_span(dst[m], extent, dsize)))
-                    return fail(GT4MI_ERR_UNSUPPORTED, "field_copy: dst %d and dst %d overlap in memory", n, m);
-            }
-        }
+        if (int rc = check_pairs_disjoint("field_copy", dst, src, nfields, extent, extent, dsize, ssize)) return rc;
         if ((int64_t)extent[0] * extent[1] > INT32_MAX || (int64_t)extent[0] * extent[1] * extent[2] > (int64_t)INT32_MAX - 2048)
             return fail(GT4MI_ERR_UNSUPPORTED, "field_copy: too many items for one launch");
     }

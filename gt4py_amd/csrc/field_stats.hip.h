@@ -42,6 +42,7 @@
 #include <cmath>
 
 #include "common.hip.h"
+#include "field_args.hip.h"
 
 namespace gt4mi {
 
@@ -278,43 +279,71 @@ field_stats_finish_kernel(const double* __restrict__ partials, double* __restric
     if (q == 0) result[(size_t)blockIdx.x * STATS_SLOTS + slot] = level[slot][0];
 }
 
-// bytes [lo, hi) that the domain of a field touches
-inline ByteSpan stats_span(const gt4mi_field& f, const int64_t domain[3], int elem_size) {
-    int64_t lo = 0, hi = 0;
-    for (int ax = 0; ax < 3; ++ax) {
-        const int64_t first = f.origin[ax] * f.stride[ax], last = (f.origin[ax] + domain[ax] - 1) * f.stride[ax];
-        lo += first < last ? first : last;
-        hi += first < last ? last : first;
-    }
-    const uintptr_t base = reinterpret_cast<uintptr_t>(f.data);
-    return ByteSpan{base + (uintptr_t)lo, base + (uintptr_t)hi + (uintptr_t)elem_size};
+// 16-byte lanes for a field: unit I stride, every lane's first item (a multiple of 4 columns from the origin) on a 16-byte boundary
+inline bool stats_vec_ok(const gt4mi_field& f, const char* origin, int elem_size) {
+    return f.stride[0] == elem_size && reinterpret_cast<uintptr_t>(origin) % 16 == 0 && f.stride[1] % 16 == 0 && f.stride[2] % 16 == 0;
 }
 
-inline int stats_check_field(const char* what, int n, const gt4mi_field& f, const int64_t domain[3], int elem_size, bool weight) {
-    if (reinterpret_cast<uintptr_t>(f.data) % (uintptr_t)elem_size != 0)
-        return fail(GT4MI_ERR_UNSUPPORTED, "field_stats: %s %d is not aligned to its item size", what, n);
-    for (int ax = 0; ax < 3; ++ax) {
-        if (f.stride[ax] % elem_size != 0)
-            return fail(GT4MI_ERR_UNSUPPORTED, "field_stats: %s %d: byte stride %lld along axis %d is not a multiple of the item size",
-                        what, n, (long long)f.stride[ax], ax);
-        if (f.stride[ax] == 0 && domain[ax] > 1) {
-            if (weight) continue;  // a broadcast axis: one item for every index, no shape to check
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: %s %d has stride 0 along axis %d (only a second field may be broadcast)",
-                        what, n, ax);
-        }
-        if (f.origin[ax] < 0)
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "field_stats: %s %d: negative origin %lld along axis %d", what, n,
-                        (long long)f.origin[ax], ax);
-        if (f.origin[ax] + domain[ax] > f.shape[ax])
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "field_stats: %s %d: origin %lld + domain %lld along axis %d is outside the array (shape %lld)",
-                        what, n, (long long)f.origin[ax], (long long)domain[ax], ax, (long long)f.shape[ax]);
+// the descriptor of one entry: field `f` and, unless null, the second field `o`
+inline void stats_fill_entry(StatsEntry& d, const gt4mi_field& f, const gt4mi_field* o, int elem_size) {
+    d = StatsEntry{};
+    d.a = origin_ptr(f);
+    d.ai = f.stride[0] / elem_size, d.aj = f.stride[1] / elem_size, d.ak = f.stride[2] / elem_size;
+    d.vec = stats_vec_ok(f, d.a, elem_size) ? 1 : 0;
+    if (o == nullptr) return;
+    d.b = origin_ptr(*o);
+    d.bi = o->stride[0] / elem_size, d.bj = o->stride[1] / elem_size, d.bk = o->stride[2] / elem_size;
+    d.vec |= stats_vec_ok(*o, d.b, elem_size) ? 2 : 0;
+}
+
+// the second field of entry n, null if there is none (others == NULL, or a descriptor with data == NULL)
+inline const gt4mi_field* stats_other(const gt4mi_field* others, int n) {
+    return others != nullptr && others[n].data != nullptr ? &others[n] : nullptr;
+}
+
+inline BoxChecks stats_checks(const char* entry) { return BoxChecks{entry, "domain", "only a second field may be broadcast", true, false}; }
+
+// the fields of a call: `field` n must exist, `other` n is checked where there is one and may be broadcast along any axis
+inline int stats_check_fields(const char* entry, const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3],
+                              int elem_size) {
+    const BoxChecks checks = stats_checks(entry);
+    for (int n = 0; n < nfields; ++n) {
+        if (int rc = check_box_field(checks, "field", n, fields[n], domain, elem_size, true)) return rc;
+        if (const gt4mi_field* o = stats_other(others, n))
+            if (int rc = check_box_field(checks, "other", n, *o, domain, elem_size, false, 7)) return rc;
     }
     return GT4MI_OK;
 }
 
-// 16-byte lanes for a field: unit I stride, every lane's first item (a multiple of 4 columns from the origin) on a 16-byte boundary
-inline bool stats_vec_ok(const gt4mi_field& f, const char* origin, int elem_size) {
-    return f.stride[0] == elem_size && reinterpret_cast<uintptr_t>(origin) % 16 == 0 && f.stride[1] % 16 == 0 && f.stride[2] % 16 == 0;
+// workspace (`needed` bytes) and result (`result_bytes`): there unless the call is a dry run, large enough, aligned to 8 bytes,
+// clear of every field and of each other.  (A dry run without buffers asks for the workspace size; buffers that are passed
+// are checked in either case.)
+inline int stats_check_buffers(const char* entry, const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3],
+                               int elem_size, const void* workspace, int64_t workspace_bytes, int64_t needed, const void* result,
+                               int64_t result_bytes, bool dry) {
+    if (!dry && (workspace == nullptr || result == nullptr))
+        return fail(GT4MI_ERR_INVALID_ARGUMENT, "%s: %s is null", entry, workspace == nullptr ? "workspace" : "result");
+    if (workspace != nullptr && workspace_bytes < needed)
+        return fail(GT4MI_ERR_INVALID_ARGUMENT, "%s: workspace of %lld bytes is too small, %lld are needed", entry, (long long)workspace_bytes,
+                    (long long)needed);
+    const ByteSpan spans[2] = {
+        ByteSpan{reinterpret_cast<uintptr_t>(workspace), reinterpret_cast<uintptr_t>(workspace) + (uintptr_t)needed},
+        ByteSpan{reinterpret_cast<uintptr_t>(result), reinterpret_cast<uintptr_t>(result) + (uintptr_t)result_bytes}};
+    const char* const names[2] = {"workspace", "result"};
+    for (int w = 0; w < 2; ++w) {
+        if (spans[w].lo == 0) continue;
+        if (spans[w].lo % 8 != 0) return fail(GT4MI_ERR_INVALID_ARGUMENT, "%s: %s is not aligned to 8 bytes", entry, names[w]);
+        for (int n = 0; n < nfields; ++n) {
+            if (spans_overlap(spans[w], box_span(fields[n], domain, elem_size)))
+                return fail(GT4MI_ERR_INVALID_ARGUMENT, "%s: %s overlaps field %d", entry, names[w], n);
+            if (const gt4mi_field* o = stats_other(others, n))
+                if (spans_overlap(spans[w], box_span(*o, domain, elem_size)))
+                    return fail(GT4MI_ERR_INVALID_ARGUMENT, "%s: %s overlaps other %d", entry, names[w], n);
+        }
+    }
+    if (workspace != nullptr && result != nullptr && spans_overlap(spans[0], spans[1]))
+        return fail(GT4MI_ERR_INVALID_ARGUMENT, "%s: workspace overlaps result", entry);
+    return GT4MI_OK;
 }
 
 // every check, then (unless `flags` carries GT4MI_STATS_DRY_RUN) the launches; *launches = kernels the call enqueues
@@ -334,37 +363,13 @@ inline int field_stats(const gt4mi_field* fields, const gt4mi_field* others, int
     const bool dry = (flags & GT4MI_STATS_DRY_RUN) != 0;
     if ((double)domain[0] * (double)domain[1] * (double)domain[2] > 1099511627776.0)  // 2^40: the lanes count in 32 bits
         return fail(GT4MI_ERR_UNSUPPORTED, "field_stats: more than 2^40 points in the domain");
-    for (int n = 0; n < nfields; ++n) {
-        if (fields[n].data == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: field %d is null", n);
-        if (int rc = stats_check_field("field", n, fields[n], domain, elem_size, false)) return rc;
-        if (others != nullptr && others[n].data != nullptr)
-            if (int rc = stats_check_field("other", n, others[n], domain, elem_size, true)) return rc;
-    }
+    if (int rc = stats_check_fields("field_stats", fields, others, nfields, domain, elem_size)) return rc;
     const StatsGeometry geo = stats_geometry(domain);
     const int64_t needed = (int64_t)nfields * geo.tiles * STATS_SLOTS * (int64_t)sizeof(double);
     if (workspace_needed) *workspace_needed = needed;
-    // (a dry run without buffers asks for the workspace size; buffers that are passed are checked in either case)
-    if (!dry && (workspace == nullptr || result == nullptr))
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: %s is null", workspace == nullptr ? "workspace" : "result");
-    if (workspace != nullptr && workspace_bytes < needed)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: workspace of %lld bytes is too small, %lld are needed",
-                    (long long)workspace_bytes, (long long)needed);
-    const ByteSpan spans[2] = {
-        ByteSpan{reinterpret_cast<uintptr_t>(workspace), reinterpret_cast<uintptr_t>(workspace) + (uintptr_t)needed},
-        ByteSpan{reinterpret_cast<uintptr_t>(result), reinterpret_cast<uintptr_t>(result) + (uintptr_t)nfields * STATS_SLOTS * sizeof(double)}};
-    const char* const names[2] = {"workspace", "result"};
-    for (int w = 0; w < 2; ++w) {
-        if (spans[w].lo == 0) continue;
-        if (spans[w].lo % 8 != 0) return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: %s is not aligned to 8 bytes", names[w]);
-        for (int n = 0; n < nfields; ++n) {
-            if (spans_overlap(spans[w], stats_span(fields[n], domain, elem_size)))
-                return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: %s overlaps field %d", names[w], n);
-            if (others != nullptr && others[n].data != nullptr && spans_overlap(spans[w], stats_span(others[n], domain, elem_size)))
-                return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: %s overlaps other %d", names[w], n);
-        }
-    }
-    if (workspace != nullptr && result != nullptr && spans_overlap(spans[0], spans[1]))
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "field_stats: workspace overlaps result");
+    if (int rc = stats_check_buffers("field_stats", fields, others, nfields, domain, elem_size, workspace, workspace_bytes, needed, result,
+                                     (int64_t)nfields * STATS_SLOTS * (int64_t)sizeof(double), dry))
+        return rc;
     const int count = (int)cdiv(nfields, STATS_MAX_ENTRIES) + 1;
     if (launches) *launches = count;
     if (dry) return GT4MI_OK;
@@ -373,20 +378,7 @@ inline int field_stats(const gt4mi_field* fields, const gt4mi_field* others, int
     a.rows = geo.rows, a.rows_per_wave = geo.rows_per_wave, a.tiles = geo.tiles;
     for (int first = 0; first < nfields; first += STATS_MAX_ENTRIES) {
         const int nf = nfields - first < STATS_MAX_ENTRIES ? nfields - first : STATS_MAX_ENTRIES;
-        for (int n = 0; n < nf; ++n) {
-            const gt4mi_field& f = fields[first + n];
-            StatsEntry& d = a.e[n];
-            d = StatsEntry{};
-            d.a = static_cast<const char*>(f.data) + f.origin[0] * f.stride[0] + f.origin[1] * f.stride[1] + f.origin[2] * f.stride[2];
-            d.ai = f.stride[0] / elem_size, d.aj = f.stride[1] / elem_size, d.ak = f.stride[2] / elem_size;
-            d.vec = stats_vec_ok(f, d.a, elem_size) ? 1 : 0;
-            if (others != nullptr && others[first + n].data != nullptr) {
-                const gt4mi_field& o = others[first + n];
-                d.b = static_cast<const char*>(o.data) + o.origin[0] * o.stride[0] + o.origin[1] * o.stride[1] + o.origin[2] * o.stride[2];
-                d.bi = o.stride[0] / elem_size, d.bj = o.stride[1] / elem_size, d.bk = o.stride[2] / elem_size;
-                d.vec |= stats_vec_ok(o, d.b, elem_size) ? 2 : 0;
-            }
-        }
+        for (int n = 0; n < nf; ++n) stats_fill_entry(a.e[n], fields[first + n], stats_other(others, first + n), elem_size);
         a.partials = static_cast<double*>(workspace) + (size_t)first * geo.tiles * STATS_SLOTS;
         const dim3 grid(geo.tiles, (unsigned)nf);
         if (elem_size == 8) hipLaunchKernelGGL((field_stats_kernel<double>), grid, dim3(64 * STATS_WAVES), 0, stream, a);

@@ -32,6 +32,7 @@
 #include <cstring>
 
 #include "common.hip.h"
+#include "field_args.hip.h"
 #include "halo.hip.h"
 
 namespace gt4mi {
@@ -254,7 +255,7 @@ inline int halo_fill(const gt4mi_field* fields, int nfields, const int64_t domai
         for (int n = 0; n < nf; ++n) {
             const gt4mi_field& f = fields[first + n];
             HaloFillField& d = a.f[n];
-            d.origin = static_cast<char*>(f.data) + f.origin[0] * f.stride[0] + f.origin[1] * f.stride[1] + f.origin[2] * f.stride[2];
+            d.origin = origin_ptr(f);
             d.si = f.stride[0] / elem_size, d.sj = f.stride[1] / elem_size, d.sk = f.stride[2] / elem_size;
             d.lead = -1;
             d.lanes = 0;

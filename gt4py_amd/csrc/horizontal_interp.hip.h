@@ -44,7 +44,7 @@
 #pragma once
 
 #include "common.hip.h"
-#include "field_copy.hip.h"
+#include "field_args.hip.h"
 
 namespace gt4mi {
 
@@ -196,48 +196,13 @@ horizontal_interp_kernel(const InterpArgs a) {
     }
 }
 
-// `grow`: the readable box of a src reaches grow[0 / 2] points below and grow[1 / 3] above the box along I / J (null: none);
-// `free_k`: a K stride of 0 broadcasts (a Field[IJ] of positions) and has no shape to check along K
-inline int interp_check_field(const char* what, int n, const gt4mi_field& f, const int64_t extent[3], const int64_t* grow, int elem_size,
-                              bool is_dst, bool free_k) {
-    if (f.data == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "horizontal_interp: %s %d is null", what, n);
-    if (reinterpret_cast<uintptr_t>(f.data) % (uintptr_t)elem_size != 0)
-        return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: %s %d is not aligned to its item size", what, n);
-    for (int ax = 0; ax < 3; ++ax) {
-        if (f.stride[ax] % elem_size != 0)
-            return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: %s %d: byte stride %lld along axis %d is not a multiple of the item size",
-                        what, n, (long long)f.stride[ax], ax);
-        if (is_dst && f.stride[ax] == 0 && extent[ax] > 1)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "horizontal_interp: dst %d has stride 0 along axis %d (only a src or a position field may be broadcast)",
-                        n, ax);
-        if (free_k && ax == 2 && f.stride[ax] == 0) continue;
-        const int64_t lo = grow != nullptr && ax < 2 ? grow[2 * ax] : 0, hi = grow != nullptr && ax < 2 ? grow[2 * ax + 1] : 0;
-        if (f.origin[ax] < 0)
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "horizontal_interp: %s %d: negative origin %lld along axis %d", what, n,
-                        (long long)f.origin[ax], ax);
-        if (f.origin[ax] < lo)
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "horizontal_interp: %s %d: origin %lld along axis %d leaves no room for a reach of %lld below the domain",
-                        what, n, (long long)f.origin[ax], ax, (long long)lo);
-        if (f.origin[ax] + extent[ax] + hi > f.shape[ax])
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "horizontal_interp: %s %d: origin %lld + extent %lld + reach %lld along axis %d is outside the array (shape %lld)",
-                        what, n, (long long)f.origin[ax], (long long)extent[ax], (long long)hi, ax, (long long)f.shape[ax]);
-    }
-    return GT4MI_OK;
-}
-
-// the byte range of a field's box, grown by the reach for a src
-inline ByteSpan interp_span(const gt4mi_field& f, const int64_t extent[3], const int64_t* grow, int elem_size) {
-    gt4mi_field g = f;
-    int64_t ext[3] = {extent[0], extent[1], extent[2]};
-    if (grow != nullptr)
-        for (int ax = 0; ax < 2; ++ax) g.origin[ax] -= grow[2 * ax], ext[ax] += grow[2 * ax] + grow[2 * ax + 1];
-    return field_copy_span(g, ext, elem_size);
-}
+const BoxChecks INTERP_CHECKS = {"horizontal_interp", "extent", "only a src or a position field may be broadcast", false, true};
+constexpr int INTERP_POS_FREE_AXES = 4;  // a Field[IJ] of positions: stride 0 along K, one item for every level, no shape to check
 
 inline InterpPos interp_pos(const gt4mi_field& f, int elem_size) {
     InterpPos q{};
-    q.p = static_cast<const char*>(f.data);
-    for (int ax = 0; ax < 3; ++ax) q.p += f.origin[ax] * f.stride[ax], q.s[ax] = f.stride[ax] / elem_size;
+    q.p = origin_ptr(f);
+    item_strides(f, elem_size, q.s);
     return q;
 }
 
@@ -287,26 +252,14 @@ inline int horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int
     if (pos_elem_size != 4 && pos_elem_size != 8)
         return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: position item size %d is not supported (float32 or float64)", pos_elem_size);
     for (int n = 0; n < nfields; ++n) {
-        if (int rc = interp_check_field("dst", n, dst[n], extent, nullptr, elem_size, true, false)) return rc;
-        if (int rc = interp_check_field("src", n, src[n], extent, reach, elem_size, false, false)) return rc;
+        if (int rc = check_box_field(INTERP_CHECKS, "dst", n, dst[n], extent, elem_size, true)) return rc;
+        if (int rc = check_box_field(INTERP_CHECKS, "src", n, src[n], extent, elem_size, false, 0, reach)) return rc;  // (the readable box)
     }
-    if (int rc = interp_check_field("pos_i", 0, *pos_i, extent, nullptr, pos_elem_size, false, true)) return rc;
-    if (int rc = interp_check_field("pos_j", 0, *pos_j, extent, nullptr, pos_elem_size, false, true)) return rc;
+    if (int rc = check_box_field(INTERP_CHECKS, "pos_i", 0, *pos_i, extent, pos_elem_size, false, INTERP_POS_FREE_AXES)) return rc;
+    if (int rc = check_box_field(INTERP_CHECKS, "pos_j", 0, *pos_j, extent, pos_elem_size, false, INTERP_POS_FREE_AXES)) return rc;
     if (extent[0] == 0 || extent[1] == 0 || extent[2] == 0) return GT4MI_OK;
-    // no dst may meet any src's readable box, a position field or another dst: what makes one launch without ordering between its
-    // threads correct
-    const ByteSpan bi = interp_span(*pos_i, extent, nullptr, pos_elem_size), bj = interp_span(*pos_j, extent, nullptr, pos_elem_size);
-    for (int n = 0; n < nfields; ++n) {
-        const ByteSpan d = interp_span(dst[n], extent, nullptr, elem_size);
-        if (spans_overlap(d, bi)) return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: dst %d and pos_i overlap in memory", n);
-        if (spans_overlap(d, bj)) return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: dst %d and pos_j overlap in memory", n);
-        for (int m = 0; m < nfields; ++m) {
-            if (spans_overlap(d, interp_span(src[m], extent, reach, elem_size)))
-                return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: dst %d and src %d overlap in memory", n, m);
-            if (m > n && spans_overlap(d, interp_span(dst[m], extent, nullptr, elem_size)))
-                return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: dst %d and dst %d overlap in memory", n, m);
-        }
-    }
+    const NamedSpan pos[2] = {{"pos_i", box_span(*pos_i, extent, pos_elem_size)}, {"pos_j", box_span(*pos_j, extent, pos_elem_size)}};
+    if (int rc = check_pairs_disjoint("horizontal_interp", dst, src, nfields, extent, extent, elem_size, elem_size, reach, pos, 2)) return rc;
     const int64_t tiles_i = cdiv(extent[0], INTERP_TILE_I), tiles_j = cdiv(extent[1], INTERP_TILE_J);
     const int64_t blocks = tiles_i * tiles_j * cdiv(extent[2], INTERP_CHUNK_K);
     if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: too many points for one launch");
@@ -324,12 +277,8 @@ inline int horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int
             InterpEntry& e = a.e[n];
             e = InterpEntry{};
             if (n >= a.nf) continue;
-            const gt4mi_field &fd = dst[first + n], &fs = src[first + n];
-            e.dst = static_cast<char*>(fd.data), e.src = static_cast<const char*>(fs.data);
-            for (int ax = 0; ax < 3; ++ax) {
-                e.dst += fd.origin[ax] * fd.stride[ax], e.src += fs.origin[ax] * fs.stride[ax];
-                e.d[ax] = fd.stride[ax] / elem_size, e.s[ax] = fs.stride[ax] / elem_size;
-            }
+            e.dst = origin_ptr(dst[first + n]), e.src = origin_ptr(src[first + n]);
+            item_strides(dst[first + n], elem_size, e.d), item_strides(src[first + n], elem_size, e.s);
         }
         if (elem_size == 8 && pos_elem_size == 8) interp_launch_method<double, double>(a, blocks, method, stream);
         else if (elem_size == 8) interp_launch_method<double, float>(a, blocks, method, stream);

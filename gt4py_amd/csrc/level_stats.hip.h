@@ -121,28 +121,6 @@ level_stats_finish_kernel(const double* __restrict__ partials, double* __restric
     if (slot == STATS_SUM) r[(size_t)GT4MI_LEVEL_STATS_MEAN * nk] = v[0] / count;
 }
 
-inline int level_stats_check_field(const char* what, int n, const gt4mi_field& f, const int64_t domain[3], int elem_size, bool weight) {
-    if (reinterpret_cast<uintptr_t>(f.data) % (uintptr_t)elem_size != 0)
-        return fail(GT4MI_ERR_UNSUPPORTED, "level_stats: %s %d is not aligned to its item size", what, n);
-    for (int ax = 0; ax < 3; ++ax) {
-        if (f.stride[ax] % elem_size != 0)
-            return fail(GT4MI_ERR_UNSUPPORTED, "level_stats: %s %d: byte stride %lld along axis %d is not a multiple of the item size",
-                        what, n, (long long)f.stride[ax], ax);
-        if (f.stride[ax] == 0 && domain[ax] > 1) {
-            if (weight) continue;  // a broadcast axis: one item for every index, no shape to check
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: %s %d has stride 0 along axis %d (only a second field may be broadcast)",
-                        what, n, ax);
-        }
-        if (f.origin[ax] < 0)
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "level_stats: %s %d: negative origin %lld along axis %d", what, n,
-                        (long long)f.origin[ax], ax);
-        if (f.origin[ax] + domain[ax] > f.shape[ax])
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "level_stats: %s %d: origin %lld + domain %lld along axis %d is outside the array (shape %lld)",
-                        what, n, (long long)f.origin[ax], (long long)domain[ax], ax, (long long)f.shape[ax]);
-    }
-    return GT4MI_OK;
-}
-
 // every check, then (unless `flags` carries GT4MI_STATS_DRY_RUN) the launches; *launches = kernels the call enqueues
 inline int level_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int elem_size,
                        void* workspace, int64_t workspace_bytes, double* result, int flags, hipStream_t stream,
@@ -163,40 +141,16 @@ inline int level_stats(const gt4mi_field* fields, const gt4mi_field* others, int
     const LevelStatsGeometry geo = level_stats_geometry(domain);
     if (domain[2] * (int64_t)geo.tiles > LEVEL_STATS_MAX_WORKGROUPS)
         return fail(GT4MI_ERR_UNSUPPORTED, "level_stats: %lld levels of %u tiles are more than 2^24 workgroups", (long long)domain[2], geo.tiles);
-    for (int n = 0; n < nfields; ++n) {
-        if (fields[n].data == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: field %d is null", n);
-        if (int rc = level_stats_check_field("field", n, fields[n], domain, elem_size, false)) return rc;
-        if (others != nullptr && others[n].data != nullptr)
-            if (int rc = level_stats_check_field("other", n, others[n], domain, elem_size, true)) return rc;
-    }
+    if (int rc = stats_check_fields("level_stats", fields, others, nfields, domain, elem_size)) return rc;
     const int64_t levels = (int64_t)nfields * domain[2];
     if (levels > ((int64_t)1 << 28))  // the finish kernel's grid: 8 threads per level, below 2^32
         return fail(GT4MI_ERR_UNSUPPORTED, "level_stats: %d fields of %lld levels are more than 2^28 profiles", nfields, (long long)domain[2]);
     const int64_t needed = levels * geo.tiles * STATS_SLOTS * (int64_t)sizeof(double);
     const int64_t result_bytes = levels * LEVEL_STATS_ROWS * (int64_t)sizeof(double);
     if (workspace_needed) *workspace_needed = needed;
-    // (a dry run without buffers asks for the workspace size; buffers that are passed are checked in either case)
-    if (!dry && (workspace == nullptr || result == nullptr))
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: %s is null", workspace == nullptr ? "workspace" : "result");
-    if (workspace != nullptr && workspace_bytes < needed)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: workspace of %lld bytes is too small, %lld are needed",
-                    (long long)workspace_bytes, (long long)needed);
-    const ByteSpan spans[2] = {
-        ByteSpan{reinterpret_cast<uintptr_t>(workspace), reinterpret_cast<uintptr_t>(workspace) + (uintptr_t)needed},
-        ByteSpan{reinterpret_cast<uintptr_t>(result), reinterpret_cast<uintptr_t>(result) + (uintptr_t)result_bytes}};
-    const char* const names[2] = {"workspace", "result"};
-    for (int w = 0; w < 2; ++w) {
-        if (spans[w].lo == 0) continue;
-        if (spans[w].lo % 8 != 0) return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: %s is not aligned to 8 bytes", names[w]);
-        for (int n = 0; n < nfields; ++n) {
-            if (spans_overlap(spans[w], stats_span(fields[n], domain, elem_size)))
-                return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: %s overlaps field %d", names[w], n);
-            if (others != nullptr && others[n].data != nullptr && spans_overlap(spans[w], stats_span(others[n], domain, elem_size)))
-                return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: %s overlaps other %d", names[w], n);
-        }
-    }
-    if (workspace != nullptr && result != nullptr && spans_overlap(spans[0], spans[1]))
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "level_stats: workspace overlaps result");
+    if (int rc = stats_check_buffers("level_stats", fields, others, nfields, domain, elem_size, workspace, workspace_bytes, needed, result,
+                                     result_bytes, dry))
+        return rc;
     const int count = (int)cdiv(nfields, STATS_MAX_ENTRIES) + 1;
     if (launches) *launches = count;
     if (dry) return GT4MI_OK;
@@ -205,20 +159,7 @@ inline int level_stats(const gt4mi_field* fields, const gt4mi_field* others, int
     a.rows_per_wave = geo.rows_per_wave, a.tiles = geo.tiles;
     for (int first = 0; first < nfields; first += STATS_MAX_ENTRIES) {
         const int nf = nfields - first < STATS_MAX_ENTRIES ? nfields - first : STATS_MAX_ENTRIES;
-        for (int n = 0; n < nf; ++n) {
-            const gt4mi_field& f = fields[first + n];
-            StatsEntry& d = a.e[n];
-            d = StatsEntry{};
-            d.a = static_cast<const char*>(f.data) + f.origin[0] * f.stride[0] + f.origin[1] * f.stride[1] + f.origin[2] * f.stride[2];
-            d.ai = f.stride[0] / elem_size, d.aj = f.stride[1] / elem_size, d.ak = f.stride[2] / elem_size;
-            d.vec = stats_vec_ok(f, d.a, elem_size) ? 1 : 0;
-            if (others != nullptr && others[first + n].data != nullptr) {
-                const gt4mi_field& o = others[first + n];
-                d.b = static_cast<const char*>(o.data) + o.origin[0] * o.stride[0] + o.origin[1] * o.stride[1] + o.origin[2] * o.stride[2];
-                d.bi = o.stride[0] / elem_size, d.bj = o.stride[1] / elem_size, d.bk = o.stride[2] / elem_size;
-                d.vec |= stats_vec_ok(o, d.b, elem_size) ? 2 : 0;
-            }
-        }
+        for (int n = 0; n < nf; ++n) stats_fill_entry(a.e[n], fields[first + n], stats_other(others, first + n), elem_size);
         a.partials = static_cast<double*>(workspace) + (size_t)first * a.nk * geo.tiles * STATS_SLOTS;
         const dim3 grid((unsigned)(domain[2] * geo.tiles), (unsigned)nf);
         if (elem_size == 8) hipLaunchKernelGGL((level_stats_kernel<double>), grid, dim3(64 * STATS_WAVES), 0, stream, a);

@@ -35,7 +35,7 @@
 #pragma once
 
 #include "common.hip.h"
-#include "field_copy.hip.h"
+#include "field_args.hip.h"
 
 namespace gt4mi {
 
@@ -152,33 +152,13 @@ vertical_remap_kernel(const RemapArgs a) {
     }
 }
 
-inline int remap_check_field(const char* what, int n, const gt4mi_field& f, const int64_t extent[3], int elem_size, bool is_dst,
-                             bool is_edges) {
-    if (f.data == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: %s %d is null", what, n);
-    if (reinterpret_cast<uintptr_t>(f.data) % (uintptr_t)elem_size != 0)
-        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: %s %d is not aligned to its item size", what, n);
-    for (int ax = 0; ax < 3; ++ax) {
-        if (f.stride[ax] % elem_size != 0)
-            return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: %s %d: byte stride %lld along axis %d is not a multiple of the item size",
-                        what, n, (long long)f.stride[ax], ax);
-        if (is_dst && f.stride[ax] == 0 && extent[ax] > 1)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: dst %d has stride 0 along axis %d (only a src or an edge field may be broadcast)",
-                        n, ax);
-        if (is_edges && ax < 2 && f.stride[ax] == 0) continue;  // a Field[K] of edges: one item for every i / j, no shape to check
-        if (f.origin[ax] < 0)
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "vertical_remap: %s %d: negative origin %lld along axis %d", what, n,
-                        (long long)f.origin[ax], ax);
-        if (f.origin[ax] + extent[ax] > f.shape[ax])
-            return fail(GT4MI_ERR_OUT_OF_BOUNDS, "vertical_remap: %s %d: origin %lld + extent %lld along axis %d is outside the array (shape %lld)",
-                        what, n, (long long)f.origin[ax], (long long)extent[ax], ax, (long long)f.shape[ax]);
-    }
-    return GT4MI_OK;
-}
+const BoxChecks REMAP_CHECKS = {"vertical_remap", "extent", "only a src or an edge field may be broadcast", false, false};
+constexpr int REMAP_EDGE_FREE_AXES = 3;  // a Field[K] of edges: stride 0 along I / J, one item for every i / j, no shape to check
 
 inline RemapEdges remap_edges(const gt4mi_field& f, int elem_size) {
     RemapEdges e{};
-    e.p = static_cast<const char*>(f.data);
-    for (int ax = 0; ax < 3; ++ax) e.p += f.origin[ax] * f.stride[ax], e.s[ax] = f.stride[ax] / elem_size;
+    e.p = origin_ptr(f);
+    item_strides(f, elem_size, e.s);
     return e;
 }
 
@@ -222,25 +202,14 @@ inline int vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nf
     const int64_t d_ext[3] = {extent_ij[0], extent_ij[1], nd}, s_ext[3] = {extent_ij[0], extent_ij[1], ns};
     const int64_t de_ext[3] = {extent_ij[0], extent_ij[1], nd + 1}, se_ext[3] = {extent_ij[0], extent_ij[1], ns + 1};
     for (int n = 0; n < nfields; ++n) {
-        if (int rc = remap_check_field("dst", n, dst[n], d_ext, elem_size, true, false)) return rc;
-        if (int rc = remap_check_field("src", n, src[n], s_ext, elem_size, false, false)) return rc;
+        if (int rc = check_box_field(REMAP_CHECKS, "dst", n, dst[n], d_ext, elem_size, true)) return rc;
+        if (int rc = check_box_field(REMAP_CHECKS, "src", n, src[n], s_ext, elem_size, false)) return rc;
     }
-    if (int rc = remap_check_field("src_edges", 0, *src_edges, se_ext, edge_elem_size, false, true)) return rc;
-    if (int rc = remap_check_field("dst_edges", 0, *dst_edges, de_ext, edge_elem_size, false, true)) return rc;
+    if (int rc = check_box_field(REMAP_CHECKS, "src_edges", 0, *src_edges, se_ext, edge_elem_size, false, REMAP_EDGE_FREE_AXES)) return rc;
+    if (int rc = check_box_field(REMAP_CHECKS, "dst_edges", 0, *dst_edges, de_ext, edge_elem_size, false, REMAP_EDGE_FREE_AXES)) return rc;
     if (extent_ij[0] == 0 || extent_ij[1] == 0) return GT4MI_OK;
-    // no dst may meet any src, an edge field or another dst: what makes one launch without ordering between its threads correct
-    const ByteSpan se = field_copy_span(*src_edges, se_ext, edge_elem_size), de = field_copy_span(*dst_edges, de_ext, edge_elem_size);
-    for (int n = 0; n < nfields; ++n) {
-        const ByteSpan d = field_copy_span(dst[n], d_ext, elem_size);
-        if (spans_overlap(d, se)) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and src_edges overlap in memory", n);
-        if (spans_overlap(d, de)) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and dst_edges overlap in memory", n);
-        for (int m = 0; m < nfields; ++m) {
-            if (spans_overlap(d, field_copy_span(src[m], s_ext, elem_size)))
-                return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and src %d overlap in memory", n, m);
-            if (m > n && spans_overlap(d, field_copy_span(dst[m], d_ext, elem_size)))
-                return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: dst %d and dst %d overlap in memory", n, m);
-        }
-    }
+    const NamedSpan edges[2] = {{"src_edges", box_span(*src_edges, se_ext, edge_elem_size)}, {"dst_edges", box_span(*dst_edges, de_ext, edge_elem_size)}};
+    if (int rc = check_pairs_disjoint("vertical_remap", dst, src, nfields, d_ext, s_ext, elem_size, elem_size, nullptr, edges, 2)) return rc;
     const int64_t tiles_i = cdiv(extent_ij[0], REMAP_TILE_I), blocks = tiles_i * cdiv(extent_ij[1], REMAP_TILE_J);
     if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: too many columns for one launch");
     if (launches) *launches = (int)cdiv(nfields, REMAP_MAX_FIELDS);
@@ -255,12 +224,8 @@ inline int vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nf
             RemapEntry& e = a.e[n];
             e = RemapEntry{};
             if (n >= a.nf) continue;
-            const gt4mi_field &fd = dst[first + n], &fs = src[first + n];
-            e.dst = static_cast<char*>(fd.data), e.src = static_cast<const char*>(fs.data);
-            for (int ax = 0; ax < 3; ++ax) {
-                e.dst += fd.origin[ax] * fd.stride[ax], e.src += fs.origin[ax] * fs.stride[ax];
-                e.d[ax] = fd.stride[ax] / elem_size, e.s[ax] = fs.stride[ax] / elem_size;
-            }
+            e.dst = origin_ptr(dst[first + n]), e.src = origin_ptr(src[first + n]);
+            item_strides(dst[first + n], elem_size, e.d), item_strides(src[first + n], elem_size, e.s);
         }
         if (elem_size == 8 && edge_elem_size == 8) remap_launch_method<double, double>(a, blocks, method, stream);
         else if (elem_size == 8) remap_launch_method<double, float>(a, blocks, method, stream);

@@ -34,13 +34,12 @@ from __future__ import annotations
 
 import ctypes
 import math
-import weakref
 from typing import Any, List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
 from . import _lib
-from .boundary import _halo4
+from ._bound import FLOATS, Bound, _box_of, _halo4, _shape3, raise_refusal
 from .storage.device_array import DeviceArray, as_device_array
 
 
@@ -131,30 +130,26 @@ def _native(fields, others, n: int, domain, itemsize: int, workspace, workspace_
     rc = getattr(_lib.load(), entry)(fields, others, n, domain, itemsize, workspace, workspace_bytes, result, flags, stream,
                                      ctypes.byref(needed), ctypes.byref(launches))
     if rc != _lib.OK:
-        message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
-        if rc == _lib.ERR_HIP:
-            raise _lib.NativeError(entry, rc, message)
-        raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+        raise_refusal(entry, rc)
     return needed.value, launches.value
 
 
-class FieldStats:
-    """The frozen form of :func:`field_stats`: arguments are checked (through the library's dry run), the descriptors, the
-    workspace and the result buffer built ONCE; ``__call__()`` makes only the ctypes call, on the stream that is current THEN,
-    and does not synchronise; :meth:`get` synchronises that stream and returns one :class:`Stats` per entry.
+class _StatsCall(Bound):
+    """What :class:`FieldStats` and :class:`LevelStats` share: everything but the entry, the public function's name in the
+    messages and the shape of a result block."""
 
-    ``result`` is a float64 :class:`DeviceArray` of shape ``(n, 8)`` (slots in the order of :class:`Stats`): a later kernel, or
-    a captured graph, can read it on the device.  Every call overwrites it.
+    _who = _entry = ""
 
-    The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it refuses to run once one of
-    them has died.  (An exporter that cannot be weakly referenced is held instead, so its memory stays valid.)"""
+    def _result_block(self) -> tuple:
+        raise NotImplementedError
 
     def __init__(self, fields: Sequence[Any], *, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
                  domain: Optional[Sequence[int]] = None, halo=0):
+        who = self._who
         fields = list(fields)
         arrays = [as_device_array(f) for f in fields]
         if not arrays:
-            raise ValueError("field_stats needs at least one field")
+            raise ValueError(f"{who} needs at least one field")
         if others is None:
             others = [None] * len(fields)
         others = list(others)
@@ -162,39 +157,23 @@ class FieldStats:
             raise ValueError(f"others must have one entry (or None) per field: {len(others)} for {len(fields)} fields")
         other_arrays = [None if o is None else as_device_array(o) for o in others]
         first = arrays[0]
-        for a in arrays + [o for o in other_arrays if o is not None]:
-            if a.dtype not in (np.dtype("float32"), np.dtype("float64")):
-                raise TypeError(f"field_stats takes float32 or float64 fields, not {a.dtype}")
+        every = arrays + [o for o in other_arrays if o is not None]
+        for a in every:
+            if a.dtype not in FLOATS:
+                raise TypeError(f"{who} takes float32 or float64 fields, not {a.dtype}")
             if a.dtype != first.dtype:
                 raise TypeError(f"the fields of one call share a dtype: {first.dtype} and {a.dtype} differ")
             if a.ndim not in (2, 3):
-                raise ValueError(f"field_stats takes IJ or IJK fields, not a field of {a.ndim} dimension(s)")
-        h = _halo4(halo)
-        if origin is None:
-            origin = (h[0], h[2], 0)
-        origin = tuple(int(o) for o in origin)
-        origin = origin + (0,) * (3 - len(origin))
-        if len(origin) != 3:
-            raise ValueError(f"origin must have at most three entries, not {origin}")
-        shape3 = tuple(first.shape) + (1,) * (3 - first.ndim)
-        if domain is None:
-            domain = (shape3[0] - origin[0] - h[1], shape3[1] - origin[1] - h[3], shape3[2] - origin[2])
-            if min(domain) < 1:
-                raise ValueError(f"halo {h} and origin {origin} leave no domain in a field of shape {first.shape}")
-        domain = tuple(int(d) for d in domain)
-        domain = domain + (1,) * (3 - len(domain))
-        if len(domain) != 3:
-            raise ValueError(f"domain must have at most three entries, not {domain}")
-        self.origin, self.domain = origin, domain
+                raise ValueError(f"{who} takes IJ or IJK fields, not a field of {a.ndim} dimension(s)")
+        self.origin, self.domain = origin, domain = _box_of(first, _halo4(halo), origin, domain, 1)
         self._itemsize = first.itemsize
         self._n = len(arrays)
 
         def describe(a, weight):
-            shape = tuple(a.shape) + (1,) * (3 - a.ndim)
             strides = tuple(a.strides) + (0,) * (3 - a.ndim)
             # a broadcast axis of a weight (stride 0) has no origin of its own
             org = tuple(0 if weight and s == 0 else o for o, s in zip(origin, strides))
-            return _lib.Field.make(a.ptr, shape, strides, org)
+            return _lib.Field.make(a.ptr, _shape3(a), strides, org)
 
         self._fields = (_lib.Field * self._n)()
         self._others = (_lib.Field * self._n)()  # (data == NULL: no second field)
@@ -205,33 +184,37 @@ class FieldStats:
         self._domain3 = _lib.domain3(domain)
         # every check of the library, nothing enqueued; also: the workspace the call needs and how many kernels it makes
         needed, self.launches = _native(self._fields, self._others, self._n, self._domain3, self._itemsize, None, 0, None,
-                                        _lib.STATS_DRY_RUN, None)
-        # (last: none of the checks above needs a device)
-        for a in arrays + [o for o in other_arrays if o is not None]:
-            if not a.tensor.is_cuda:
-                raise TypeError("field_stats works on device fields; a host array was passed")
+                                        _lib.STATS_DRY_RUN, None, self._entry)
+        self._bind(who, every, fields + [o for o in others if o is not None])
         import torch
 
         self._workspace = torch.empty(needed // 8, dtype=torch.float64, device=first.tensor.device)
-        self.result = DeviceArray(torch.zeros((self._n, _lib.STATS_SLOTS), dtype=torch.float64, device=first.tensor.device))
+        self.result = DeviceArray(torch.zeros((self._n,) + self._result_block(), dtype=torch.float64, device=first.tensor.device))
         self._workspace_bytes = needed
         # the buffers against the fields (overlap, alignment): the dry run once more, now with them
         _native(self._fields, self._others, self._n, self._domain3, self._itemsize, self._workspace.data_ptr(), needed,
-                self.result.ptr, _lib.STATS_DRY_RUN, None)
-        # what must stay alive is what the CALLER holds (see HaloFill)
-        self._refs, self._held = [], []
-        for f in fields + [o for o in others if o is not None]:
-            try:
-                self._refs.append(weakref.ref(f))
-            except TypeError:
-                self._held.append(f)
-        self._current_stream = torch.cuda.current_stream
+                self.result.ptr, _lib.STATS_DRY_RUN, None, self._entry)
         self._stream = None
-        self._lib = _lib.load()
+
+
+class FieldStats(_StatsCall):
+    """The frozen form of :func:`field_stats`: arguments are checked (through the library's dry run), the descriptors, the
+    workspace and the result buffer built ONCE; ``__call__()`` makes only the ctypes call, on the stream that is current THEN,
+    and does not synchronise; :meth:`get` synchronises that stream and returns one :class:`Stats` per entry.
+
+    ``result`` is a float64 :class:`DeviceArray` of shape ``(n, 8)`` (slots in the order of :class:`Stats`): a later kernel, or
+    a captured graph, can read it on the device.  Every call overwrites it.
+
+    The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it refuses to run once one of
+    them has died.  (An exporter that cannot be weakly referenced is held instead, so its memory stays valid.)"""
+
+    _who, _entry = "field_stats", "gt4mi_field_stats"
+
+    def _result_block(self) -> tuple:
+        return (_lib.STATS_SLOTS,)
 
     def __call__(self) -> None:
-        if any(r() is None for r in self._refs):
-            raise RuntimeError("FieldStats: an array this call was bound to no longer exists; build a new FieldStats")
+        self._check_alive()
         self._stream = self._current_stream()
         rc = self._lib.gt4mi_field_stats(self._fields, self._others, self._n, self._domain3, self._itemsize,
                                          self._workspace.data_ptr(), self._workspace_bytes, self.result.ptr, 0,
@@ -373,7 +356,7 @@ def merge_profiles(parts: Sequence[Profile]) -> Profile:
     return Profile(*(np.array([getattr(s, name) for s in levels]) for name in Stats._fields))
 
 
-class LevelStats:
+class LevelStats(_StatsCall):
     """The frozen form of :func:`level_stats`, with the arguments and defaults of :class:`FieldStats`; ``origin[2]`` /
     ``domain[2]`` select the levels, profile index 0 is level ``origin[2]``, and IJ fields give ``nk = 1``.  Arguments are
     checked (through the library's dry run), the descriptors, the workspace and the result buffer built ONCE; ``__call__()``
@@ -387,95 +370,17 @@ class LevelStats:
     The object holds raw pointers and weak references to the CALLER's objects, as :class:`FieldStats` does: it refuses to run
     once one of them has died."""
 
-    def __init__(self, fields: Sequence[Any], *, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
-                 domain: Optional[Sequence[int]] = None, halo=0):
-        fields = list(fields)
-        arrays = [as_device_array(f) for f in fields]
-        if not arrays:
-            raise ValueError("level_stats needs at least one field")
-        if others is None:
-            others = [None] * len(fields)
-        others = list(others)
-        if len(others) != len(fields):
-            raise ValueError(f"others must have one entry (or None) per field: {len(others)} for {len(fields)} fields")
-        other_arrays = [None if o is None else as_device_array(o) for o in others]
-        first = arrays[0]
-        every = arrays + [o for o in other_arrays if o is not None]
-        for a in every:
-            if a.dtype not in (np.dtype("float32"), np.dtype("float64")):
-                raise TypeError(f"level_stats takes float32 or float64 fields, not {a.dtype}")
-            if a.dtype != first.dtype:
-                raise TypeError(f"the fields of one call share a dtype: {first.dtype} and {a.dtype} differ")
-            if a.ndim not in (2, 3):
-                raise ValueError(f"level_stats takes IJ or IJK fields, not a field of {a.ndim} dimension(s)")
-        h = _halo4(halo)
-        if origin is None:
-            origin = (h[0], h[2], 0)
-        origin = tuple(int(o) for o in origin)
-        origin = origin + (0,) * (3 - len(origin))
-        if len(origin) != 3:
-            raise ValueError(f"origin must have at most three entries, not {origin}")
-        shape3 = tuple(first.shape) + (1,) * (3 - first.ndim)
-        if domain is None:
-            domain = (shape3[0] - origin[0] - h[1], shape3[1] - origin[1] - h[3], shape3[2] - origin[2])
-            if min(domain) < 1:
-                raise ValueError(f"halo {h} and origin {origin} leave no domain in a field of shape {first.shape}")
-        domain = tuple(int(d) for d in domain)
-        domain = domain + (1,) * (3 - len(domain))
-        if len(domain) != 3:
-            raise ValueError(f"domain must have at most three entries, not {domain}")
-        self.origin, self.domain = origin, domain
-        self._itemsize = first.itemsize
-        self._n = len(arrays)
+    _who, _entry = "level_stats", "gt4mi_level_stats"
 
-        def describe(a, weight):
-            shape = tuple(a.shape) + (1,) * (3 - a.ndim)
-            strides = tuple(a.strides) + (0,) * (3 - a.ndim)
-            # a broadcast axis of a weight (stride 0) has no origin of its own
-            org = tuple(0 if weight and s == 0 else o for o, s in zip(origin, strides))
-            return _lib.Field.make(a.ptr, shape, strides, org)
-
-        self._fields = (_lib.Field * self._n)()
-        self._others = (_lib.Field * self._n)()  # (data == NULL: no second field)
-        for n, (a, o) in enumerate(zip(arrays, other_arrays)):
-            self._fields[n] = describe(a, False)
-            if o is not None:
-                self._others[n] = describe(o, True)
-        self._domain3 = _lib.domain3(domain)
-        # every check of the library, nothing enqueued; also: the workspace the call needs and how many kernels it makes
-        needed, self.launches = _native(self._fields, self._others, self._n, self._domain3, self._itemsize, None, 0, None,
-                                        _lib.STATS_DRY_RUN, None, "gt4mi_level_stats")
-        # (last: none of the checks above needs a device)
-        for a in every:
-            if not a.tensor.is_cuda:
-                raise TypeError("level_stats works on device fields; a host array was passed")
-        import torch
-
-        self._workspace = torch.empty(needed // 8, dtype=torch.float64, device=first.tensor.device)
-        self.result = DeviceArray(torch.zeros((self._n, _lib.LEVEL_STATS_ROWS, domain[2]), dtype=torch.float64,
-                                              device=first.tensor.device))
-        self._workspace_bytes = needed
-        # the buffers against the fields (overlap, alignment): the dry run once more, now with them
-        _native(self._fields, self._others, self._n, self._domain3, self._itemsize, self._workspace.data_ptr(), needed,
-                self.result.ptr, _lib.STATS_DRY_RUN, None, "gt4mi_level_stats")
-        # what must stay alive is what the CALLER holds (see HaloFill)
-        self._refs, self._held = [], []
-        for f in fields + [o for o in others if o is not None]:
-            try:
-                self._refs.append(weakref.ref(f))
-            except TypeError:
-                self._held.append(f)
-        self._current_stream = torch.cuda.current_stream
-        self._stream = None
-        self._lib = _lib.load()
+    def _result_block(self) -> tuple:
+        return (_lib.LEVEL_STATS_ROWS, self.domain[2])
 
     @property
     def nk(self) -> int:
         return self.domain[2]
 
     def __call__(self) -> None:
-        if any(r() is None for r in self._refs):
-            raise RuntimeError("LevelStats: an array this call was bound to no longer exists; build a new LevelStats")
+        self._check_alive()
         self._stream = self._current_stream()
         rc = self._lib.gt4mi_level_stats(self._fields, self._others, self._n, self._domain3, self._itemsize,
                                          self._workspace.data_ptr(), self._workspace_bytes, self.result.ptr, 0,

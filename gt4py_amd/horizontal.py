@@ -29,19 +29,14 @@ gives the same bits whatever the layout, the position in the call or the device.
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Optional, Sequence
 
-import numpy as np
-
 from . import _lib
-from .boundary import _halo4
-from .storage.device_array import DeviceArray, as_device_array
-from .transfer import _as_list, _triple
+from ._bound import Bound, _float_pairs, _origin3, raise_refusal
+from .storage.device_array import DeviceArray
 
 METHODS = {"nearest": _lib.INTERP_NEAREST, "linear": _lib.INTERP_LINEAR, "cubic": _lib.INTERP_CUBIC,
            "cubic_monotone": _lib.INTERP_CUBIC_MONOTONE}
-_FLOATS = (np.dtype("float32"), np.dtype("float64"))
 
 
 def _native(dst, src, n: int, pos_i, pos_j, extent, reach, size: int, pos_size: int, method: int, flags: int, stream: Optional[int]) -> int:
@@ -51,10 +46,7 @@ def _native(dst, src, n: int, pos_i, pos_j, extent, reach, size: int, pos_size: 
     rc = _lib.load().gt4mi_horizontal_interp(dst, src, n, ctypes.byref(pos_i), ctypes.byref(pos_j), extent, reach, size, pos_size, method,
                                              flags, stream, ctypes.byref(launches))
     if rc != _lib.OK:
-        message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
-        if rc == _lib.ERR_HIP:
-            raise _lib.NativeError("gt4mi_horizontal_interp", rc, message)
-        raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+        raise_refusal("gt4mi_horizontal_interp", rc)
     return launches.value
 
 
@@ -64,7 +56,7 @@ def _position_field(a: DeviceArray, origin) -> "_lib.Field":
     return _lib.Field.make(a.ptr, a.shape, a.strides, origin)
 
 
-class HorizontalInterp:
+class HorizontalInterp(Bound):
     """The frozen form of :func:`interpolate` (what ``FrozenStencil`` is for stencils): arguments are checked (through the
     library's dry run) and the native descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is
     current THEN.
@@ -75,39 +67,12 @@ class HorizontalInterp:
 
     def __init__(self, dst, src, *, pos_i, pos_j, method: str = "linear", relative: bool = False, halo=0,
                  origin: Optional[Sequence[int]] = None):
-        dsts, srcs = _as_list(dst), _as_list(src)
-        if not dsts or not srcs:
-            raise ValueError("interpolate needs at least one pair of fields")
-        if len(dsts) != len(srcs):
-            raise ValueError(f"interpolate pairs fields one to one: {len(dsts)} destination(s) and {len(srcs)} source(s) were passed")
-        if method not in METHODS:
-            raise ValueError(f"method must be one of {sorted(METHODS)}, not {method!r}")
+        dsts, srcs, d_arrays, s_arrays, p_arrays, self._halo = _float_pairs(
+            "interpolate", dst, src, halo, method, METHODS, shared=(pos_i, pos_j), names=("pos_i", "pos_j"), ndims=(2, 3), kind="Field[IJ]",
+            plural="position fields")
         self.method, self.relative = method, bool(relative)
-        d_arrays = [as_device_array(f) for f in dsts]
-        s_arrays = [as_device_array(f) for f in srcs]
-        p_arrays = [as_device_array(pos_i), as_device_array(pos_j)]
-        self._halo = _halo4(halo)
-        if min(self._halo) < 0:
-            raise ValueError(f"halo widths must not be negative: {self._halo}")
-        for a in d_arrays + s_arrays:
-            if a.ndim != 3:
-                raise ValueError(f"interpolate takes IJK fields, not a field of {a.ndim} dimension(s)")
-        for name, a in zip(("pos_i", "pos_j"), p_arrays):
-            if a.ndim not in (2, 3):
-                raise ValueError(f"{name} must be an IJK field or a Field[IJ], not a field of {a.ndim} dimension(s)")
-        dtype = d_arrays[0].dtype
-        for a in d_arrays + s_arrays:
-            if a.dtype != dtype:
-                raise TypeError(f"the fields of one call share a dtype: {dtype} and {a.dtype} differ")
-        if dtype not in _FLOATS:
-            raise TypeError(f"interpolate takes float32 or float64 fields, not {dtype}")
-        if p_arrays[0].dtype != p_arrays[1].dtype:
-            raise TypeError(f"pos_i and pos_j share a dtype: {p_arrays[0].dtype} and {p_arrays[1].dtype} differ")
-        if p_arrays[0].dtype not in _FLOATS:
-            raise TypeError(f"position fields are float32 or float64, not {p_arrays[0].dtype}")
         lo_i, hi_i, lo_j, hi_j = self._halo
-        origin = (lo_i, lo_j, 0) if origin is None else _triple(origin, "origin", 0)
-        self.origin = origin
+        self.origin = origin = _origin3(origin, self._halo)
         # the common compute domain: what every array has left behind its origin and (in I and J) in front of its high ghost cells
         rest = [tuple(s - o - h for s, o, h in zip(a.shape, origin, (hi_i, hi_j, 0))) for a in d_arrays + s_arrays + p_arrays]
         domain = tuple(min(r[ax] for r in rest if len(r) > ax) for ax in range(3))
@@ -127,25 +92,10 @@ class HorizontalInterp:
         # every check of the library, nothing enqueued; also: how many kernels
         self.launches = _native(self._dst, self._src, self._n, self._pos_i, self._pos_j, self._extent, self._reach, self._size,
                                 self._pos_size, self._method, self._flags | _lib.INTERP_DRY_RUN, None)
-        # (last: none of the checks above needs a device)
-        for a in d_arrays + s_arrays + p_arrays:
-            if not a.tensor.is_cuda:
-                raise TypeError("interpolate works on device fields; a host array was passed")
-        # what must stay alive is what the CALLER holds (see boundary.HaloFill)
-        self._refs, self._held = [], []
-        for f in dsts + srcs + [pos_i, pos_j]:
-            try:
-                self._refs.append(weakref.ref(f))
-            except TypeError:
-                self._held.append(f)
-        import torch
-
-        self._current_stream = torch.cuda.current_stream
-        self._lib = _lib.load()
+        self._bind("interpolate", d_arrays + s_arrays + p_arrays, dsts + srcs + [pos_i, pos_j])
 
     def __call__(self) -> None:
-        if any(r() is None for r in self._refs):
-            raise RuntimeError("HorizontalInterp: an array this call was bound to no longer exists; build a new HorizontalInterp")
+        self._check_alive()
         rc = self._lib.gt4mi_horizontal_interp(self._dst, self._src, self._n, ctypes.byref(self._pos_i), ctypes.byref(self._pos_j),
                                                self._extent, self._reach, self._size, self._pos_size, self._method, self._flags,
                                                self._current_stream().cuda_stream, None)

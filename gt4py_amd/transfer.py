@@ -27,19 +27,16 @@ float64 -> float32 is one rounding to nearest even and float32 -> float64 is exa
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
-from .boundary import _halo4
+from ._bound import FLOATS as _FLOATS, Bound, _as_list, _halo4, _origin3, _pair_lists, _shape3, _triple, raise_refusal, refuse_host_arrays
 from .storage.device_array import DeviceArray, as_device_array, torch_dtype
 
 PATH_ROWS, PATH_TILES, PATH_ITEMS = _lib.COPY_PATH_ROWS, _lib.COPY_PATH_TILES, _lib.COPY_PATH_ITEMS
 PATH_NAMES = {PATH_ROWS: "rows", PATH_TILES: "tiles", PATH_ITEMS: "items"}
-
-_FLOATS = (np.dtype("float32"), np.dtype("float64"))
 
 
 def _native(dst, src, n: int, extent, dsize: int, ssize: int, flags: int, stream: Optional[int]) -> Tuple[List[int], int]:
@@ -48,27 +45,8 @@ def _native(dst, src, n: int, extent, dsize: int, ssize: int, flags: int, stream
     paths, launches = (ctypes.c_int * n)(), ctypes.c_int(0)
     rc = _lib.load().gt4mi_field_copy(dst, src, n, extent, dsize, ssize, flags, stream, paths, ctypes.byref(launches))
     if rc != _lib.OK:
-        message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
-        if rc == _lib.ERR_HIP:
-            raise _lib.NativeError("gt4mi_field_copy", rc, message)
-        raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+        raise_refusal("gt4mi_field_copy", rc)
     return list(paths), launches.value
-
-
-def _as_list(fields) -> list:
-    """One field or a sequence of fields (a tuple or list; an array is ONE field whatever its length)."""
-    return list(fields) if isinstance(fields, (tuple, list)) else [fields]
-
-
-def _triple(value, name: str, fill: int) -> Tuple[int, int, int]:
-    value = tuple(int(v) for v in value)
-    if len(value) > 3:
-        raise ValueError(f"{name} must have at most three entries, not {value}")
-    return value + (fill,) * (3 - len(value))  # type: ignore[return-value]
-
-
-def _shape3(a: DeviceArray) -> Tuple[int, ...]:
-    return tuple(a.shape) + (1,) * (3 - a.ndim)
 
 
 def _conversion(dst_dtype: np.dtype, src_dtype: np.dtype, convert: bool, who: str) -> int:
@@ -82,7 +60,7 @@ def _conversion(dst_dtype: np.dtype, src_dtype: np.dtype, convert: bool, who: st
     return _lib.COPY_CONVERT
 
 
-class FieldCopy:
+class FieldCopy(Bound):
     """The frozen form of :func:`copy_fields` (what ``FrozenStencil`` is for stencils): arguments are checked (through the
     library's dry run) and the native descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is
     current THEN.
@@ -93,16 +71,7 @@ class FieldCopy:
 
     def __init__(self, dsts, srcs, *, halo=0, origin: Optional[Sequence[int]] = None, domain: Optional[Sequence[int]] = None,
                  convert: bool = False, dst_origin: Optional[Sequence[int]] = None, src_origin: Optional[Sequence[int]] = None):
-        dsts, srcs = _as_list(dsts), _as_list(srcs)
-        if not dsts or not srcs:
-            raise ValueError("copy_fields needs at least one pair of fields")
-        if len(dsts) != len(srcs):
-            raise ValueError(f"copy_fields pairs fields one to one: {len(dsts)} destination(s) and {len(srcs)} source(s) were passed")
-        d_arrays = [as_device_array(f) for f in dsts]
-        s_arrays = [as_device_array(f) for f in srcs]
-        self._halo = _halo4(halo)
-        if min(self._halo) < 0:
-            raise ValueError(f"halo widths must not be negative: {self._halo}")
+        dsts, srcs, d_arrays, s_arrays, _, self._halo = _pair_lists("copy_fields", dsts, srcs, halo)
         for a in d_arrays + s_arrays:
             if a.ndim not in (2, 3):
                 raise ValueError(f"copy_fields takes IJ or IJK fields, not a field of {a.ndim} dimension(s)")
@@ -113,7 +82,7 @@ class FieldCopy:
         self._flags = _conversion(d_arrays[0].dtype, s_arrays[0].dtype, bool(convert), "copy_fields")
         self._dsize, self._ssize = d_arrays[0].itemsize, s_arrays[0].itemsize
         lo_i, hi_i, lo_j, hi_j = self._halo
-        default = (lo_i, lo_j, 0) if origin is None else _triple(origin, "origin", 0)
+        default = _origin3(origin, self._halo)
         d_origin = default if dst_origin is None else _triple(dst_origin, "dst_origin", 0)
         s_origin = default if src_origin is None else _triple(src_origin, "src_origin", 0)
         if domain is None:
@@ -138,25 +107,10 @@ class FieldCopy:
         # every check of the library, nothing enqueued; also: which paths, how many kernels
         self.paths, self.launches = _native(self._dst, self._src, self._n, self._extent3, self._dsize, self._ssize,
                                             self._flags | _lib.COPY_DRY_RUN, None)
-        # (last: none of the checks above needs a device)
-        for a in d_arrays + s_arrays:
-            if not a.tensor.is_cuda:
-                raise TypeError("copy_fields works on device fields; a host array was passed")
-        # what must stay alive is what the CALLER holds (see boundary.HaloFill)
-        self._refs, self._held = [], []
-        for f in dsts + srcs:
-            try:
-                self._refs.append(weakref.ref(f))
-            except TypeError:
-                self._held.append(f)
-        import torch
-
-        self._current_stream = torch.cuda.current_stream
-        self._lib = _lib.load()
+        self._bind("copy_fields", d_arrays + s_arrays, dsts + srcs)
 
     def __call__(self) -> None:
-        if any(r() is None for r in self._refs):
-            raise RuntimeError("FieldCopy: an array this call was bound to no longer exists; build a new FieldCopy")
+        self._check_alive()
         rc = self._lib.gt4mi_field_copy(self._dst, self._src, self._n, self._extent3, self._dsize, self._ssize, self._flags,
                                         self._current_stream().cuda_stream, None, None)
         if rc != _lib.OK:
@@ -205,7 +159,7 @@ class _Staged:
         if min(halo4) < 0:
             raise ValueError(f"halo widths must not be negative: {halo4}")
         lo_i, hi_i, lo_j, hi_j = halo4
-        origin = (lo_i, lo_j, 0) if origin is None else _triple(origin, "origin", 0)
+        origin = _origin3(origin, halo4)
         if domain is None:
             rest = [tuple(s - o - h for s, o, h in zip(_shape3(a), origin, (hi_i, hi_j, 0))) for a in arrays]
             domain = tuple(min(r[ax] for r in rest) for ax in range(3))
@@ -219,9 +173,7 @@ class _Staged:
         # the library's own checks of the fields' side (bounds, strides) before anything is allocated: a dry run against made-up
         # staging addresses in C order, far from the fields
         self._check_fields(arrays, halo4, origin, domain, box, download)
-        for a in arrays:
-            if not a.tensor.is_cuda:
-                raise TypeError(f"{who} works on device fields; a host array was passed")
+        refuse_host_arrays(who, arrays)
         import torch
 
         self._torch = torch

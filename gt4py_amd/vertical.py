@@ -27,18 +27,13 @@ range sees the end cell's mean there.  The arithmetic -- float64 throughout, its
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Optional, Sequence
 
-import numpy as np
-
 from . import _lib
-from .boundary import _halo4
-from .storage.device_array import DeviceArray, as_device_array
-from .transfer import _as_list, _triple
+from ._bound import Bound, _float_pairs, _origin3, raise_refusal
+from .storage.device_array import DeviceArray
 
 METHODS = {"pcm": _lib.REMAP_PCM, "plm": _lib.REMAP_PLM}
-_FLOATS = (np.dtype("float32"), np.dtype("float64"))
 
 
 def _native(dst, src, n: int, src_edges, dst_edges, extent_ij, ns: int, nd: int, size: int, edge_size: int, method: int, flags: int,
@@ -49,10 +44,7 @@ def _native(dst, src, n: int, src_edges, dst_edges, extent_ij, ns: int, nd: int,
     rc = _lib.load().gt4mi_vertical_remap(dst, src, n, ctypes.byref(src_edges), ctypes.byref(dst_edges), extent_ij, ns, nd, size,
                                           edge_size, method, flags, stream, ctypes.byref(launches))
     if rc != _lib.OK:
-        message = _lib.load().gt4mi_last_error().decode("utf-8", "replace")
-        if rc == _lib.ERR_HIP:
-            raise _lib.NativeError("gt4mi_vertical_remap", rc, message)
-        raise (TypeError if rc == _lib.ERR_UNSUPPORTED else ValueError)(message)
+        raise_refusal("gt4mi_vertical_remap", rc)
     return launches.value
 
 
@@ -62,7 +54,7 @@ def _edge_field(a: DeviceArray, start) -> "_lib.Field":
     return _lib.Field.make(a.ptr, a.shape, a.strides, start)
 
 
-class VerticalRemap:
+class VerticalRemap(Bound):
     """The frozen form of :func:`remap_levels` (what ``FrozenStencil`` is for stencils): arguments are checked (through the
     library's dry run) and the native descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is
     current THEN.
@@ -72,39 +64,12 @@ class VerticalRemap:
     refuses to run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
 
     def __init__(self, dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0, origin: Optional[Sequence[int]] = None):
-        dsts, srcs = _as_list(dst), _as_list(src)
-        if not dsts or not srcs:
-            raise ValueError("remap_levels needs at least one pair of fields")
-        if len(dsts) != len(srcs):
-            raise ValueError(f"remap_levels pairs fields one to one: {len(dsts)} destination(s) and {len(srcs)} source(s) were passed")
-        if method not in METHODS:
-            raise ValueError(f"method must be one of {sorted(METHODS)}, not {method!r}")
+        dsts, srcs, d_arrays, s_arrays, e_arrays, self._halo = _float_pairs(
+            "remap_levels", dst, src, halo, method, METHODS, shared=(src_edges, dst_edges), names=("src_edges", "dst_edges"), ndims=(1, 3),
+            kind="Field[K]", plural="edge fields")
         self.method = method
-        d_arrays = [as_device_array(f) for f in dsts]
-        s_arrays = [as_device_array(f) for f in srcs]
-        e_arrays = [as_device_array(src_edges), as_device_array(dst_edges)]
-        self._halo = _halo4(halo)
-        if min(self._halo) < 0:
-            raise ValueError(f"halo widths must not be negative: {self._halo}")
-        for a in d_arrays + s_arrays:
-            if a.ndim != 3:
-                raise ValueError(f"remap_levels takes IJK fields, not a field of {a.ndim} dimension(s)")
-        for name, a in zip(("src_edges", "dst_edges"), e_arrays):
-            if a.ndim not in (1, 3):
-                raise ValueError(f"{name} must be an IJK field or a Field[K], not a field of {a.ndim} dimension(s)")
-        dtype = d_arrays[0].dtype
-        for a in d_arrays + s_arrays:
-            if a.dtype != dtype:
-                raise TypeError(f"the fields of one call share a dtype: {dtype} and {a.dtype} differ")
-        if dtype not in _FLOATS:
-            raise TypeError(f"remap_levels takes float32 or float64 fields, not {dtype}")
-        if e_arrays[0].dtype != e_arrays[1].dtype:
-            raise TypeError(f"src_edges and dst_edges share a dtype: {e_arrays[0].dtype} and {e_arrays[1].dtype} differ")
-        if e_arrays[0].dtype not in _FLOATS:
-            raise TypeError(f"edge fields are float32 or float64, not {e_arrays[0].dtype}")
         lo_i, hi_i, lo_j, hi_j = self._halo
-        origin = (lo_i, lo_j, 0) if origin is None else _triple(origin, "origin", 0)
-        self.origin = origin
+        self.origin = origin = _origin3(origin, self._halo)
         # levels: what every src / dst has behind the origin; an edge field has one more
         levels = []
         for side, arrays, edges, name in (("sources", s_arrays, e_arrays[0], "src_edges"), ("destinations", d_arrays, e_arrays[1], "dst_edges")):
@@ -139,25 +104,10 @@ class VerticalRemap:
         # every check of the library, nothing enqueued; also: how many kernels
         self.launches = _native(self._dst, self._src, self._n, self._src_edges, self._dst_edges, self._extent2, self.ns, self.nd,
                                 self._size, self._edge_size, self._method, _lib.REMAP_DRY_RUN, None)
-        # (last: none of the checks above needs a device)
-        for a in d_arrays + s_arrays + e_arrays:
-            if not a.tensor.is_cuda:
-                raise TypeError("remap_levels works on device fields; a host array was passed")
-        # what must stay alive is what the CALLER holds (see boundary.HaloFill)
-        self._refs, self._held = [], []
-        for f in dsts + srcs + [src_edges, dst_edges]:
-            try:
-                self._refs.append(weakref.ref(f))
-            except TypeError:
-                self._held.append(f)
-        import torch
-
-        self._current_stream = torch.cuda.current_stream
-        self._lib = _lib.load()
+        self._bind("remap_levels", d_arrays + s_arrays + e_arrays, dsts + srcs + [src_edges, dst_edges])
 
     def __call__(self) -> None:
-        if any(r() is None for r in self._refs):
-            raise RuntimeError("VerticalRemap: an array this call was bound to no longer exists; build a new VerticalRemap")
+        self._check_alive()
         rc = self._lib.gt4mi_vertical_remap(self._dst, self._src, self._n, ctypes.byref(self._src_edges), ctypes.byref(self._dst_edges),
                                             self._extent2, self.ns, self.nd, self._size, self._edge_size, self._method, 0,
                                             self._current_stream().cuda_stream, None)

@@ -261,7 +261,8 @@ int gt4mi_level_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
  *   GT4MI_COPY_PATH_ROWS    both sides have unit item stride along the same axis (of extent > 1): rows, 16-byte lanes where both allow
  *   GT4MI_COPY_PATH_TILES   unit item stride along different axes: a transpose, tiles through on-chip memory, coalesced on both sides
  *   GT4MI_COPY_PATH_ITEMS   anything else: a side without unit stride on an axis of extent > 1, a broadcast src
- * A src stride of 0 is allowed and broadcasts; a dst stride of 0 on an axis of extent > 1 is GT4MI_ERR_INVALID_ARGUMENT.  The bytes
+ * A src stride of 0 is allowed and broadcasts; a dst stride of 0 on an axis of extent > 1 is GT4MI_ERR_INVALID_ARGUMENT (reported
+ * before an origin or extent outside the array along the same axis, as the other entries do).  The bytes
  * of a dst box (first to last item) must meet neither those of any src box nor of another dst box of the call
  * (GT4MI_ERR_UNSUPPORTED).  No byte outside the dst boxes changes.  An extent with a zero entry is GT4MI_OK, nothing enqueued.
  * Every check runs before the first launch; a refused call enqueues nothing.  With GT4MI_COPY_DRY_RUN the checks run, paths and

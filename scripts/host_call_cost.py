@@ -53,3 +53,37 @@ for _ in range(50): g.replay()
 torch.cuda.synchronize()
 graph = (time.perf_counter() - t) / 50
 print(f"20 dependent 128x128x64 Laplacian applies: eager {eager*1e6:7.1f} us, hipGraph replay {graph*1e6:7.1f} us")
+
+# frozen utility calls (boundary, diagnostics, transfer, vertical, horizontal): host cost of one call, 16 x 16 x 8 domain, halo 2.
+# Five repeats of 2 000 calls with one synchronisation at the end of each; the median and the spread (max - min) of the five.
+import statistics
+from gt4py_amd import boundary, diagnostics, horizontal, transfer, vertical
+
+
+def _frozen_utilities():
+    def field(nk=8):
+        return gt_storage.zeros((20, 20, nk), backend="hip:mi300", aligned_index=(2, 2, 0))
+
+    a, b, c, d, pi, pj = (field() for _ in range(6))  # (named: a frozen call holds weak references to what it was given)
+    zs = gt_storage.from_array(np.arange(9.0), backend="hip:mi300")
+    zd = gt_storage.from_array(np.arange(9.0), backend="hip:mi300")
+    yield "HaloFill", boundary.HaloFill([a, b], halo=2, mode="periodic")
+    yield "FieldStats", diagnostics.FieldStats([a, b], halo=2)
+    yield "LevelStats", diagnostics.LevelStats([a, b], halo=2)
+    yield "FieldCopy", transfer.FieldCopy([c, d], [a, b], halo=2)
+    yield "VerticalRemap", vertical.VerticalRemap([c, d], [a, b], src_edges=zs, dst_edges=zd, method="plm", halo=2)
+    yield "HorizontalInterp", horizontal.HorizontalInterp([c, d], [a, b], pos_i=pi, pos_j=pj, relative=True, method="cubic", halo=2)
+
+
+print(f"{'frozen utility call':18s} {'median us':>10s} {'spread us':>10s}   five repeats of 2000 calls (us per call)")
+for name, call in _frozen_utilities():
+    assert tuple(getattr(call, "domain", (16, 16, 8)))[:2] == (16, 16)
+    for _ in range(20): call()
+    torch.cuda.synchronize()
+    per_call = []
+    for _ in range(5):
+        t = time.perf_counter()
+        for _ in range(2000): call()
+        t1 = time.perf_counter(); torch.cuda.synchronize()
+        per_call.append((t1 - t) / 2000 * 1e6)
+    print(f"{name:18s} {statistics.median(per_call):10.2f} {max(per_call) - min(per_call):10.2f}   " + " ".join(f"{x:6.2f}" for x in per_call))
