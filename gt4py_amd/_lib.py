@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = (
     "gt4mi_field_copy",
     "gt4mi_vertical_remap",
     "gt4mi_horizontal_interp",
+    "gt4mi_overlap_table",
+    "gt4mi_horizontal_remap",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -113,6 +115,8 @@ REMAP_PCM, REMAP_PLM, REMAP_DRY_RUN = 0, 1, 256
 # gt4mi_horizontal_interp: methods, flags
 INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC, INTERP_CUBIC_MONOTONE = 0, 1, 2, 3
 INTERP_RELATIVE, INTERP_DRY_RUN = 1, 256
+# gt4mi_horizontal_remap: methods, flags
+HREMAP_PCM, HREMAP_PLM, HREMAP_DRY_RUN = 0, 1, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -135,6 +139,14 @@ class Field(ctypes.Structure):
             raise ValueError("gt4mi_field describes exactly three axes (I, J, K)")
         return cls(ctypes.c_void_p(ptr), _Int3(*map(int, shape)), _Int3(*map(int, strides)),
                    _Int3(*map(int, origin)))
+
+
+class OverlapAxis(ctypes.Structure):
+    """``gt4mi_overlap_axis``: the overlap table of one axis -- counts and six pointers (device pointers for
+    ``gt4mi_horizontal_remap``)."""
+
+    _fields_ = [("ns", ctypes.c_int32), ("nd", ctypes.c_int32), ("nnz", ctypes.c_int32), ("ptr", ctypes.c_void_p), ("cell", ctypes.c_void_p),
+                ("w", ctypes.c_void_p), ("h", ctypes.c_void_p), ("c", ctypes.c_void_p), ("den", ctypes.c_void_p)]
 
 
 class HaloMsg(ctypes.Structure):
@@ -224,6 +236,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_vertical_remap.argtypes = [FP, FP, I, FP, FP, DOM, ctypes.c_int64, ctypes.c_int64, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_horizontal_interp.restype = I
     lib.gt4mi_horizontal_interp.argtypes = [FP, FP, I, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_overlap_table.restype = I
+    lib.gt4mi_overlap_table.argtypes = [P, I, P, I, P, P, P, P, P, P, I, ctypes.POINTER(ctypes.c_int)]
+    AP = ctypes.POINTER(OverlapAxis)
+    lib.gt4mi_horizontal_remap.restype = I
+    lib.gt4mi_horizontal_remap.argtypes = [FP, FP, I, AP, AP, ctypes.c_int64, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

@@ -1,5 +1,5 @@
 // Host-side helpers that the multi-field utility entries (halo_fill, field_stats, level_stats, field_copy, vertical_remap,
-// horizontal_interp) share: where a field's origin item is, which bytes its box touches, the per-field argument check and
+// horizontal_interp, horizontal_remap) share: where a field's origin item is, which bytes its box touches, the per-field argument check and
 // the "no dst meets anything that is read" sweep.  What differs between the entries is DATA (BoxChecks, the arguments of
 // check_box_field): a new entry states its differences here instead of copying a check function.  The messages are part of
 // the library's behaviour (tests/test_refusal_messages.py holds them byte for byte).

@@ -16,6 +16,7 @@
 #include "field_copy.hip.h"
 #include "vertical_remap.hip.h"
 #include "horizontal_interp.hip.h"
+#include "horizontal_remap.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -231,6 +232,18 @@ int gt4mi_horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int 
                             int pos_elem_size, int method, int flags, void* stream, int* launches) {
     return gt4mi::horizontal_interp(dst, src, nfields, pos_i, pos_j, extent, reach, elem_size, pos_elem_size, method, flags,
                                     static_cast<hipStream_t>(stream), launches);
+}
+
+int gt4mi_overlap_table(const double* src_edges, int ns, const double* dst_edges, int nd, int32_t* ptr, int32_t* cell, double* w,
+                        double* h, double* c, double* den, int capacity, int* nnz) {
+    return gt4mi::overlap_table(src_edges, ns, dst_edges, nd, ptr, cell, w, h, c, den, capacity, nnz);
+}
+
+int gt4mi_horizontal_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_overlap_axis* axis_i,
+                           const gt4mi_overlap_axis* axis_j, int64_t nk, int elem_size, int method, int flags, void* stream,
+                           int* launches) {
+    return gt4mi::horizontal_remap(dst, src, nfields, axis_i, axis_j, nk, elem_size, method, flags, static_cast<hipStream_t>(stream),
+                                   launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

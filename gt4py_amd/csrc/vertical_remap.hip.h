@@ -60,15 +60,21 @@ struct RemapArgs {
     unsigned tiles_i;
 };
 
-__device__ __forceinline__ double remap_slope(double qm, double qc, double qp, double hm, double hc, double hp) {
+// the limited centred slope across a cell of thickness hc, den = 0.5 h[k-1] + h[k] + 0.5 h[k+1] (horizontal_remap.hip.h reads den
+// from its overlap table)
+__device__ __forceinline__ double remap_slope_den(double qm, double qc, double qp, double den, double hc) {
     const double dl = qc - qm, dr = qp - qc;
     if (!(dl * dr > 0.0)) return 0.0;
-    const double g = (qp - qm) / (0.5 * hm + hc + 0.5 * hp) * hc;
+    const double g = (qp - qm) / den * hc;
     double a = fabs(g);
     const double b = 2.0 * fabs(dl), c = 2.0 * fabs(dr);
     if (b < a) a = b;
     if (c < a) a = c;
     return copysign(a, g);
+}
+
+__device__ __forceinline__ double remap_slope(double qm, double qc, double qp, double hm, double hc, double hp) {
+    return remap_slope_den(qm, qc, qp, 0.5 * hm + hc + 0.5 * hp, hc);
 }
 
 // T: item type of the fields, E: of the edges, METHOD: GT4MI_REMAP_*, NF: entries the kernel has registers for (a.nf <= NF)

@@ -1,4 +1,5 @@
-"""``gt4py_amd.horizontal`` -- the value of fields at run-time horizontal positions, one kernel launch per 8 fields.
+"""``gt4py_amd.horizontal`` -- the value of fields at run-time horizontal positions (:func:`interpolate`) and their cell means on
+another rectilinear grid (:func:`remap_cells`), one kernel launch per 8 fields.
 
 GTScript takes compile-time horizontal offsets only (only K may be indexed at run time), so "the value of a field at a point whose
 I / J position is data" -- the departure-point interpolation of a semi-Lagrangian step, sampling on a rotated, shifted or nested
@@ -24,6 +25,24 @@ decomposed run the halo width is the Courant limit.  ``method`` is ``"nearest"``
 ``"cubic_monotone"`` (the cubic limited to the range of the four surrounding items: the quasi-monotone limiter of semi-Lagrangian
 schemes).  The arithmetic -- float64 throughout, its order fixed -- is part of the contract (include/gt4py_amd.h): the same point
 gives the same bits whatever the layout, the position in the call or the device.
+
+Point sampling neither conserves nor averages.  ``gt4mi_horizontal_remap`` (csrc/horizontal_remap.hip.h) takes cell MEANS on one
+rectilinear grid to cell means on another -- coarser, finer or shifted: output at reduced resolution, a nest and its parent, the
+restriction and prolongation of a multigrid cycle --, which no stencil can write (a destination point reads sources at compile-time
+constant offsets only, never ``2*i`` or a source of another shape).  The grids are four 1-d HOST arrays of edges, fixed for the
+life of the frozen call; the geometry is two small per-axis overlap tables computed once on the host.
+
+    coarsen = horizontal.HorizontalRemap([u_c, v_c, t_c], [u, v, t], src_edges=(x, y), dst_edges=(x_out, y_out), method="plm")
+    out = transfer.Download([u_c, v_c, t_c], dtype=np.float32)
+    for step in range(steps):
+        ...
+        if step % n == 0:
+            coarsen()            # enqueues; the download behind it on the same stream reads the coarse fields
+            pending = out()
+
+``method`` is ``"pcm"`` (piecewise constant) or ``"plm"`` (piecewise linear, slopes limited per axis).  Both conserve the integral
+when the outer edges of the two grids coincide; a destination cell that reaches outside the source grid sees the end cell's mean
+there.
 """
 
 from __future__ import annotations
@@ -31,8 +50,10 @@ from __future__ import annotations
 import ctypes
 from typing import Optional, Sequence
 
+import numpy as np
+
 from . import _lib
-from ._bound import Bound, _float_pairs, _origin3, raise_refusal
+from ._bound import FLOATS, Bound, _float_pairs, _origin3, _pair_lists, _triple, raise_refusal
 from .storage.device_array import DeviceArray
 
 METHODS = {"nearest": _lib.INTERP_NEAREST, "linear": _lib.INTERP_LINEAR, "cubic": _lib.INTERP_CUBIC,
@@ -122,3 +143,139 @@ def interpolate(dst, src, *, pos_i, pos_j, method: str = "linear", relative: boo
     Raises ``ValueError`` / ``TypeError`` (with the library's message) before any GPU work.  For a time loop build a
     :class:`HorizontalInterp` once instead."""
     HorizontalInterp(dst, src, pos_i=pos_i, pos_j=pos_j, method=method, relative=relative, halo=halo, origin=origin)()
+
+
+# ---- conservative remapping between rectilinear grids ---------------------------------------------------------------------------
+REMAP_METHODS = {"pcm": _lib.HREMAP_PCM, "plm": _lib.HREMAP_PLM}
+
+
+def overlap_table(src_edges, dst_edges):
+    """The overlap table of one axis (``gt4mi_overlap_table``, host code): ``(ptr, cell, w, h, c, den)`` as numpy arrays, int32 /
+    int32 / float64 x 4; the terms of destination cell ``m`` are ``ptr[m] .. ptr[m + 1]``."""
+    xs, xd = (np.ascontiguousarray(e, dtype=np.float64) for e in (src_edges, dst_edges))
+    ns, nd = xs.size - 1, xd.size - 1
+    capacity = max(ns + nd - 1, 1)
+    ptr, cell = np.zeros(max(nd, 0) + 1, dtype=np.int32), np.zeros(capacity, dtype=np.int32)
+    w, h, c, den = (np.zeros(capacity, dtype=np.float64) for _ in range(4))
+    nnz = ctypes.c_int(0)
+    rc = _lib.load().gt4mi_overlap_table(xs.ctypes.data, ns, xd.ctypes.data, nd, ptr.ctypes.data, cell.ctypes.data, w.ctypes.data,
+                                         h.ctypes.data, c.ctypes.data, den.ctypes.data, capacity, ctypes.byref(nnz))
+    if rc != _lib.OK:
+        raise_refusal("gt4mi_overlap_table", rc)
+    return (ptr,) + tuple(a[: nnz.value] for a in (cell, w, h, c, den))
+
+
+def _edge_pair(edges, name: str):
+    if not isinstance(edges, (tuple, list)) or len(edges) != 2:
+        raise ValueError(f"{name} must be a pair (edges along I, edges along J)")
+    out = []
+    for axis, e in zip("IJ", edges):
+        try:
+            e = np.array(e, dtype=np.float64)  # (a copy: the edges are fixed for the life of the call)
+        except (TypeError, ValueError):
+            raise TypeError(f"{name} along {axis} must be a 1-d host array-like of numbers") from None
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError(f"{name} along {axis} must be a 1-d array of at least 2 edges, not an array of shape {e.shape}")
+        out.append(e)
+    return out
+
+
+def _native_remap(dst, src, n: int, axis_i, axis_j, nk: int, size: int, method: int, flags: int, stream: Optional[int]) -> int:
+    launches = ctypes.c_int(0)
+    rc = _lib.load().gt4mi_horizontal_remap(dst, src, n, ctypes.byref(axis_i), ctypes.byref(axis_j), nk, size, method, flags, stream,
+                                            ctypes.byref(launches))
+    if rc != _lib.OK:
+        raise_refusal("gt4mi_horizontal_remap", rc)
+    return launches.value
+
+
+class HorizontalRemap(Bound):
+    """The frozen form of :func:`remap_cells`: arguments are checked, the two overlap tables computed on the host
+    (``gt4mi_overlap_table``) and copied to device arrays that the object OWNS, the library's dry run made and the native
+    descriptors built once; ``__call__()`` makes only the ctypes call, on the stream that is current THEN.
+
+    ``src_extent`` / ``dst_extent`` are the (I, J) cells of the two grids, ``nk`` the levels, ``terms`` the table entries per axis,
+    ``launches`` the kernels a call enqueues.  The object holds raw pointers and weak references to the CALLER's fields, not the
+    arrays: it refuses to run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
+
+    def __init__(self, dst, src, *, src_edges, dst_edges, method: str = "pcm", src_origin: Optional[Sequence[int]] = None,
+                 dst_origin: Optional[Sequence[int]] = None):
+        dsts, srcs, d_arrays, s_arrays, _, _ = _pair_lists("remap_cells", dst, src, 0, method, REMAP_METHODS)
+        for a in d_arrays + s_arrays:
+            if a.ndim != 3:
+                raise ValueError(f"remap_cells takes IJK fields, not a field of {a.ndim} dimension(s)")
+        dtype = d_arrays[0].dtype
+        for a in d_arrays + s_arrays:
+            if a.dtype != dtype:
+                raise TypeError(f"the fields of one call share a dtype: {dtype} and {a.dtype} differ")
+        if dtype not in FLOATS:
+            raise TypeError(f"remap_cells takes float32 or float64 fields, not {dtype}")
+        self.method = method
+        xs, xd = _edge_pair(src_edges, "src_edges"), _edge_pair(dst_edges, "dst_edges")
+        self.src_extent, self.dst_extent = tuple(e.size - 1 for e in xs), tuple(e.size - 1 for e in xd)
+        self.src_origin = s_origin = (0, 0, 0) if src_origin is None else _triple(src_origin, "src_origin", 0)
+        self.dst_origin = d_origin = (0, 0, 0) if dst_origin is None else _triple(dst_origin, "dst_origin", 0)
+        # levels: what every field has behind its origin along K; cells: what the edges say must fit behind the origin in I and J
+        levels = {a.shape[2] - org[2] for arrays, org in ((d_arrays, d_origin), (s_arrays, s_origin)) for a in arrays}
+        if len(levels) != 1:
+            raise ValueError(f"the fields of one call share their number of levels behind the origin: {sorted(levels)} differ")
+        self.nk = levels.pop()
+        if self.nk < 1:
+            raise ValueError(f"origins {d_origin} (dst) / {s_origin} (src) leave no level in fields of shapes {[a.shape for a in d_arrays + s_arrays]}")
+        for side, arrays, org, extent in (("dst", d_arrays, d_origin, self.dst_extent), ("src", s_arrays, s_origin, self.src_extent)):
+            for n, a in enumerate(arrays):
+                for ax in range(2):
+                    if org[ax] < 0 or org[ax] + extent[ax] > a.shape[ax]:
+                        raise ValueError(f"{side}_edges along {'IJ'[ax]} has {extent[ax] + 1} edges: {extent[ax]} cells from origin {org[ax]} do "
+                                         f"not match {side} {n} of shape {a.shape}")
+        tables = [overlap_table(s, d) for s, d in zip(xs, xd)]  # (refuses edges that are not finite and strictly increasing)
+        self.terms = tuple(int(t[1].size) for t in tables)
+        import torch
+
+        device = d_arrays[0].tensor.device
+        self._tables, axes = [], []
+        for (ptr, cell, *reals), ns, nd in zip(tables, self.src_extent, self.dst_extent):
+            ints = torch.from_numpy(np.concatenate([ptr, cell])).to(device)
+            real = torch.from_numpy(np.concatenate(reals)).to(device)
+            self._tables += [ints, real]
+            nnz = cell.size
+            axes.append(_lib.OverlapAxis(ns, nd, nnz, ints.data_ptr(), ints.data_ptr() + 4 * (nd + 1),
+                                         *[real.data_ptr() + 8 * nnz * m for m in range(4)]))
+        self._axis_i, self._axis_j = axes
+        self._n = len(d_arrays)
+        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
+        for table, arrays, org in ((self._dst, d_arrays, d_origin), (self._src, s_arrays, s_origin)):
+            for n, a in enumerate(arrays):
+                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, org)
+        self._size, self._method = d_arrays[0].itemsize, REMAP_METHODS[method]
+        # every check of the library, nothing enqueued; also: how many kernels
+        self.launches = _native_remap(self._dst, self._src, self._n, self._axis_i, self._axis_j, self.nk, self._size, self._method,
+                                      _lib.HREMAP_DRY_RUN, None)
+        self._bind("remap_cells", d_arrays + s_arrays, dsts + srcs)
+
+    def __call__(self) -> None:
+        self._check_alive()
+        rc = self._lib.gt4mi_horizontal_remap(self._dst, self._src, self._n, ctypes.byref(self._axis_i), ctypes.byref(self._axis_j), self.nk,
+                                              self._size, self._method, 0, self._current_stream().cuda_stream, None)
+        if rc != _lib.OK:
+            _lib.check("gt4mi_horizontal_remap", rc)
+
+
+def remap_cells(dst, src, *, src_edges, dst_edges, method: str = "pcm", src_origin: Optional[Sequence[int]] = None,
+                dst_origin: Optional[Sequence[int]] = None) -> None:
+    """Remap the cell means ``src`` on the rectilinear grid ``src_edges`` to cell means ``dst`` on the grid ``dst_edges``, level by
+    level, in one kernel launch (per 8 pairs) on the current stream.
+
+    ``dst``, ``src``  one field each or two sequences of equal length: IJK :class:`DeviceArray`\\ s of one dtype (float32 or
+                float64) or anything ``as_device_array`` accepts; every field may differ in address, strides and padding, the
+                sources have one horizontal shape and the destinations another.  A dst must not share memory with a src or
+                another dst.
+    ``src_edges``, ``dst_edges``  pairs ``(edges along I, edges along J)`` of 1-d HOST array-likes, converted to float64: finite,
+                strictly increasing, ``cells + 1`` each.  The boxes they describe start at the origins.
+    ``method``  ``"pcm"`` or ``"plm"``.
+    ``src_origin``, ``dst_origin``  first cell of the grid in every src / dst, default ``(0, 0, 0)``; all fields have the same
+                number of levels ``nk`` behind their origin.
+
+    Raises ``ValueError`` / ``TypeError`` (with the library's message) before any GPU work.  For a time loop build a
+    :class:`HorizontalRemap` once instead."""
+    HorizontalRemap(dst, src, src_edges=src_edges, dst_edges=dst_edges, method=method, src_origin=src_origin, dst_origin=dst_origin)()

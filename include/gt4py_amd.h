@@ -365,6 +365,82 @@ int gt4mi_horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int 
                             const gt4mi_field* pos_j, const int64_t extent[3], const int64_t reach[4], int elem_size,
                             int pos_elem_size, int method, int flags, void* stream, int* launches);
 
+/* ---- conservative horizontal remapping between rectilinear grids (NEW entries, additive: the ABI version stays 8; no reference
+ * counterpart -- a GTScript destination point (i, j) reads sources at compile-time constant offsets from (i, j) only: not 2*i, not a
+ * run-time range of source cells, not a source field of another horizontal shape) ---------------------------------------------------
+ * Takes cell MEANS of `nfields` fields on one rectilinear horizontal grid to cell means on another (coarser, finer or shifted), level
+ * by level.  Each of the I and J axes has ns + 1 source edges and nd + 1 destination edges; a 2-d overlap is the product of two 1-d
+ * overlaps, so all geometry is two small per-axis tables, computed ONCE on the host by gt4mi_overlap_table and applied to every level of
+ * up to 8 fields per launch by gt4mi_horizontal_remap.
+ *
+ * gt4mi_overlap_table (pure host code, no GPU): src_edges[0..ns], dst_edges[0..nd] are HOST float64 arrays, finite and strictly
+ * increasing; the table goes to the caller's HOST arrays ptr[nd + 1], cell / w / h / c / den[capacity]; capacity >= ns + nd - 1 is
+ * always enough; *nnz receives the number of terms.  h, c, den may all three be NULL (a table for GT4MI_HREMAP_PCM only).
+ * THE ARITHMETIC IS PART OF THE CONTRACT and is gt4mi_vertical_remap's, per axis (tests/horizontal_remap_ref.py restates it in plain
+ * Python): float64, one IEEE rounding per operation, no FMA.  With xs = src_edges, xd = dst_edges: the first source cell extends to
+ * -inf and the last to +inf (edge replication: a destination cell that reaches outside the source range sees the end cell's mean there,
+ * the weights of a destination cell still sum to 1, nothing is extrapolated).  A source index k is kept across the destination cells
+ * and never decreases.  For destination cell m, lo = xd[m], hi = xd[m+1], d = hi - lo:
+ *   1. advance: while k < ns-1 and not (xs[k+1] > lo): k += 1
+ *   2. for each overlapping k, in increasing order, one TERM:
+ *        l = lo if k == 0    else max(lo, xs[k])     (max(a, b) = b if b > a else a)
+ *        r = hi if k == ns-1 else min(hi, xs[k+1])   (min(a, b) = b if b < a else a)
+ *        cell = k,  w = (r - l) / d
+ *        h = xs[k+1] - xs[k],  xl = (l - xs[k]) / h,  xr = (r - xs[k]) / h,  c = 0.5 * (xl + xr) - 0.5
+ *        den = 0.5 * h[k-1] + h[k] + 0.5 * h[k+1] (left to right), 1.0 in the two end cells (k == 0 or k == ns-1)
+ *        stop after the term for which k == ns-1 or xs[k+1] >= hi, otherwise k += 1
+ *   ptr[m] .. ptr[m+1] are the terms of destination cell m (ptr[0] = 0, ptr[nd] = *nnz); nd <= *nnz <= ns + nd - 1; with identical grids
+ *   every cell has one term with w exactly 1.0.
+ * Refusals of gt4mi_overlap_table, each with a message: a null pointer (h, c, den: only some of the three), ns < 1 or nd < 1, edges that
+ * are not finite and strictly increasing (GT4MI_ERR_INVALID_ARGUMENT); a capacity that is too small (GT4MI_ERR_OUT_OF_BOUNDS). */
+typedef struct gt4mi_overlap_axis {
+    int32_t ns, nd, nnz;  /* source cells, destination cells, terms                            */
+    const int32_t* ptr;   /* nd + 1: the terms of destination cell m are ptr[m] .. ptr[m+1]    */
+    const int32_t* cell;  /* nnz: the source cell k of a term                                  */
+    const double* w;      /* nnz: its weight                                                   */
+    const double* h;      /* nnz: the thickness of source cell k       (GT4MI_HREMAP_PLM only) */
+    const double* c;      /* nnz: where the overlap's centre lies in it (GT4MI_HREMAP_PLM only) */
+    const double* den;    /* nnz: the centred difference's denominator (GT4MI_HREMAP_PLM only) */
+} gt4mi_overlap_axis;
+int gt4mi_overlap_table(const double* src_edges, int ns, const double* dst_edges, int nd, int32_t* ptr, int32_t* cell, double* w,
+                        double* h, double* c, double* den, int capacity, int* nnz);
+
+/* gt4mi_horizontal_remap: the table pointers of axis_i / axis_j are DEVICE pointers (the two structs themselves are host memory).  The
+ * dst box is (axis_i->nd, axis_j->nd, nk) from the origin of each dst[n], the src box (axis_i->ns, axis_j->ns, nk) from the origin of
+ * each src[n]; ONE kernel launch per 8 pairs, on `stream`, without synchronisation or allocation.  `elem_size` is 4 (float32) or 8
+ * (float64); any strides and any two layouts; a src stride of 0 broadcasts; a dst stride of 0 on an extent above 1 is
+ * GT4MI_ERR_INVALID_ARGUMENT.
+ * THE VALUES ARE PART OF THE CONTRACT (csrc/horizontal_remap.hip.h states them again).  Everything is float64, items are widened exactly
+ * on load, the result is rounded once on store, each product is rounded before its addition.  For a destination point the outer loop
+ * runs over the J terms b in table order, the inner loop over the I terms a in table order; q[a, b] is the item of the level at source
+ * cell (cell_i[a], cell_j[b]):
+ *   GT4MI_HREMAP_PCM   row_b = sum_a wi_a * q[a, b];  out = sum_b wj_b * row_b.  The first term of each sum IS the accumulator, so with
+ *                      identical grids q comes back bit for bit, -0.0 included.
+ *   GT4MI_HREMAP_PLM   the same two sums over v = (q[a, b] + si * ci_a) + sj * cj_b, with si / sj the limited centred slopes of source
+ *                      cell (a, b) along I / J, formula and order of gt4mi_vertical_remap: with q-, q+ the neighbours along the axis,
+ *                      dl = q - q-, dr = q+ - q: if dl * dr > 0 then g = (q+ - q-) / den * h and the slope is
+ *                      copysign(min(|g|, 2|dl|, 2|dr|), g) (min(a, b) = b if b < a else a, in this order), otherwise 0.  The slope is 0
+ *                      when the cell is the first or last of that axis of the source BOX: nothing outside the box is ever read.
+ *                      The limiter acts per axis: plm is conservative and reproduces fields linear in x and y away from the end cells,
+ *                      but it is not strictly monotone in 2-d (the two corrections add up at a corner of the overlap).
+ * Both methods conserve the integral over the grid when the outer edges of the two grids coincide.  The bits of a point do not depend
+ * on layout, strides, position in the call or number of fields in the call.
+ * SAFETY: the only data that reaches an address are table integers.  The kernel clamps each ptr value to [0, nnz], takes a
+ * non-increasing pair as zero terms, and clamps every cell and cell +- 1 to the source box: a corrupt table gives unspecified values,
+ * never an address outside the boxes the host has checked.  No loop bound depends on field data.
+ * Refusals: null pointers (h, c, den may be NULL for GT4MI_HREMAP_PCM), nfields < 1, nk < 1, ns < 1 or nd < 1, an unknown method or
+ * flag, nnz outside [nd, ns + nd - 1] (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a misaligned field or table array
+ * (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS); the bytes of a dst box (first to last item)
+ * meeting those of any src box, of another dst box or of any table array (GT4MI_ERR_UNSUPPORTED, the rule of gt4mi_field_copy).  No byte
+ * outside the dst boxes changes.  Every check runs before the first launch; a refused call enqueues nothing.  With
+ * GT4MI_HREMAP_DRY_RUN the checks run, *launches is set and no device is touched.  *launches (may be NULL) = the kernels the call
+ * enqueues: ceil(nfields / 8). */
+enum { GT4MI_HREMAP_PCM = 0, GT4MI_HREMAP_PLM = 1 };
+enum { GT4MI_HREMAP_DRY_RUN = 256 };
+int gt4mi_horizontal_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_overlap_axis* axis_i,
+                           const gt4mi_overlap_axis* axis_j, int64_t nk, int elem_size, int method, int flags, void* stream,
+                           int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
