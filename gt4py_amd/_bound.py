@@ -1,5 +1,5 @@
 """What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
-``vertical.VerticalRemap``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``) share on the Python side: turning a refusal of the library into an
+``vertical.VerticalRemap``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``linesolve.LineSolve``) share on the Python side: turning a refusal of the library into an
 exception, normalising halo / origin / domain / field lists, and binding a checked call to the caller's objects.  A new
 utility states what differs (its name in the messages, its extra fields) and takes the rest from here."""
 
@@ -79,15 +79,16 @@ def _box_of(first: DeviceArray, halo4, origin, domain, least: int):
     return origin, _triple(domain, "domain", 1)
 
 
-def _pair_lists(who: str, dst, src, halo, method=None, methods=None, shared=()):
+def _pair_lists(who: str, dst, src, halo, method=None, methods=None, shared=(), roles=("destination(s)", "source(s)")):
     """The opening of a call on (dst, src) pairs, in the order the checks have always had: two lists of equal length, a known
     ``method`` (where there are ``methods``), DeviceArrays of everything (``shared``: fields every pair reads), the halo.
+    ``roles``: what the length message calls the two lists.
     Returns (dsts, srcs, dst arrays, src arrays, shared arrays, halo4)."""
     dsts, srcs = _as_list(dst), _as_list(src)
     if not dsts or not srcs:
         raise ValueError(f"{who} needs at least one pair of fields")
     if len(dsts) != len(srcs):
-        raise ValueError(f"{who} pairs fields one to one: {len(dsts)} destination(s) and {len(srcs)} source(s) were passed")
+        raise ValueError(f"{who} pairs fields one to one: {len(dsts)} {roles[0]} and {len(srcs)} {roles[1]} were passed")
     if methods is not None and method not in methods:
         raise ValueError(f"method must be one of {sorted(methods)}, not {method!r}")
     d_arrays = [as_device_array(f) for f in dsts]

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_horizontal_interp",
     "gt4mi_overlap_table",
     "gt4mi_horizontal_remap",
+    "gt4mi_line_solve",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -117,6 +118,9 @@ INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC, INTERP_CUBIC_MONOTONE = 0, 1, 2, 3
 INTERP_RELATIVE, INTERP_DRY_RUN = 1, 256
 # gt4mi_horizontal_remap: methods, flags
 HREMAP_PCM, HREMAP_PLM, HREMAP_DRY_RUN = 0, 1, 256
+# gt4mi_line_solve: paths, flags
+LINE_PATH_LANES, LINE_PATH_TILES, LINE_PATH_ITEMS = 0, 1, 2
+LINE_PERIODIC, LINE_DRY_RUN = 1, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -241,6 +245,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     AP = ctypes.POINTER(OverlapAxis)
     lib.gt4mi_horizontal_remap.restype = I
     lib.gt4mi_horizontal_remap.argtypes = [FP, FP, I, AP, AP, ctypes.c_int64, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_line_solve.restype = I
+    lib.gt4mi_line_solve.argtypes = [FP, FP, I, FP, FP, FP, DOM, I, I, I, P, ctypes.c_int64, P, ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

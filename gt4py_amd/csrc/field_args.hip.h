@@ -1,5 +1,5 @@
 // Host-side helpers that the multi-field utility entries (halo_fill, field_stats, level_stats, field_copy, vertical_remap,
-// horizontal_interp, horizontal_remap) share: where a field's origin item is, which bytes its box touches, the per-field argument check and
+// horizontal_interp, horizontal_remap, line_solve) share: where a field's origin item is, which bytes its box touches, the per-field argument check and
 // the "no dst meets anything that is read" sweep.  What differs between the entries is DATA (BoxChecks, the arguments of
 // check_box_field): a new entry states its differences here instead of copying a check function.  The messages are part of
 // the library's behaviour (tests/test_refusal_messages.py holds them byte for byte).
@@ -81,20 +81,32 @@ struct NamedSpan {
     ByteSpan span;
 };
 
+// what check_pairs_disjoint takes from the entry where it differs from the default {"dst", "src", false}
+struct PairRoles {
+    const char* dst;  // what the messages call the written field of a pair ...
+    const char* src;  // ... and the read one
+    bool same_box;    // dst[n] may BE src[n]: the same first item and the same strides (an in-place call); any other meeting is refused
+};
+
 // No dst may meet a shared field, any src (its box grown by `src_grow`) or another dst: what makes one launch without ordering
 // between its workgroups correct.
 inline int check_pairs_disjoint(const char* entry, const gt4mi_field* dst, const gt4mi_field* src, int n, const int64_t dst_extent[3],
                                 const int64_t src_extent[3], int dsize, int ssize, const int64_t* src_grow = nullptr,
-                                const NamedSpan* shared = nullptr, int nshared = 0) {
+                                const NamedSpan* shared = nullptr, int nshared = 0, const PairRoles* roles = nullptr) {
+    const char* const dname = roles != nullptr ? roles->dst : "dst";
+    const char* const sname = roles != nullptr ? roles->src : "src";
     for (int a = 0; a < n; ++a) {
         const ByteSpan d = box_span(dst[a], dst_extent, dsize);
         for (int s = 0; s < nshared; ++s)
-            if (spans_overlap(d, shared[s].span)) return fail(GT4MI_ERR_UNSUPPORTED, "%s: dst %d and %s overlap in memory", entry, a, shared[s].name);
+            if (spans_overlap(d, shared[s].span))
+                return fail(GT4MI_ERR_UNSUPPORTED, "%s: %s %d and %s overlap in memory", entry, dname, a, shared[s].name);
         for (int b = 0; b < n; ++b) {
-            if (spans_overlap(d, box_span(src[b], src_extent, ssize, src_grow)))
-                return fail(GT4MI_ERR_UNSUPPORTED, "%s: dst %d and src %d overlap in memory", entry, a, b);
+            const bool same = roles != nullptr && roles->same_box && a == b && origin_ptr(dst[a]) == origin_ptr(src[a]) &&
+                              dst[a].stride[0] == src[a].stride[0] && dst[a].stride[1] == src[a].stride[1] && dst[a].stride[2] == src[a].stride[2];
+            if (!same && spans_overlap(d, box_span(src[b], src_extent, ssize, src_grow)))
+                return fail(GT4MI_ERR_UNSUPPORTED, "%s: %s %d and %s %d overlap in memory", entry, dname, a, sname, b);
             if (b > a && spans_overlap(d, box_span(dst[b], dst_extent, dsize)))
-                return fail(GT4MI_ERR_UNSUPPORTED, "%s: dst %d and dst %d overlap in memory", entry, a, b);
+                return fail(GT4MI_ERR_UNSUPPORTED, "%s: %s %d and %s %d overlap in memory", entry, dname, a, dname, b);
         }
     }
     return GT4MI_OK;

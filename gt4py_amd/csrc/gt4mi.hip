@@ -17,6 +17,7 @@
 #include "vertical_remap.hip.h"
 #include "horizontal_interp.hip.h"
 #include "horizontal_remap.hip.h"
+#include "line_solve.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -244,6 +245,13 @@ int gt4mi_horizontal_remap(const gt4mi_field* dst, const gt4mi_field* src, int n
                            int* launches) {
     return gt4mi::horizontal_remap(dst, src, nfields, axis_i, axis_j, nk, elem_size, method, flags, static_cast<hipStream_t>(stream),
                                    launches);
+}
+
+int gt4mi_line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfields, const gt4mi_field* lower, const gt4mi_field* diag,
+                     const gt4mi_field* upper, const int64_t extent[3], int axis, int elem_size, int flags, void* workspace,
+                     int64_t workspace_bytes, void* stream, int64_t* workspace_needed, int* path, int* launches) {
+    return gt4mi::line_solve(out, rhs, nfields, lower, diag, upper, extent, axis, elem_size, flags, workspace, workspace_bytes,
+                             static_cast<hipStream_t>(stream), workspace_needed, path, launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

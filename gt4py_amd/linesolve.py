@@ -1,0 +1,169 @@
+"""``gt4py_amd.linesolve`` -- tridiagonal solves along the lines of I, J or K, one kernel launch per 8 right-hand sides.
+
+GTScript iterates sequentially along K only, so a recurrence along I or J -- implicit horizontal diffusion, an ADI step, a compact
+finite difference, an implicit zonal filter, the line relaxation of a semi-implicit solver -- cannot be written as a stencil; the
+kernel library's one Thomas solve (``tridiagonal_solver``) is K only, takes one right-hand side, rewrites its coefficients and has
+no periodic closure.  ``gt4mi_line_solve`` (csrc/line_solve.hip.h) solves
+
+    a[m] x[m-1] + b[m] x[m] + c[m] x[m+1] = d[m],   m = 0 .. n-1
+
+for every line of the box along ``axis``, for up to eight (out, rhs) pairs per launch that share one set of coefficients, on the
+current stream, without synchronisation or allocation; the elimination factors of a line are formed once for all its fields.
+
+    from gt4py_amd import linesolve
+    linesolve.solve_lines(out, rhs, lower=a, diag=b, upper=c, axis="I")
+    solve = linesolve.LineSolve([u_new, v_new], [ru, rv], lower=a, diag=b, upper=c, axis="I", periodic=True)   # frozen
+    for step in range(steps):
+        build_rhs(u, v, ru, rv, ...)      # a stencil
+        solve()                           # one call on the current stream
+        physics(u_new, v_new, ...)
+
+The coefficients are never written.  ``out[n]`` may be ``rhs[n]`` itself (an in-place solve); nothing else may overlap.  With
+``periodic=True`` the line is closed (``a[0]`` couples point 0 to point n-1, ``c[n-1]`` point n-1 to point 0; n >= 3); without it
+``a[0]`` and ``c[n-1]`` are never read.  The arithmetic -- the fields' dtype throughout, its order fixed, no pivoting -- is part of
+the contract (include/gt4py_amd.h): the same line gives the same bits whatever the layout, the axis, the position in the call or
+the device.  A rank's block must hold whole lines along ``axis``; block-tridiagonal and pentadiagonal systems and mixed dtypes are
+out of scope.
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence
+
+from . import _lib
+from ._bound import FLOATS, Bound, _origin3, _pair_lists, raise_refusal, refuse_host_arrays
+from .storage.device_array import DeviceArray
+
+AXES = {"I": 0, "J": 1, "K": 2}
+PATHS = {_lib.LINE_PATH_LANES: "lanes", _lib.LINE_PATH_TILES: "tiles", _lib.LINE_PATH_ITEMS: "items"}
+COEFFICIENTS = ("lower", "diag", "upper")
+
+
+def _native(out, rhs, n: int, coefficients, extent, axis: int, size: int, flags: int, workspace, workspace_bytes: int, stream):
+    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
+    library's message.  Returns (workspace bytes needed, path, kernels enqueued)."""
+    needed, path, launches = ctypes.c_int64(0), ctypes.c_int(-1), ctypes.c_int(0)
+    lower, diag, upper = coefficients
+    rc = _lib.load().gt4mi_line_solve(out, rhs, n, ctypes.byref(lower), ctypes.byref(diag), ctypes.byref(upper), extent, axis, size, flags,
+                                      workspace, workspace_bytes, stream, ctypes.byref(needed), ctypes.byref(path), ctypes.byref(launches))
+    if rc != _lib.OK:
+        raise_refusal("gt4mi_line_solve", rc)
+    return needed.value, path.value, launches.value
+
+
+def _coefficient(a: DeviceArray, axis: int, start) -> "_lib.Field":
+    if a.ndim == 1:  # n items along the line axis: every line reads the same ones
+        shape, strides, origin = [1, 1, 1], [0, 0, 0], [0, 0, 0]
+        shape[axis], strides[axis] = a.shape[0], a.strides[0]
+        return _lib.Field.make(a.ptr, shape, strides, origin)
+    return _lib.Field.make(a.ptr, a.shape, a.strides, start)
+
+
+class LineSolve(Bound):
+    """The frozen form of :func:`solve_lines` (what ``FrozenStencil`` is for stencils): arguments are checked (through the
+    library's dry run), the native descriptors and the workspace built once, ``__call__()`` makes only the ctypes call, on the
+    stream that is current THEN.
+
+    ``n`` is the line length, ``lines`` the number of lines, ``extent`` the IJK box (the compute domain grown by the halo in I
+    and J), ``launches`` the kernels a call enqueues, ``path`` the kernel the strides select (``"lanes"``: lanes along a
+    unit-stride axis other than ``axis``; ``"tiles"``: ``axis`` is the unit-stride axis, tiles go through LDS; ``"items"``:
+    anything else, slow), ``workspace`` the :class:`DeviceArray` that holds the elimination factors: its layout is the library's,
+    and no result depends on what it held before a call.  The object holds raw pointers and weak references to the CALLER's
+    objects, not the arrays: it refuses to run once one of them has died."""
+
+    def __init__(self, out, rhs, *, lower, diag, upper, axis: str = "I", periodic: bool = False, halo=0,
+                 origin: Optional[Sequence[int]] = None):
+        outs, rhss, o_arrays, r_arrays, c_arrays, self._halo = _pair_lists("solve_lines", out, rhs, halo, shared=(lower, diag, upper),
+                                                                               roles=("out field(s)", "rhs field(s)"))
+        if axis not in AXES:
+            raise ValueError(f"axis must be one of {sorted(AXES)}, not {axis!r}")
+        self.axis, self.periodic = axis, bool(periodic)
+        ax = AXES[axis]
+        for a in o_arrays + r_arrays:
+            if a.ndim != 3:
+                raise ValueError(f"solve_lines takes IJK fields, not a field of {a.ndim} dimension(s)")
+        for name, a in zip(COEFFICIENTS, c_arrays):
+            if a.ndim not in (1, 3):
+                raise ValueError(f"{name} must be an IJK field or a 1-d array along {axis}, not a field of {a.ndim} dimension(s)")
+        dtype = o_arrays[0].dtype
+        for a in o_arrays + r_arrays + c_arrays:
+            if a.dtype != dtype:
+                raise TypeError(f"the fields and coefficients of one call share a dtype: {dtype} and {a.dtype} differ")
+        if dtype not in FLOATS:
+            raise TypeError(f"solve_lines takes float32 or float64 fields, not {dtype}")
+        lo_i, hi_i, lo_j, hi_j = self._halo
+        self.origin = origin = _origin3(origin, self._halo)
+        # the common compute domain: what every IJK array has left behind its origin and in front of its high ghost cells; along
+        # the line axis the arrays must agree, a line is never cut short silently
+        full = [a for a in o_arrays + r_arrays + c_arrays if a.ndim == 3]
+        rest = [tuple(s - o - h for s, o, h in zip(a.shape, origin, (hi_i, hi_j, 0))) for a in full]
+        domain = tuple(min(r[x] for r in rest) for x in range(3))
+        if min(domain) < 0 or domain[2] < 1:
+            raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in fields of shapes {[a.shape for a in full]}")
+        for r in rest:
+            if r[ax] != domain[ax]:
+                raise ValueError(f"the fields of one call share their length along {axis}: {domain[ax]} and {r[ax]} differ")
+        self.domain = domain
+        #: the IJK box that is solved: the domain grown by the halo in I and J
+        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j, domain[2])
+        #: the line length, and how many lines the box holds
+        self.n = self.extent[ax]
+        self.lines = self.extent[(ax + 1) % 3] * self.extent[(ax + 2) % 3]
+        for name, a in zip(COEFFICIENTS, c_arrays):
+            if a.ndim == 1 and a.shape[0] != self.n:
+                raise ValueError(f"{name} has {a.shape[0]} items, a line of {self.n} points along {axis} needs {self.n}")
+        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
+        self._n = len(o_arrays)
+        self._out, self._rhs = (_lib.Field * self._n)(), (_lib.Field * self._n)()
+        for table, arrays in ((self._out, o_arrays), (self._rhs, r_arrays)):
+            for n, a in enumerate(arrays):
+                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, start)
+        self._coefficients = tuple(_coefficient(a, ax, start) for a in c_arrays)
+        self._extent3 = _lib.domain3(self.extent)
+        self._axis, self._size = ax, o_arrays[0].itemsize
+        self._flags = _lib.LINE_PERIODIC if self.periodic else 0
+        # every check of the library, nothing enqueued; also: the workspace the call needs, its path and how many kernels it makes
+        needed, path, self.launches = _native(self._out, self._rhs, self._n, self._coefficients, self._extent3, ax, self._size,
+                                              self._flags | _lib.LINE_DRY_RUN, None, 0, None)
+        self.path = PATHS.get(path)
+        arrays = o_arrays + r_arrays + c_arrays
+        refuse_host_arrays("solve_lines", arrays)
+        import torch
+
+        first = o_arrays[0].tensor
+        #: the elimination factors of every line (and, for a periodic call, the closure's solution); private layout
+        self.workspace = DeviceArray(torch.empty(max(needed // self._size, 1), dtype=first.dtype, device=first.device))
+        self._workspace_bytes = needed
+        _native(self._out, self._rhs, self._n, self._coefficients, self._extent3, ax, self._size, self._flags | _lib.LINE_DRY_RUN,
+                self.workspace.ptr, needed, None)  # (the workspace against every field)
+        self._bind("solve_lines", arrays, outs + rhss + [lower, diag, upper])
+
+    def __call__(self) -> None:
+        self._check_alive()
+        lower, diag, upper = self._coefficients
+        rc = self._lib.gt4mi_line_solve(self._out, self._rhs, self._n, ctypes.byref(lower), ctypes.byref(diag), ctypes.byref(upper),
+                                        self._extent3, self._axis, self._size, self._flags, self.workspace.ptr, self._workspace_bytes,
+                                        self._current_stream().cuda_stream, None, None, None)
+        if rc != _lib.OK:
+            _lib.check("gt4mi_line_solve", rc)
+
+
+def solve_lines(out, rhs, *, lower, diag, upper, axis: str = "I", periodic: bool = False, halo=0,
+                origin: Optional[Sequence[int]] = None) -> None:
+    """Solve ``lower[m] x[m-1] + diag[m] x[m] + upper[m] x[m+1] = rhs[m]`` along every line of the compute domain (plus ``halo``
+    ghost cells in I and J) along ``axis``, in one kernel launch (per 8 pairs) on the current stream.
+
+    ``out``, ``rhs``  one field each or two sequences of equal length: IJK :class:`DeviceArray`\\ s of one dtype (float32 or
+                float64) or anything ``as_device_array`` accepts; every field may differ in address, strides and padding.
+                ``out[n]`` may be ``rhs[n]`` itself (in place); every other overlap is refused.
+    ``lower``, ``diag``, ``upper``  of the fields' dtype, never written: IJK fields, or 1-d arrays of n items along ``axis``
+                that every line shares (broadcast, not copied).
+    ``axis``    ``"I"``, ``"J"`` or ``"K"``.
+    ``periodic``  close the line: ``lower[0]`` couples point 0 to point n-1, ``upper[n-1]`` point n-1 to point 0; n >= 3.
+    ``halo``    an int, ``(hi, hj)`` or ``((lo_i, hi_i), (lo_j, hi_j))``, as for ``boundary.fill_halo``.
+    ``origin``  first compute-domain point of every IJK array, default ``(lo_i, lo_j, 0)``.
+
+    Allocates the workspace of the call; for a time loop build a :class:`LineSolve` once instead.  Raises ``ValueError`` /
+    ``TypeError`` (with the library's message) before any GPU work."""
+    LineSolve(out, rhs, lower=lower, diag=diag, upper=upper, axis=axis, periodic=periodic, halo=halo, origin=origin)()

@@ -441,6 +441,56 @@ int gt4mi_horizontal_remap(const gt4mi_field* dst, const gt4mi_field* src, int n
                            const gt4mi_overlap_axis* axis_j, int64_t nk, int elem_size, int method, int flags, void* stream,
                            int* launches);
 
+/* ---- tridiagonal line solves along I, J or K (NEW entry, additive: the ABI version stays 8; the reference has one Thomas solve, the
+ * K-only `tridiagonal_solver` stencil behind gt4mi_tridiag_*, which takes one right-hand side, rewrites its coefficients and has no
+ * periodic closure; GTScript cannot write a recurrence along I or J) ------------------------------------------------------------------
+ * For every line along `axis` (0 = I, 1 = J, 2 = K) of the box [origin, origin + extent) solves
+ *   a[m] x[m-1] + b[m] x[m] + c[m] x[m+1] = d[m],  m = 0 .. n-1,  n = extent[axis],
+ * with a = lower, b = diag, c = upper, d = rhs[k], x = out[k], for `nfields` (out, rhs) pairs that share ONE set of coefficients, in
+ * ONE kernel launch per 8 pairs, on `stream`, without synchronisation or allocation; the elimination factors of a line are formed
+ * once for all its right-hand sides.  `elem_size` is 4 (float32) or 8 (float64) and is the item size of EVERY field.  The
+ * coefficients are never written.  A coefficient may have byte stride 0 along the two axes other than `axis`: a 1-d array of n
+ * items that every line shares broadcasts without a copy and is exempt from the shape check on those axes.  A rhs stride of 0
+ * broadcasts too; an out stride of 0 on an extent above 1 is GT4MI_ERR_INVALID_ARGUMENT.
+ * out[k] may BE rhs[k] -- the same first item and the same strides: an in-place solve.  Every other meeting of the bytes of an out box
+ * (first to last item) with a rhs box, another out box or a coefficient, and of any field with the workspace, is refused.
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/line_solve.hip.h states it again, tests/line_solve_ref.py restates it in plain Python).
+ * All of it is in the fields' type, one IEEE rounding per operation, no FMA; division is IEEE division, there is no reciprocal.
+ * Without GT4MI_LINE_PERIODIC (a[0] and c[n-1] are never read):
+ *   m = 0 :  cp[0] = c[0] / b[0]                     dp[0] = d[0] / b[0]
+ *   m >= 1:  den = b[m] - a[m] * cp[m-1]
+ *            cp[m] = c[m] / den   (not for m = n-1)  dp[m] = (d[m] - a[m] * dp[m-1]) / den
+ *   x[n-1] = dp[n-1] ;  x[m] = dp[m] - cp[m] * x[m+1]   for m = n-2 .. 0
+ * which is the arithmetic of gt4mi_tridiag_*: one right-hand side gives the bits of that solve on the permuted data.
+ * With GT4MI_LINE_PERIODIC the line is closed: a[0] couples point 0 to point n-1, c[n-1] couples point n-1 to point 0; n >= 3.
+ * Sherman-Morrison with alpha = c[n-1], beta = a[0], gamma = -b[0]:
+ *   bb[0] = b[0] - gamma ;  bb[n-1] = b[n-1] - (alpha * beta) / gamma ;  bb[m] = b[m] otherwise
+ *   q = the solution of the non-periodic system with diagonal bb and right-hand side (gamma, 0, ..., 0, alpha)   [once per line]
+ *   y = the solution of the same system with right-hand side d                                                   [per field]
+ *   fact = (y[0] + (beta * y[n-1]) / gamma) / ((1 + q[0]) + (beta * q[n-1]) / gamma)
+ *   x[m] = y[m] - fact * q[m]
+ * The elimination of the periodic system reads c[n-1] only as alpha, cp[n-1] is not formed; the zeros of q's right-hand side take
+ * part as written (0 - a[m] * qp[m-1]).  No pivoting.  Every loop counts to n; no loop bound and no address depends on field data: a
+ * zero or NaN pivot gives its line what IEEE arithmetic gives and changes nothing in any other line.
+ * `workspace` holds the elimination factors (and q): its layout is private to the library, its size depends on extent, axis,
+ * elem_size and flags and is reported in *workspace_needed (may be NULL); it is aligned to 8 bytes; the result never depends on what
+ * it held before the call.  No byte outside the out boxes and the workspace is written.
+ * *path (may be NULL) = which kernel the strides of the call select: GT4MI_LINE_PATH_LANES (an axis other than `axis` has unit stride
+ * in every field: lanes along it, every step a coalesced row), GT4MI_LINE_PATH_TILES (`axis` itself has unit stride in every field: a
+ * lane owns a line, tiles of 64 lines x 128 bytes go through LDS), GT4MI_LINE_PATH_ITEMS (anything else: one lane per line, item by
+ * item, correct and slow).  The bits do not depend on the path.
+ * Refusals: null pointers, nfields < 1, an invalid extent or axis, an unknown flag, a periodic line of fewer than 3 points, a
+ * workspace that is too small (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a misaligned field or workspace, a
+ * forbidden overlap (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS).  An extent with a zero
+ * entry is GT4MI_OK, nothing enqueued.  Every check runs before the first launch; a refused call enqueues nothing.  With
+ * GT4MI_LINE_DRY_RUN the checks run, *workspace_needed, *path and *launches are set and no device is touched; `workspace` may then
+ * be NULL (a workspace that is passed is checked).  *launches (may be NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_LINE_PATH_LANES = 0, GT4MI_LINE_PATH_TILES = 1, GT4MI_LINE_PATH_ITEMS = 2 };
+enum { GT4MI_LINE_PERIODIC = 1, GT4MI_LINE_DRY_RUN = 256 };
+int gt4mi_line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfields, const gt4mi_field* lower, const gt4mi_field* diag,
+                     const gt4mi_field* upper, const int64_t extent[3], int axis, int elem_size, int flags, void* workspace,
+                     int64_t workspace_bytes, void* stream, int64_t* workspace_needed, int* path, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
