@@ -18,6 +18,8 @@
 // (in, coeff read; out written), 2*sizeof(T) with a scalar coefficient.
 #pragma once
 
+#include <type_traits>
+
 #include "common.hip.h"
 
 #pragma clang fp contract(off)
@@ -134,16 +136,58 @@ inline int hdiff_launch(const View<const T>& in, const View<T>& out, const View<
     return GT4MI_OK;
 }
 
-template <typename T, typename W, typename PW>
-inline int hdiff_dispatch(const View<const T>& in, const View<T>& out, const View<const T>& cf,
-                          bool coeff_field, PW coeff_scalar, bool limiter, const int64_t d[3],
-                          hipStream_t stream, bool point_per_thread = false) {
-    if (limiter) {
-        if (coeff_field) return hdiff_launch<T, W, PW, true, true>(in, out, cf, coeff_scalar, d, stream, point_per_thread);
-        return hdiff_launch<T, W, PW, true, false>(in, out, cf, coeff_scalar, d, stream, point_per_thread);
+// ---- argument preparation shared by hdiff_run and hdiff_ring_run (hdiff_ring.hip.h) ------------------------------------------
+template <typename T>
+struct HdiffViews {
+    View<const T> in;
+    View<T> out;
+    View<const T> cf;  // p == nullptr: scalar coefficient
+    bool alias;        // out_field IS coeff: a point's coefficient is read before that point is written
+};
+
+// The three views on a (checked) domain and the two overlap rules: in / out must not overlap (`overlap`: what that is refused
+// with), coeff / out only as the same elements.  An empty domain touches nothing: no overlap is looked for, the caller returns.
+template <typename T>
+inline int hdiff_views(const int64_t domain[3], const gt4mi_field* in_field, const gt4mi_field* out_field, const gt4mi_field* coeff,
+                       const char* overlap, HdiffViews<T>* v) {
+    const int h2[3] = {2, 2, 0}, h0[3] = {0, 0, 0};
+    View<T> in_v, cf_v{nullptr, 0, 0, 0};
+    if (int rc = make_view<T>("in_field", in_field, domain, h2, h2, &in_v)) return rc;
+    if (int rc = make_view<T>("out_field", out_field, domain, h0, h0, &v->out)) return rc;
+    if (coeff != nullptr)
+        if (int rc = make_view<T>("coeff", coeff, domain, h0, h0, &cf_v)) return rc;
+    v->in = View<const T>{in_v.p, in_v.si, in_v.sj, in_v.sk};
+    v->cf = View<const T>{cf_v.p, cf_v.si, cf_v.sj, cf_v.sk};
+    v->alias = false;
+    if (domain[0] == 0 || domain[1] == 0 || domain[2] == 0) return GT4MI_OK;
+    if (views_overlap(in_v, h2, h2, v->out, h0, h0, domain)) return fail(GT4MI_ERR_UNSUPPORTED, "%s", overlap);
+    if (coeff != nullptr && views_overlap(cf_v, h0, h0, v->out, h0, h0, domain)) {
+        if (!same_view(cf_v, v->out))
+            return fail(GT4MI_ERR_UNSUPPORTED, "hdiff: 'coeff' and 'out_field' overlap in memory without being the same elements");
+        v->alias = true;
     }
-    if (coeff_field) return hdiff_launch<T, W, PW, false, true>(in, out, cf, coeff_scalar, d, stream, point_per_thread);
-    return hdiff_launch<T, W, PW, false, false>(in, out, cf, coeff_scalar, d, stream, point_per_thread);
+    return GT4MI_OK;
+}
+
+// `flags`, the kind of coefficient and its scalar value, resolved by the dtype rules at the top of this file:
+// f(W(), the scalar as PW, std::bool_constant<LIMITER>(), std::bool_constant<COEFF_FIELD>()) -> return code.
+template <typename T, typename F>
+inline int hdiff_with_types(int flags, bool coeff_field, double coeff_scalar, F&& f) {
+    const bool limiter = (flags & GT4MI_HDIFF_LIMITER) != 0;
+    const bool c32 = (flags & GT4MI_HDIFF_COEFF_F32) != 0;
+    auto kinds = [&](auto w, auto scalar) {
+        if (limiter) {
+            if (coeff_field) return f(w, scalar, std::true_type(), std::true_type());
+            return f(w, scalar, std::true_type(), std::false_type());
+        }
+        if (coeff_field) return f(w, scalar, std::false_type(), std::true_type());
+        return f(w, scalar, std::false_type(), std::false_type());
+    };
+    using N = typename std::conditional<sizeof(T) == 4, float, double>::type;  // narrower internals: only 4-byte fields have any
+    const bool w32 = sizeof(T) == 4 && (flags & GT4MI_HDIFF_INTERNAL_F32) != 0;
+    if (!w32) return kinds(double(), c32 ? (double)(float)coeff_scalar : coeff_scalar);
+    if (coeff_field || c32) return kinds(N(), (N)coeff_scalar);
+    return kinds(N(), coeff_scalar);
 }
 
 template <typename T>
@@ -151,45 +195,19 @@ inline int hdiff_run(const int64_t domain[3], const gt4mi_field* in_field,
                      const gt4mi_field* out_field, const gt4mi_field* coeff, double coeff_scalar,
                      int flags, hipStream_t stream) {
     if (int rc = check_domain(domain)) return rc;
-    const int h2[3] = {2, 2, 0}, h0[3] = {0, 0, 0};
-    View<T> in_v, out_v, cf_v{nullptr, 0, 0, 0};
-    if (int rc = make_view<T>("in_field", in_field, domain, h2, h2, &in_v)) return rc;
-    if (int rc = make_view<T>("out_field", out_field, domain, h0, h0, &out_v)) return rc;
-    if (coeff != nullptr)
-        if (int rc = make_view<T>("coeff", coeff, domain, h0, h0, &cf_v)) return rc;
+    HdiffViews<T> v;
+    if (int rc = hdiff_views<T>(domain, in_field, out_field, coeff,
+                                "hdiff: 'in_field' and 'out_field' overlap in memory; every point reads its neighbours' OLD values "
+                                "(the reference evaluates the right-hand side before it assigns), which an in-place kernel cannot "
+                                "provide -- pass a separate output array",
+                                &v))
+        return rc;
     if (domain[0] == 0 || domain[1] == 0 || domain[2] == 0) return GT4MI_OK;
-    if (views_overlap(in_v, h2, h2, out_v, h0, h0, domain))
-        return fail(GT4MI_ERR_UNSUPPORTED,
-                    "hdiff: 'in_field' and 'out_field' overlap in memory; every point reads its neighbours' OLD values "
-                    "(the reference evaluates the right-hand side before it assigns), which an in-place kernel cannot "
-                    "provide -- pass a separate output array");
-    bool alias = false;  // out_field IS coeff: a point's coefficient is read before that point is written
-    if (coeff != nullptr && views_overlap(cf_v, h0, h0, out_v, h0, h0, domain)) {
-        if (!same_view(cf_v, out_v))
-            return fail(GT4MI_ERR_UNSUPPORTED, "hdiff: 'coeff' and 'out_field' overlap in memory without being the same elements");
-        alias = true;
-    }
-    const View<const T> in_c{in_v.p, in_v.si, in_v.sj, in_v.sk};
-    const View<const T> cf_c{cf_v.p, cf_v.si, cf_v.sj, cf_v.sk};
-    const bool limiter = (flags & GT4MI_HDIFF_LIMITER) != 0;
-    const bool has_field = coeff != nullptr;
-    int rc;
-    if constexpr (sizeof(T) == 8) {
-        double cs = (flags & GT4MI_HDIFF_COEFF_F32) ? (double)(float)coeff_scalar : coeff_scalar;
-        rc = hdiff_dispatch<T, double, double>(in_c, out_v, cf_c, has_field, cs, limiter, domain, stream, alias);
-    } else {
-        const bool w32 = (flags & GT4MI_HDIFF_INTERNAL_F32) != 0;
-        const bool c32 = (flags & GT4MI_HDIFF_COEFF_F32) != 0;
-        if (!w32) {
-            double cs = c32 ? (double)(float)coeff_scalar : coeff_scalar;
-            rc = hdiff_dispatch<T, double, double>(in_c, out_v, cf_c, has_field, cs, limiter, domain, stream, alias);
-        } else if (has_field || c32) {
-            rc = hdiff_dispatch<T, float, float>(in_c, out_v, cf_c, has_field, (float)coeff_scalar, limiter, domain, stream, alias);
-        } else {
-            rc = hdiff_dispatch<T, float, double>(in_c, out_v, cf_c, has_field, coeff_scalar, limiter, domain, stream, alias);
-        }
-    }
-    if (rc) return rc;
+    if (int rc = hdiff_with_types<T>(flags, coeff != nullptr, coeff_scalar, [&](auto w, auto scalar, auto limiter, auto field) {
+            return hdiff_launch<T, decltype(w), decltype(scalar), decltype(limiter)::value, decltype(field)::value>(
+                v.in, v.out, v.cf, scalar, domain, stream, v.alias);
+        }))
+        return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
     return GT4MI_OK;
 }

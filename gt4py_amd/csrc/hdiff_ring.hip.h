@@ -187,18 +187,6 @@ inline int hdiff_launch_ring(const View<const T>& in, const View<T>& out, const 
     return GT4MI_OK;
 }
 
-template <typename T, typename W, typename PW>
-inline int hdiff_ring_dispatch(const View<const T>& in, const View<T>& out, const View<const T>& cf, bool coeff_field,
-                               PW coeff_scalar, bool limiter, const int64_t d[3], const int widths[4], hipStream_t stream,
-                               bool point_per_thread) {
-    if (limiter) {
-        if (coeff_field) return hdiff_launch_ring<T, W, PW, true, true>(in, out, cf, coeff_scalar, d, widths, stream, point_per_thread);
-        return hdiff_launch_ring<T, W, PW, true, false>(in, out, cf, coeff_scalar, d, widths, stream, point_per_thread);
-    }
-    if (coeff_field) return hdiff_launch_ring<T, W, PW, false, true>(in, out, cf, coeff_scalar, d, widths, stream, point_per_thread);
-    return hdiff_launch_ring<T, W, PW, false, false>(in, out, cf, coeff_scalar, d, widths, stream, point_per_thread);
-}
-
 // The ring of `domain` (widths towards W, E, S, N; each 0 or <= the domain) -- same argument rules as hdiff_run.
 template <typename T>
 inline int hdiff_ring_run(const int64_t domain[3], const gt4mi_field* in_field, const gt4mi_field* out_field,
@@ -209,42 +197,15 @@ inline int hdiff_ring_run(const int64_t domain[3], const gt4mi_field* in_field, 
         widths[2] + widths[3] > domain[1])
         return fail(GT4MI_ERR_INVALID_ARGUMENT, "hdiff ring: widths (%d, %d, %d, %d) do not fit the %lld x %lld domain", widths[0],
                     widths[1], widths[2], widths[3], (long long)domain[0], (long long)domain[1]);
-    const int h2[3] = {2, 2, 0}, h0[3] = {0, 0, 0};
-    View<T> in_v, out_v, cf_v{nullptr, 0, 0, 0};
-    if (int rc = make_view<T>("in_field", in_field, domain, h2, h2, &in_v)) return rc;
-    if (int rc = make_view<T>("out_field", out_field, domain, h0, h0, &out_v)) return rc;
-    if (coeff != nullptr)
-        if (int rc = make_view<T>("coeff", coeff, domain, h0, h0, &cf_v)) return rc;
+    HdiffViews<T> v;
+    if (int rc = hdiff_views<T>(domain, in_field, out_field, coeff, "hdiff: 'in_field' and 'out_field' overlap in memory (see gt4mi_hdiff_*)", &v))
+        return rc;
     if (domain[0] == 0 || domain[1] == 0 || domain[2] == 0) return GT4MI_OK;
-    if (views_overlap(in_v, h2, h2, out_v, h0, h0, domain))
-        return fail(GT4MI_ERR_UNSUPPORTED, "hdiff: 'in_field' and 'out_field' overlap in memory (see gt4mi_hdiff_*)");
-    bool alias = false;  // out_field IS coeff (see hdiff_run)
-    if (coeff != nullptr && views_overlap(cf_v, h0, h0, out_v, h0, h0, domain)) {
-        if (!same_view(cf_v, out_v))
-            return fail(GT4MI_ERR_UNSUPPORTED, "hdiff: 'coeff' and 'out_field' overlap in memory without being the same elements");
-        alias = true;
-    }
-    const View<const T> in_c{in_v.p, in_v.si, in_v.sj, in_v.sk};
-    const View<const T> cf_c{cf_v.p, cf_v.si, cf_v.sj, cf_v.sk};
-    const bool limiter = (flags & GT4MI_HDIFF_LIMITER) != 0;
-    const bool has_field = coeff != nullptr;
-    int rc;
-    if constexpr (sizeof(T) == 8) {
-        const double cs = (flags & GT4MI_HDIFF_COEFF_F32) ? (double)(float)coeff_scalar : coeff_scalar;
-        rc = hdiff_ring_dispatch<T, double, double>(in_c, out_v, cf_c, has_field, cs, limiter, domain, widths, stream, alias);
-    } else {
-        const bool w32 = (flags & GT4MI_HDIFF_INTERNAL_F32) != 0;
-        const bool c32 = (flags & GT4MI_HDIFF_COEFF_F32) != 0;
-        if (!w32) {
-            const double cs = c32 ? (double)(float)coeff_scalar : coeff_scalar;
-            rc = hdiff_ring_dispatch<T, double, double>(in_c, out_v, cf_c, has_field, cs, limiter, domain, widths, stream, alias);
-        } else if (has_field || c32) {
-            rc = hdiff_ring_dispatch<T, float, float>(in_c, out_v, cf_c, has_field, (float)coeff_scalar, limiter, domain, widths, stream, alias);
-        } else {
-            rc = hdiff_ring_dispatch<T, float, double>(in_c, out_v, cf_c, has_field, coeff_scalar, limiter, domain, widths, stream, alias);
-        }
-    }
-    if (rc) return rc;
+    if (int rc = hdiff_with_types<T>(flags, coeff != nullptr, coeff_scalar, [&](auto w, auto scalar, auto limiter, auto field) {
+            return hdiff_launch_ring<T, decltype(w), decltype(scalar), decltype(limiter)::value, decltype(field)::value>(
+                v.in, v.out, v.cf, scalar, domain, widths, stream, v.alias);
+        }))
+        return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
     return GT4MI_OK;
 }

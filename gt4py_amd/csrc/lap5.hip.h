@@ -16,6 +16,8 @@
 // Tuning data: profiles/r1_microbench_*.log (LJ, block size, nt loads/stores, XCD order).
 #pragma once
 
+#include <type_traits>
+
 #include "common.hip.h"
 #include "lane_shift.hip.h"
 
@@ -163,19 +165,6 @@ lap5_strip_kernel(View<const T> in, View<T> out, int dI, int dJ, unsigned tiles_
     lap5_strip_tile<T, W, VARIANT, VEC, LJ, BLOCK, MASKED>(in, out, dI, dJ, bx, (int)by * LJ, k, c_lo);
 }
 
-// Up to two single J rows (row_a, row_b) of every level in ONE launch: the boundary strips of a
-// J-decomposed domain, which wait for the halo exchange (gt4mi_dist_lap5_f64).
-template <typename T, typename W, int VARIANT, int VEC, int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
-lap5_rows_kernel(View<const T> in, View<T> out, int dI, int row_a, int row_b, unsigned tiles_x, unsigned nrows) {
-    const unsigned b = blockIdx.x;
-    const unsigned bx = b % tiles_x;
-    const unsigned r = (b / tiles_x) % nrows;
-    const unsigned k = b / (tiles_x * nrows);
-    const int j = r == 0 ? row_a : row_b;
-    lap5_strip_tile<T, W, VARIANT, VEC, 1, BLOCK>(in, out, dI, j + 1, bx, j, k);
-}
-
 // Any-stride fallback: one thread per point, I fastest across lanes.  Correct for every layout the
 // reference accepts (stencil_object.py:412-425 only warns about non-optimal layouts).
 template <typename T, typename W, int VARIANT>
@@ -222,6 +211,10 @@ inline int lap5_launch_strip_masked(const View<const T>& in, const View<T>& out,
     return GT4MI_OK;
 }
 
+// Lanes per strip tile for rows of `lanes_per_row` lanes: a row of up to 64 / 128 lanes gets tiles of one / two waves, so that no
+// workgroup carries waves that lie past the end of the row; anything wider gets the 256 lanes the kernels were tuned with.
+inline int lap5_tile_lanes(int64_t lanes_per_row) { return lanes_per_row <= 64 ? 64 : (lanes_per_row <= 128 ? 128 : 256); }
+
 template <typename T, typename W, int VARIANT>
 inline int lap5_launch_variant(const View<const T>& in, const View<T>& out, const int64_t d[3],
                                hipStream_t stream) {
@@ -230,9 +223,9 @@ inline int lap5_launch_variant(const View<const T>& in, const View<T>& out, cons
     if (in.si == 1 && out.si == 1 && d[0] >= 16) {
         const bool vec = vec_ok(in, VMAX) && vec_ok(out, VMAX) && (d[0] % VMAX == 0);
         if (vec) {
-            const int64_t lanes = d[0] / VMAX;
-            if (lanes <= 64) return lap5_launch_strip<T, W, VARIANT, VMAX, 64>(in, out, d, stream);
-            if (lanes <= 128) return lap5_launch_strip<T, W, VARIANT, VMAX, 128>(in, out, d, stream);
+            const int block = lap5_tile_lanes(d[0] / VMAX);
+            if (block == 64) return lap5_launch_strip<T, W, VARIANT, VMAX, 64>(in, out, d, stream);
+            if (block == 128) return lap5_launch_strip<T, W, VARIANT, VMAX, 128>(in, out, d, stream);
             return lap5_launch_strip<T, W, VARIANT, VMAX, 256>(in, out, d, stream);
         }
         {
@@ -247,8 +240,9 @@ inline int lap5_launch_variant(const View<const T>& in, const View<T>& out, cons
             const bool same = lead == (int)((reinterpret_cast<uintptr_t>(out.p) % unit) / sizeof(T));
             if (same && in.sj % VM == 0 && in.sk % VM == 0 && out.sj % VM == 0 && out.sk % VM == 0) {
                 const int64_t lanes = cdiv(d[0] + lead, VM);
-                if (lanes <= 64) return lap5_launch_strip_masked<T, W, VARIANT, VM, 64>(in, out, d, lead, stream);
-                if (lanes <= 128) return lap5_launch_strip_masked<T, W, VARIANT, VM, 128>(in, out, d, lead, stream);
+                const int block = lap5_tile_lanes(lanes);
+                if (block == 64) return lap5_launch_strip_masked<T, W, VARIANT, VM, 64>(in, out, d, lead, stream);
+                if (block == 128) return lap5_launch_strip_masked<T, W, VARIANT, VM, 128>(in, out, d, lead, stream);
                 // one lane more than the aligned domain needs (512 columns from an odd origin: 257 lanes) must not cost a
                 // second, almost empty workgroup per row: five waves instead of four where that wastes fewer lanes
                 if (cdiv(lanes, 320) * 320 < cdiv(lanes, 256) * 256)
@@ -266,81 +260,84 @@ inline int lap5_launch_variant(const View<const T>& in, const View<T>& out, cons
     return GT4MI_OK;
 }
 
+// ---- argument preparation shared by every host entry of the family (this file, lap5_ring / lap5_push / lap5_edge.hip.h) ------
+template <typename T>
+inline View<const T> const_view(const View<T>& v) { return View<const T>{v.p, v.si, v.sj, v.sk}; }
+
+inline bool empty_domain(const int64_t d[3]) { return d[0] == 0 || d[1] == 0 || d[2] == 0; }
+
+// What the forms built on gt4mi_lap5_* refuse an overlap with; gt4mi_lap5_* itself says why (lap5_run).
+constexpr const char* LAP5_OVERLAP_SEE = "lap5: 'inp' and 'out' overlap in memory (see gt4mi_lap5_*)";
+
+// `inp` is read `reach` points beyond `domain` along I and J, `out` is written on `domain`: may a written element be a read one?
+template <typename T>
+inline int lap5_refuse_overlap(const View<T>& in_v, const View<T>& out_v, const int64_t domain[3], int reach, const char* message) {
+    const int h[3] = {reach, reach, 0}, h0[3] = {0, 0, 0};
+    return views_overlap(in_v, h, h, out_v, h0, h0, domain) ? fail(GT4MI_ERR_UNSUPPORTED, "%s", message) : GT4MI_OK;
+}
+
+// The views of `inp` and `out` on a (checked) domain.  `overlap` is what an overlap of the two is refused with; nullptr: not tested
+// here -- the caller does it later (lap5_run: behind its empty-domain return; lap5_step_run) or has done it on a larger domain.
+template <typename T>
+inline int lap5_views(const int64_t domain[3], const gt4mi_field* inp, const gt4mi_field* outf, int reach, const char* overlap,
+                      View<T>* in_v, View<T>* out_v) {
+    const int h[3] = {reach, reach, 0}, h0[3] = {0, 0, 0};
+    if (int rc = make_view<T>("inp", inp, domain, h, h, in_v)) return rc;
+    if (int rc = make_view<T>("out", outf, domain, h0, h0, out_v)) return rc;
+    return overlap ? lap5_refuse_overlap(*in_v, *out_v, domain, reach, overlap) : GT4MI_OK;
+}
+
+// The run-time `variant` as a compile-time constant: f(std::integral_constant<int, GT4MI_LAP_*>{}) -> return code.
+template <typename F>
+inline int lap5_with_variant(int variant, F&& f) {
+    switch (variant) {
+        case GT4MI_LAP_NOTEBOOK: return f(std::integral_constant<int, GT4MI_LAP_NOTEBOOK>{});
+        case GT4MI_LAP_DOCS: return f(std::integral_constant<int, GT4MI_LAP_DOCS>{});
+        case GT4MI_LAP_SUITE: return f(std::integral_constant<int, GT4MI_LAP_SUITE>{});
+        case GT4MI_LAP_AVG: return f(std::integral_constant<int, GT4MI_LAP_AVG>{});
+        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
+    }
+}
+
+// The interior of a distributed step on whole 16-byte lanes, inside a launch that holds other work too (lap5_push / lap5_edge
+// .hip.h): the strips of lap5_strip_kernel, `tpb` tiles of lap5_tile_lanes lanes to a 256-thread workgroup.
+struct Lap5InteriorTiling {
+    int tpb;           // tiles per workgroup: 4 / 2 / 1
+    unsigned tx, ty;   // tiles along I and J of one level
+    int64_t tiles;     // of all levels
+    int64_t interior;  // workgroups
+};
+
+template <typename T>
+inline Lap5InteriorTiling lap5_interior_tiling(int64_t di, int64_t rows, int64_t dk) {
+    constexpr int VMAX = 16 / (int)sizeof(T);
+    Lap5InteriorTiling t;
+    const int lanes = lap5_tile_lanes(di / VMAX);
+    t.tpb = 256 / lanes;
+    t.tx = (unsigned)cdiv(di, (int64_t)lanes * VMAX);
+    t.ty = (unsigned)cdiv(rows > 0 ? rows : 0, (int64_t)Lap5Tuning::LJ);
+    t.tiles = (int64_t)t.tx * t.ty * dk;
+    t.interior = cdiv(t.tiles, (int64_t)t.tpb);
+    return t;
+}
+
 template <typename T, typename W>
 inline int lap5_run(const int64_t domain[3], const gt4mi_field* inp, const gt4mi_field* outf,
                     int variant, hipStream_t stream) {
     if (int rc = check_domain(domain)) return rc;
-    const int h1[3] = {1, 1, 0}, h0[3] = {0, 0, 0};
     View<T> in_v, out_v;
-    if (int rc = make_view<T>("inp", inp, domain, h1, h1, &in_v)) return rc;
-    if (int rc = make_view<T>("out", outf, domain, h0, h0, &out_v)) return rc;
-    if (domain[0] == 0 || domain[1] == 0 || domain[2] == 0) return GT4MI_OK;
-    if (views_overlap(in_v, h1, h1, out_v, h0, h0, domain))
-        return fail(GT4MI_ERR_UNSUPPORTED,
-                    "lap5: 'inp' and 'out' overlap in memory; every point reads its neighbours' OLD values (the "
-                    "reference evaluates the right-hand side before it assigns), which an in-place kernel cannot "
-                    "provide -- pass a separate output array");
-    View<const T> in_c{in_v.p, in_v.si, in_v.sj, in_v.sk};
-    int rc;
-    switch (variant) {
-        case GT4MI_LAP_NOTEBOOK: rc = lap5_launch_variant<T, W, GT4MI_LAP_NOTEBOOK>(in_c, out_v, domain, stream); break;
-        case GT4MI_LAP_DOCS: rc = lap5_launch_variant<T, W, GT4MI_LAP_DOCS>(in_c, out_v, domain, stream); break;
-        case GT4MI_LAP_SUITE: rc = lap5_launch_variant<T, W, GT4MI_LAP_SUITE>(in_c, out_v, domain, stream); break;
-        case GT4MI_LAP_AVG: rc = lap5_launch_variant<T, W, GT4MI_LAP_AVG>(in_c, out_v, domain, stream); break;
-        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
-    }
-    if (rc) return rc;
+    if (int rc = lap5_views<T>(domain, inp, outf, 1, nullptr, &in_v, &out_v)) return rc;
+    if (empty_domain(domain)) return GT4MI_OK;
+    if (int rc = lap5_refuse_overlap(in_v, out_v, domain, 1,
+                                     "lap5: 'inp' and 'out' overlap in memory; every point reads its neighbours' OLD values (the "
+                                     "reference evaluates the right-hand side before it assigns), which an in-place kernel cannot "
+                                     "provide -- pass a separate output array"))
+        return rc;
+    if (int rc = lap5_with_variant(variant, [&](auto v) {
+            return lap5_launch_variant<T, W, decltype(v)::value>(const_view(in_v), out_v, domain, stream);
+        }))
+        return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
-    return GT4MI_OK;
-}
-
-// Rows row_a (and row_b when nrows == 2) of the compute domain, all K levels, in one launch.
-// Falls back to per-row lap5_run calls when the fields do not qualify for the vector path.
-template <typename T, typename W, int VARIANT>
-inline int lap5_rows_variant(const View<const T>& in, const View<T>& out, const int64_t d[3], int row_a, int row_b,
-                             int nrows, hipStream_t stream, bool* done) {
-    constexpr int VMAX = 16 / sizeof(T);
-    *done = false;
-    if (!(in.si == 1 && out.si == 1 && vec_ok(in, VMAX) && vec_ok(out, VMAX) && d[0] % VMAX == 0)) return GT4MI_OK;
-    const unsigned tx = (unsigned)cdiv(d[0], (int64_t)256 * VMAX);
-    hipLaunchKernelGGL((lap5_rows_kernel<T, W, VARIANT, VMAX, 256>), dim3(tx * (unsigned)nrows * (unsigned)d[2]), dim3(256), 0,
-                       stream, in, out, (int)d[0], row_a, row_b, tx, (unsigned)nrows);
-    *done = true;
-    return GT4MI_OK;
-}
-
-template <typename T, typename W>
-inline int lap5_run_rows(const int64_t domain[3], const gt4mi_field* inp, const gt4mi_field* outf, int variant,
-                         int row_a, int row_b, int nrows, hipStream_t stream) {
-    if (nrows <= 0 || domain[0] <= 0 || domain[2] <= 0) return GT4MI_OK;
-    if (int rc = check_domain(domain)) return rc;
-    const int h1[3] = {1, 1, 0}, h0[3] = {0, 0, 0};
-    View<T> in_v, out_v;
-    if (int rc = make_view<T>("inp", inp, domain, h1, h1, &in_v)) return rc;
-    if (int rc = make_view<T>("out", outf, domain, h0, h0, &out_v)) return rc;
-    if (views_overlap(in_v, h1, h1, out_v, h0, h0, domain))
-        return fail(GT4MI_ERR_UNSUPPORTED, "lap5: 'inp' and 'out' overlap in memory (see gt4mi_lap5_*)");
-    View<const T> in_c{in_v.p, in_v.si, in_v.sj, in_v.sk};
-    bool done = false;
-    switch (variant) {
-        case GT4MI_LAP_NOTEBOOK: lap5_rows_variant<T, W, GT4MI_LAP_NOTEBOOK>(in_c, out_v, domain, row_a, row_b, nrows, stream, &done); break;
-        case GT4MI_LAP_DOCS: lap5_rows_variant<T, W, GT4MI_LAP_DOCS>(in_c, out_v, domain, row_a, row_b, nrows, stream, &done); break;
-        case GT4MI_LAP_SUITE: lap5_rows_variant<T, W, GT4MI_LAP_SUITE>(in_c, out_v, domain, row_a, row_b, nrows, stream, &done); break;
-        case GT4MI_LAP_AVG: lap5_rows_variant<T, W, GT4MI_LAP_AVG>(in_c, out_v, domain, row_a, row_b, nrows, stream, &done); break;
-        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
-    }
-    if (done) {
-        GT4MI_HIP_CHECK(hipGetLastError());
-        return GT4MI_OK;
-    }
-    for (int r = 0; r < nrows; ++r) {  // generic layouts: one ordinary launch per row
-        gt4mi_field a = *inp, b = *outf;
-        const int j = r == 0 ? row_a : row_b;
-        a.origin[1] += j;
-        b.origin[1] += j;
-        const int64_t d1[3] = {domain[0], 1, domain[2]};
-        if (int rc = lap5_run<T, W>(d1, &a, &b, variant, stream)) return rc;
-    }
     return GT4MI_OK;
 }
 

@@ -344,10 +344,8 @@ inline int lap5_edge_prepare(gt4mi_halo_plan* plan, const int64_t domain[3], con
             phase = p;
         }
     if (phase < 0 || plan->recvs[phase].empty() || (int)plan->recvs[phase].size() > BoxBatch::MAX) return GT4MI_OK;
-    const int h0[3] = {0, 0, 0}, h1[3] = {1, 1, 0};
-    if (int rc = make_view<T>("inp", inp, domain, h1, h1, in_v)) return rc;
-    if (int rc = make_view<T>("out", outf, domain, h0, h0, out_v)) return rc;
-    if (!(in_v->si == 1 && out_v->si == 1 && vec_ok(View<const T>{in_v->p, 1, in_v->sj, in_v->sk}, VEC) && vec_ok(*out_v, VEC))) return GT4MI_OK;
+    if (int rc = lap5_views<T>(domain, inp, outf, 1, nullptr, in_v, out_v)) return rc;  // (overlap: lap5_step_run)
+    if (!(in_v->si == 1 && out_v->si == 1 && vec_ok(*in_v, VEC) && vec_ok(*out_v, VEC))) return GT4MI_OK;
     // (RCCL) flags that are always satisfied, a sink for the signals, counters of their own: plan->edge_words
     uint32_t* const zero = plan->edge_words, * const sink = plan->edge_words + 1;
     unsigned* const counters = direct ? dx.ring_counters : reinterpret_cast<unsigned*>(plan->edge_words + 4);
@@ -439,18 +437,14 @@ inline int lap5_edge_run(gt4mi_halo_plan* plan, const int64_t domain[3], const g
     if (!ok) return GT4MI_OK;
     constexpr int VEC = 16 / (int)sizeof(T);
     const unsigned blocks = cp.blocks + (unsigned)cdiv((int64_t)g.first[4], (int64_t)4);
-#define GT4MI_LAP5_EDGE(V)                                                                                                       \
-    hipLaunchKernelGGL((lap5_edge_kernel<T, W, V, VEC, U>), dim3(blocks), dim3(256), 0, stream, in_v, out_v, (int)domain[0],      \
-                       (int)domain[1], (int)domain[2], g, cp, static_cast<U*>(inp->data), inp->stride[0] / (int64_t)sizeof(U),   \
-                       inp->stride[1] / (int64_t)sizeof(U), inp->stride[2] / (int64_t)sizeof(U))
-    switch (variant) {
-        case GT4MI_LAP_NOTEBOOK: GT4MI_LAP5_EDGE(GT4MI_LAP_NOTEBOOK); break;
-        case GT4MI_LAP_DOCS: GT4MI_LAP5_EDGE(GT4MI_LAP_DOCS); break;
-        case GT4MI_LAP_SUITE: GT4MI_LAP5_EDGE(GT4MI_LAP_SUITE); break;
-        case GT4MI_LAP_AVG: GT4MI_LAP5_EDGE(GT4MI_LAP_AVG); break;
-        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
-    }
-#undef GT4MI_LAP5_EDGE
+    if (int rc = lap5_with_variant(variant, [&](auto v) {
+            hipLaunchKernelGGL((lap5_edge_kernel<T, W, decltype(v)::value, VEC, U>), dim3(blocks), dim3(256), 0, stream, in_v, out_v,
+                               (int)domain[0], (int)domain[1], (int)domain[2], g, cp, static_cast<U*>(inp->data),
+                               inp->stride[0] / (int64_t)sizeof(U), inp->stride[1] / (int64_t)sizeof(U),
+                               inp->stride[2] / (int64_t)sizeof(U));
+            return GT4MI_OK;
+        }))
+        return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
     *done = true;
     return GT4MI_OK;
@@ -471,11 +465,9 @@ inline int lap5_step_run(gt4mi_halo_plan* plan, const int64_t domain[3], const g
     bool ok = false;
     if (int rc = lap5_edge_prepare<T>(plan, domain, inp, outf, sides, &in_v, &out_v, &g, &cp, &phase, &ok)) return rc;
     if (!ok) return GT4MI_OK;
-    constexpr int VMAX = 16 / (int)sizeof(T), LJ = Lap5Tuning::LJ;
+    constexpr int VMAX = 16 / (int)sizeof(T);
     const int64_t di = domain[0], dj = domain[1], dk = domain[2];
-    const int h1[3] = {1, 1, 0}, h0[3] = {0, 0, 0};
-    if (views_overlap(in_v, h1, h1, out_v, h0, h0, domain))
-        return fail(GT4MI_ERR_UNSUPPORTED, "lap5: 'inp' and 'out' overlap in memory (see gt4mi_lap5_*)");
+    if (int rc = lap5_refuse_overlap(in_v, out_v, domain, 1, LAP5_OVERLAP_SEE)) return rc;
     // the interior: every column of the rows that read no S / N ghost row; the first / last column is not stored where a W / E face
     // is on its way
     const int64_t lo_j = g.have[2] ? 1 : 0, rows = dj - lo_j - (g.have[3] ? 1 : 0);
@@ -483,47 +475,38 @@ inline int lap5_step_run(gt4mi_halo_plan* plan, const int64_t domain[3], const g
     const View<T> out_i{out_v.p + lo_j * out_v.sj, 1, out_v.sj, out_v.sk};
     const bool masked = g.have[0] || g.have[1];
     const int c_lo = g.have[0] ? VMAX : 0, c_hi = (int)di - (g.have[1] ? VMAX : 0);  // (whole lanes: lap5_edge_col_unit)
-    const int64_t lanes_per_row = di / VMAX;
-    const int tpb = lanes_per_row <= 64 ? 4 : (lanes_per_row <= 128 ? 2 : 1);  // tiles of 64 / 128 / 256 lanes, as lap5_launch_variant
-    const unsigned tx = (unsigned)cdiv(di, (int64_t)(256 / tpb) * VMAX), ty = (unsigned)cdiv(rows > 0 ? rows : 0, (int64_t)LJ);
-    const int64_t tiles = (int64_t)tx * ty * dk, interior = cdiv(tiles, (int64_t)tpb);
+    const Lap5InteriorTiling t = lap5_interior_tiling<T>(di, rows, dk);
     BoxBatch pb;
     DirectBatch pd;
     int64_t per_box = 0;
     if (int rc = direct_batches<U, true>(plan, inp, phase, pb, pd, per_box)) return rc;
     const int64_t pad = cdiv(per_box * pb.n, (int64_t)8) * 8;
     const int64_t tail = cdiv((int64_t)cp.blocks + cdiv((int64_t)g.first[4], (int64_t)4), (int64_t)8) * 8;
-    if (tiles > INT32_MAX || interior + pad + tail > INT32_MAX) return GT4MI_OK;
+    if (t.tiles > INT32_MAX || t.interior + pad + tail > INT32_MAX) return GT4MI_OK;
     // the units start after 85 % of the interior's workgroups
-    const int64_t split = (interior * 85 / 100) / 8 * 8;
-    const dim3 grid((unsigned)(pad + interior + tail));
-#define GT4MI_LAP5_STEP_T(V, TPB, M)                                                                                              \
+    const int64_t split = (t.interior * 85 / 100) / 8 * 8;
+    const dim3 grid((unsigned)(pad + t.interior + tail));
+    if (int rc = lap5_with_variant(variant, [&](auto v) {
+            constexpr int V = decltype(v)::value;
+#define GT4MI_LAP5_STEP(TPB, M)                                                                                                   \
     hipLaunchKernelGGL((lap5_step_kernel<T, W, V, U, TPB, M>), grid, dim3(256), launch_dynamic_lds(), stream, in_i, out_i, (int)di, \
-                       (int)rows, tx, ty, (unsigned)tiles, (unsigned)interior, (unsigned)pad, (unsigned)(per_box > 0 ? per_box : 1), \
-                       (unsigned)split, (unsigned)tail, c_lo, c_hi, static_cast<U*>(inp->data), inp->stride[0] / (int64_t)sizeof(U),                               \
-                       inp->stride[1] / (int64_t)sizeof(U), inp->stride[2] / (int64_t)sizeof(U), pb, pd, in_v, out_v, (int)dj,    \
-                       (int)dk, g, cp)
-#define GT4MI_LAP5_STEP(V)                                                    \
-    do {                                                                      \
-        if (masked) {                                                         \
-            if (tpb == 1) GT4MI_LAP5_STEP_T(V, 1, true);                      \
-            else if (tpb == 2) GT4MI_LAP5_STEP_T(V, 2, true);                 \
-            else GT4MI_LAP5_STEP_T(V, 4, true);                               \
-        } else {                                                              \
-            if (tpb == 1) GT4MI_LAP5_STEP_T(V, 1, false);                     \
-            else if (tpb == 2) GT4MI_LAP5_STEP_T(V, 2, false);                \
-            else GT4MI_LAP5_STEP_T(V, 4, false);                              \
-        }                                                                     \
-    } while (0)
-    switch (variant) {
-        case GT4MI_LAP_NOTEBOOK: GT4MI_LAP5_STEP(GT4MI_LAP_NOTEBOOK); break;
-        case GT4MI_LAP_DOCS: GT4MI_LAP5_STEP(GT4MI_LAP_DOCS); break;
-        case GT4MI_LAP_SUITE: GT4MI_LAP5_STEP(GT4MI_LAP_SUITE); break;
-        case GT4MI_LAP_AVG: GT4MI_LAP5_STEP(GT4MI_LAP_AVG); break;
-        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
-    }
+                       (int)rows, t.tx, t.ty, (unsigned)t.tiles, (unsigned)t.interior, (unsigned)pad,                              \
+                       (unsigned)(per_box > 0 ? per_box : 1), (unsigned)split, (unsigned)tail, c_lo, c_hi,                         \
+                       static_cast<U*>(inp->data), inp->stride[0] / (int64_t)sizeof(U), inp->stride[1] / (int64_t)sizeof(U),       \
+                       inp->stride[2] / (int64_t)sizeof(U), pb, pd, in_v, out_v, (int)dj, (int)dk, g, cp)
+            if (masked) {
+                if (t.tpb == 1) GT4MI_LAP5_STEP(1, true);
+                else if (t.tpb == 2) GT4MI_LAP5_STEP(2, true);
+                else GT4MI_LAP5_STEP(4, true);
+            } else {
+                if (t.tpb == 1) GT4MI_LAP5_STEP(1, false);
+                else if (t.tpb == 2) GT4MI_LAP5_STEP(2, false);
+                else GT4MI_LAP5_STEP(4, false);
+            }
 #undef GT4MI_LAP5_STEP
-#undef GT4MI_LAP5_STEP_T
+            return GT4MI_OK;
+        }))
+        return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
     *done = true;
     return GT4MI_OK;

@@ -48,49 +48,36 @@ inline int lap5_interior_with_push(gt4mi_halo_plan* plan, const int64_t sub[3], 
     using U = typename std::conditional<sizeof(T) == 8, uint64_t, uint32_t>::type;
     *fused = false;
     if (sub[0] <= 0 || sub[1] <= 0 || sub[2] <= 0) return GT4MI_OK;
-    constexpr int VMAX = 16 / (int)sizeof(T), LJ = Lap5Tuning::LJ;
+    constexpr int VMAX = 16 / (int)sizeof(T);
     if (int rc = check_domain(sub)) return rc;
-    const int h1[3] = {1, 1, 0}, h0[3] = {0, 0, 0};
     View<T> in_v, out_v;
-    if (int rc = make_view<T>("inp", a, sub, h1, h1, &in_v)) return rc;
-    if (int rc = make_view<T>("out", o, sub, h0, h0, &out_v)) return rc;
-    if (views_overlap(in_v, h1, h1, out_v, h0, h0, sub))
-        return fail(GT4MI_ERR_UNSUPPORTED, "lap5: 'inp' and 'out' overlap in memory (see gt4mi_lap5_*)");
-    const View<const T> in_c{in_v.p, in_v.si, in_v.sj, in_v.sk};
+    if (int rc = lap5_views<T>(sub, a, o, 1, LAP5_OVERLAP_SEE, &in_v, &out_v)) return rc;
+    const View<const T> in_c = const_view(in_v);
     if (!(in_c.si == 1 && out_v.si == 1 && vec_ok(in_c, VMAX) && vec_ok(out_v, VMAX) && sub[0] % VMAX == 0))
         return GT4MI_OK;  // another kernel of lap5_launch_variant would run this interior: keep the two launches
-    const int64_t lanes_per_row = sub[0] / VMAX;
-    const int tpb = lanes_per_row <= 64 ? 4 : (lanes_per_row <= 128 ? 2 : 1);  // tiles of 64 / 128 / 256 lanes, as lap5_launch_variant
-    const unsigned tx = (unsigned)cdiv(sub[0], (int64_t)(256 / tpb) * VMAX), ty = (unsigned)cdiv(sub[1], LJ);
-    const int64_t tiles = (int64_t)tx * ty * sub[2], interior = cdiv(tiles, (int64_t)tpb);
+    const Lap5InteriorTiling t = lap5_interior_tiling<T>(sub[0], sub[1], sub[2]);
     BoxBatch b;
     DirectBatch d;
     int64_t per_box = 0;
     if (int rc = direct_batches<U, true>(plan, exchanged, phase, b, d, per_box)) return rc;
     if (per_box == 0) return GT4MI_OK;  // nothing to push in this phase
     const int64_t pad = cdiv(per_box * b.n, (int64_t)8) * 8;
-    if (tiles > INT32_MAX || interior + pad > INT32_MAX) return GT4MI_OK;
-#define GT4MI_LAP5_PUSH_T(V, TPB)                                                                                                  \
-    hipLaunchKernelGGL((lap5_interior_push_kernel<T, W, V, U, TPB>), dim3((unsigned)(interior + pad)), dim3(256),                   \
-                       launch_dynamic_lds(), stream, in_c, out_v, (int)sub[0], (int)sub[1], tx, ty, (unsigned)tiles,                \
-                       (unsigned)interior, (unsigned)pad, (unsigned)per_box, static_cast<U*>(exchanged->data),                      \
+    if (t.tiles > INT32_MAX || t.interior + pad > INT32_MAX) return GT4MI_OK;
+    if (int rc = lap5_with_variant(variant, [&](auto v) {
+            constexpr int V = decltype(v)::value;
+#define GT4MI_LAP5_PUSH(TPB)                                                                                                       \
+    hipLaunchKernelGGL((lap5_interior_push_kernel<T, W, V, U, TPB>), dim3((unsigned)(t.interior + pad)), dim3(256),                 \
+                       launch_dynamic_lds(), stream, in_c, out_v, (int)sub[0], (int)sub[1], t.tx, t.ty, (unsigned)t.tiles,          \
+                       (unsigned)t.interior, (unsigned)pad, (unsigned)per_box, static_cast<U*>(exchanged->data),                    \
                        exchanged->stride[0] / (int64_t)sizeof(U), exchanged->stride[1] / (int64_t)sizeof(U),                        \
                        exchanged->stride[2] / (int64_t)sizeof(U), b, d)
-#define GT4MI_LAP5_PUSH(V)                          \
-    do {                                            \
-        if (tpb == 1) GT4MI_LAP5_PUSH_T(V, 1);      \
-        else if (tpb == 2) GT4MI_LAP5_PUSH_T(V, 2); \
-        else GT4MI_LAP5_PUSH_T(V, 4);               \
-    } while (0)
-    switch (variant) {
-        case GT4MI_LAP_NOTEBOOK: GT4MI_LAP5_PUSH(GT4MI_LAP_NOTEBOOK); break;
-        case GT4MI_LAP_DOCS: GT4MI_LAP5_PUSH(GT4MI_LAP_DOCS); break;
-        case GT4MI_LAP_SUITE: GT4MI_LAP5_PUSH(GT4MI_LAP_SUITE); break;
-        case GT4MI_LAP_AVG: GT4MI_LAP5_PUSH(GT4MI_LAP_AVG); break;
-        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
-    }
+            if (t.tpb == 1) GT4MI_LAP5_PUSH(1);
+            else if (t.tpb == 2) GT4MI_LAP5_PUSH(2);
+            else GT4MI_LAP5_PUSH(4);
 #undef GT4MI_LAP5_PUSH
-#undef GT4MI_LAP5_PUSH_T
+            return GT4MI_OK;
+        }))
+        return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
     *fused = true;
     return GT4MI_OK;

@@ -118,18 +118,17 @@ inline int lap5_launch_ring(const View<const T>& in, const View<T>& out, const i
         b.first[m + 1] = (unsigned)total;
     }
     const unsigned blocks = b.first[n];
-#define GT4MI_LAP5_RING(V, L) \
+    auto launch = [&](auto lanes) {  // lanes of VMAX items or of one
+        constexpr int V = decltype(lanes)::value;
+#define GT4MI_LAP5_RING(L) \
     hipLaunchKernelGGL((lap5_ring_kernel<T, W, VARIANT, V, L>), dim3(blocks), dim3(256), 0, stream, in, out, b)
-    if (vec) {
-        if (lj == 1) GT4MI_LAP5_RING(VMAX, 1);
-        else if (lj == 2) GT4MI_LAP5_RING(VMAX, 2);
-        else GT4MI_LAP5_RING(VMAX, 4);
-    } else {
-        if (lj == 1) GT4MI_LAP5_RING(1, 1);
-        else if (lj == 2) GT4MI_LAP5_RING(1, 2);
-        else GT4MI_LAP5_RING(1, 4);
-    }
+        if (lj == 1) GT4MI_LAP5_RING(1);
+        else if (lj == 2) GT4MI_LAP5_RING(2);
+        else GT4MI_LAP5_RING(4);
 #undef GT4MI_LAP5_RING
+    };
+    if (vec) launch(std::integral_constant<int, VMAX>());
+    else launch(std::integral_constant<int, 1>());
     return GT4MI_OK;
 }
 
@@ -145,30 +144,18 @@ inline int lap5_ring_run(const int64_t domain[3], const gt4mi_field* inp, const 
     if (inner[0] + inner[1] > domain[0] || inner[2] + inner[3] > domain[1])
         return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5 ring: inner widths do not fit the %lld x %lld domain", (long long)domain[0],
                     (long long)domain[1]);
-    if (domain[0] == 0 || domain[1] == 0 || domain[2] == 0) return GT4MI_OK;
+    if (empty_domain(domain)) return GT4MI_OK;
     // bounds and aliasing on the grown domain
     gt4mi_field a = *inp, o = *outf;
     a.origin[0] -= outer[0]; a.origin[1] -= outer[2];
     o.origin[0] -= outer[0]; o.origin[1] -= outer[2];
     const int64_t grown[3] = {domain[0] + outer[0] + outer[1], domain[1] + outer[2] + outer[3], domain[2]};
-    const int h1[3] = {1, 1, 0}, h0[3] = {0, 0, 0};
-    View<T> in_g, out_g;
-    if (int rc = make_view<T>("inp", &a, grown, h1, h1, &in_g)) return rc;
-    if (int rc = make_view<T>("out", &o, grown, h0, h0, &out_g)) return rc;
-    if (views_overlap(in_g, h1, h1, out_g, h0, h0, grown))
-        return fail(GT4MI_ERR_UNSUPPORTED, "lap5: 'inp' and 'out' overlap in memory (see gt4mi_lap5_*)");
     View<T> in_v, out_v;
-    if (int rc = make_view<T>("inp", inp, domain, h0, h0, &in_v)) return rc;
-    if (int rc = make_view<T>("out", outf, domain, h0, h0, &out_v)) return rc;
-    const View<const T> in_c{in_v.p, in_v.si, in_v.sj, in_v.sk};
-    int rc;
-    switch (variant) {
-        case GT4MI_LAP_NOTEBOOK: rc = lap5_launch_ring<T, W, GT4MI_LAP_NOTEBOOK>(in_c, out_v, domain, outer, inner, stream); break;
-        case GT4MI_LAP_DOCS: rc = lap5_launch_ring<T, W, GT4MI_LAP_DOCS>(in_c, out_v, domain, outer, inner, stream); break;
-        case GT4MI_LAP_SUITE: rc = lap5_launch_ring<T, W, GT4MI_LAP_SUITE>(in_c, out_v, domain, outer, inner, stream); break;
-        case GT4MI_LAP_AVG: rc = lap5_launch_ring<T, W, GT4MI_LAP_AVG>(in_c, out_v, domain, outer, inner, stream); break;
-        default: return fail(GT4MI_ERR_INVALID_ARGUMENT, "lap5: unknown variant %d", variant);
-    }
+    if (int rc = lap5_views<T>(grown, &a, &o, 1, LAP5_OVERLAP_SEE, &in_v, &out_v)) return rc;
+    if (int rc = lap5_views<T>(domain, inp, outf, 0, nullptr, &in_v, &out_v)) return rc;  // what the kernel gets
+    const int rc = lap5_with_variant(variant, [&](auto v) {
+        return lap5_launch_ring<T, W, decltype(v)::value>(const_view(in_v), out_v, domain, outer, inner, stream);
+    });
     if (rc) return rc;
     GT4MI_HIP_CHECK(hipGetLastError());
     return GT4MI_OK;
