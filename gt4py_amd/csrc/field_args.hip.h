@@ -3,7 +3,16 @@
 // the "no dst meets anything that is read" sweep.  What differs between the entries is DATA (BoxChecks, the arguments of
 // check_box_field): a new entry states its differences here instead of copying a check function.  The messages are part of
 // the library's behaviour (tests/test_refusal_messages.py holds them byte for byte).
+//
+// The PAIR entries (vertical_remap, horizontal_interp, horizontal_remap, line_solve) take (written, read) pairs, up to
+// PAIR_MAX_FIELDS per launch, the descriptors passed by value, the kernel instantiated for 1, 4 and 8 entries.  Such an entry states
+// its own args struct (`PairEntry e[PAIR_MAX_FIELDS]` first, then its SharedFields and scalars, and an `int nf`), its kernel
+// template with NF as a parameter, its scalar checks and its BoxChecks.  From here it takes the checks above, shared_field for what
+// every pair reads, next_pair_batch for the loop over the launches of a call, with_pair_entries for NF and with_item_type for
+// float / double; it keeps one hipLaunchKernelGGL per kernel template and the GT4MI_HIP_CHECK after each batch.
 #pragma once
+
+#include <type_traits>
 
 #include "common.hip.h"
 
@@ -14,9 +23,10 @@ inline char* origin_ptr(const gt4mi_field& f) {
     return static_cast<char*>(f.data) + f.origin[0] * f.stride[0] + f.origin[1] * f.stride[1] + f.origin[2] * f.stride[2];
 }
 
-// strides in ITEMS (the callers have checked that the byte strides are multiples of the item size)
-inline void item_strides(const gt4mi_field& f, int elem_size, int64_t out[3]) {
-    for (int ax = 0; ax < 3; ++ax) out[ax] = f.stride[ax] / elem_size;
+// strides in ITEMS (the callers have checked that the byte strides are multiples of the item size); with an `order`, out[x] is the
+// stride along axis order[x]
+inline void item_strides(const gt4mi_field& f, int elem_size, int64_t out[3], const int* order = nullptr) {
+    for (int x = 0; x < 3; ++x) out[x] = f.stride[order != nullptr ? order[x] : x] / elem_size;
 }
 
 // the byte range the box [origin, origin + extent) of a field touches; `grow` (null: none) widens the box by grow[0 / 2] points
@@ -110,6 +120,64 @@ inline int check_pairs_disjoint(const char* entry, const gt4mi_field* dst, const
         }
     }
     return GT4MI_OK;
+}
+
+// ---- the launches of the pair entries ----------------------------------------------------------------------------------------------
+constexpr int PAIR_MAX_FIELDS = 8;  // pairs of one launch (include/gt4py_amd.h and the Python wrappers say "per 8 pairs")
+
+struct PairEntry {
+    char* dst;           // first item of the written box
+    const char* src;     // first item of the read box
+    int64_t d[3], s[3];  // strides in ITEMS of dst / src
+};
+
+// a field that every pair of a launch reads (edges, positions, coefficients)
+struct SharedField {
+    const char* p;  // first item of the box
+    int64_t s[3];   // strides in ITEMS; 0 broadcasts
+};
+
+inline SharedField shared_field(const gt4mi_field& f, int elem_size, const int* order = nullptr) {
+    SharedField q{};
+    q.p = origin_ptr(f);
+    item_strides(f, elem_size, q.s, order);
+    return q;
+}
+
+// The loop over the launches of a call: `int next = 0; while (next_pair_batch(a, dst, src, &next, ...)) { launch a; }`.  False when
+// no pair is left; else pairs [*next, *next + a.nf) go to a.e[0 .. a.nf), the rest of a.e is zeroed (the kernel is handed the whole
+// block) and *next moves on.  `order` as in item_strides.
+template <typename Args>
+inline bool next_pair_batch(Args& a, const gt4mi_field* dst, const gt4mi_field* src, int* next, int nfields, int elem_size,
+                            const int* order = nullptr) {
+    const int first = *next;
+    if (first >= nfields) return false;
+    a.nf = nfields - first < PAIR_MAX_FIELDS ? nfields - first : PAIR_MAX_FIELDS;
+    for (int n = 0; n < PAIR_MAX_FIELDS; ++n) {
+        PairEntry& e = a.e[n];
+        e = PairEntry{};
+        if (n >= a.nf) continue;
+        e.dst = origin_ptr(dst[first + n]), e.src = origin_ptr(src[first + n]);
+        item_strides(dst[first + n], elem_size, e.d, order), item_strides(src[first + n], elem_size, e.s, order);
+    }
+    *next = first + a.nf;
+    return true;
+}
+
+// The entries a kernel is instantiated for, as a compile-time constant: f(std::integral_constant<int, NF>{}) with the smallest of
+// 1, 4 and 8 that holds `nf`.
+template <typename F>
+inline void with_pair_entries(int nf, F&& f) {
+    if (nf == 1) f(std::integral_constant<int, 1>{});
+    else if (nf <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, PAIR_MAX_FIELDS>{});
+}
+
+// An item size the entry has checked to be 4 or 8 as a type: f(float{}) or f(double{}).
+template <typename F>
+inline void with_item_type(int elem_size, F&& f) {
+    if (elem_size == 8) f(double{});
+    else f(float{});
 }
 
 }  // namespace gt4mi

@@ -48,23 +48,11 @@
 
 namespace gt4mi {
 
-constexpr int INTERP_MAX_FIELDS = 8;
 constexpr int INTERP_TILE_I = 64, INTERP_TILE_J = 4, INTERP_CHUNK_K = 8;
 
-struct InterpEntry {
-    char* dst;        // domain point (0, 0, 0)
-    const char* src;  // domain point (0, 0, 0); readable from -lo to n - 1 + hi along I and J
-    int64_t d[3], s[3];  // strides in ITEMS
-};
-
-struct InterpPos {
-    const char* p;  // domain point (0, 0, 0)
-    int64_t s[3];   // strides in ITEMS; 0 along K broadcasts a Field[IJ]
-};
-
 struct InterpArgs {
-    InterpEntry e[INTERP_MAX_FIELDS];
-    InterpPos pi, pj;
+    PairEntry e[PAIR_MAX_FIELDS];  // dst, src: domain point (0, 0, 0); a src is readable from -lo to n - 1 + hi along I and J
+    SharedField pi, pj;            // domain point (0, 0, 0); stride 0 along K broadcasts a Field[IJ]
     int ni, nj, nk, nf;
     int lo_i, hi_i, lo_j, hi_j;
     unsigned tiles_i, tiles_j;
@@ -163,7 +151,7 @@ horizontal_interp_kernel(const InterpArgs a) {
 #pragma unroll
         for (int n = 0; n < NF; ++n) {
             if (n >= nf) continue;
-            const InterpEntry& e = a.e[n];
+            const PairEntry& e = a.e[n];
             if constexpr (METHOD == GT4MI_INTERP_NEAREST) {
                 using U = typename InterpBits<T>::type;
                 const U v = reinterpret_cast<const U*>(e.src)[k * e.s[2] + jj[0] * e.s[1] + ii[0] * e.s[0]];
@@ -199,27 +187,12 @@ horizontal_interp_kernel(const InterpArgs a) {
 const BoxChecks INTERP_CHECKS = {"horizontal_interp", "extent", "only a src or a position field may be broadcast", false, true};
 constexpr int INTERP_POS_FREE_AXES = 4;  // a Field[IJ] of positions: stride 0 along K, one item for every level, no shape to check
 
-inline InterpPos interp_pos(const gt4mi_field& f, int elem_size) {
-    InterpPos q{};
-    q.p = origin_ptr(f);
-    item_strides(f, elem_size, q.s);
-    return q;
-}
-
 template <typename T, typename P, int METHOD>
 inline void interp_launch(const InterpArgs& a, int64_t blocks, hipStream_t stream) {
-    const dim3 grid((unsigned)blocks), block(INTERP_TILE_I * INTERP_TILE_J);
-    if (a.nf == 1) hipLaunchKernelGGL((horizontal_interp_kernel<T, P, METHOD, 1>), grid, block, 0, stream, a);
-    else if (a.nf <= 4) hipLaunchKernelGGL((horizontal_interp_kernel<T, P, METHOD, 4>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((horizontal_interp_kernel<T, P, METHOD, 8>), grid, block, 0, stream, a);
-}
-
-template <typename T, typename P>
-inline void interp_launch_method(const InterpArgs& a, int64_t blocks, int method, hipStream_t stream) {
-    if (method == GT4MI_INTERP_NEAREST) interp_launch<T, P, GT4MI_INTERP_NEAREST>(a, blocks, stream);
-    else if (method == GT4MI_INTERP_LINEAR) interp_launch<T, P, GT4MI_INTERP_LINEAR>(a, blocks, stream);
-    else if (method == GT4MI_INTERP_CUBIC) interp_launch<T, P, GT4MI_INTERP_CUBIC>(a, blocks, stream);
-    else interp_launch<T, P, GT4MI_INTERP_CUBIC_MONOTONE>(a, blocks, stream);
+    with_pair_entries(a.nf, [&](auto nf) {
+        hipLaunchKernelGGL((horizontal_interp_kernel<T, P, METHOD, decltype(nf)::value>), dim3((unsigned)blocks),
+                           dim3(INTERP_TILE_I * INTERP_TILE_J), 0, stream, a);
+    });
 }
 
 // every check, then (unless `flags` carries GT4MI_INTERP_DRY_RUN) the launches
@@ -263,27 +236,26 @@ inline int horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int
     const int64_t tiles_i = cdiv(extent[0], INTERP_TILE_I), tiles_j = cdiv(extent[1], INTERP_TILE_J);
     const int64_t blocks = tiles_i * tiles_j * cdiv(extent[2], INTERP_CHUNK_K);
     if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_interp: too many points for one launch");
-    if (launches) *launches = (int)cdiv(nfields, INTERP_MAX_FIELDS);
+    if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
     if (flags & GT4MI_INTERP_DRY_RUN) return GT4MI_OK;
     InterpArgs a{};
-    a.pi = interp_pos(*pos_i, pos_elem_size), a.pj = interp_pos(*pos_j, pos_elem_size);
+    a.pi = shared_field(*pos_i, pos_elem_size), a.pj = shared_field(*pos_j, pos_elem_size);
     a.ni = (int)extent[0], a.nj = (int)extent[1], a.nk = (int)extent[2];
     a.lo_i = (int)reach[0], a.hi_i = (int)reach[1], a.lo_j = (int)reach[2], a.hi_j = (int)reach[3];
     a.tiles_i = (unsigned)tiles_i, a.tiles_j = (unsigned)tiles_j;
     a.relative = (flags & GT4MI_INTERP_RELATIVE) ? 1 : 0;
-    for (int first = 0; first < nfields; first += INTERP_MAX_FIELDS) {
-        a.nf = nfields - first < INTERP_MAX_FIELDS ? nfields - first : INTERP_MAX_FIELDS;
-        for (int n = 0; n < INTERP_MAX_FIELDS; ++n) {
-            InterpEntry& e = a.e[n];
-            e = InterpEntry{};
-            if (n >= a.nf) continue;
-            e.dst = origin_ptr(dst[first + n]), e.src = origin_ptr(src[first + n]);
-            item_strides(dst[first + n], elem_size, e.d), item_strides(src[first + n], elem_size, e.s);
-        }
-        if (elem_size == 8 && pos_elem_size == 8) interp_launch_method<double, double>(a, blocks, method, stream);
-        else if (elem_size == 8) interp_launch_method<double, float>(a, blocks, method, stream);
-        else if (pos_elem_size == 8) interp_launch_method<float, double>(a, blocks, method, stream);
-        else interp_launch_method<float, float>(a, blocks, method, stream);
+    int next = 0;
+    while (next_pair_batch(a, dst, src, &next, nfields, elem_size)) {
+        with_item_type(elem_size, [&](auto t) {
+            with_item_type(pos_elem_size, [&](auto p) {
+                using T = decltype(t);
+                using P = decltype(p);
+                if (method == GT4MI_INTERP_NEAREST) interp_launch<T, P, GT4MI_INTERP_NEAREST>(a, blocks, stream);
+                else if (method == GT4MI_INTERP_LINEAR) interp_launch<T, P, GT4MI_INTERP_LINEAR>(a, blocks, stream);
+                else if (method == GT4MI_INTERP_CUBIC) interp_launch<T, P, GT4MI_INTERP_CUBIC>(a, blocks, stream);
+                else interp_launch<T, P, GT4MI_INTERP_CUBIC_MONOTONE>(a, blocks, stream);
+            });
+        });
         GT4MI_HIP_CHECK(hipGetLastError());
     }
     return GT4MI_OK;

@@ -106,17 +106,10 @@ inline int overlap_table(const double* xs, int ns, const double* xd, int nd, int
 }
 
 // ---- the kernel -----------------------------------------------------------------------------------------------------------------
-constexpr int HREMAP_MAX_FIELDS = 8;
 constexpr int HREMAP_TILE_I = 64, HREMAP_TILE_J = 4, HREMAP_CHUNK_K = 8;
 
-struct HRemapEntry {
-    char* dst;        // first item of the dst box
-    const char* src;  // first item of the src box
-    int64_t d[3], s[3];  // strides in ITEMS
-};
-
 struct HRemapArgs {
-    HRemapEntry e[HREMAP_MAX_FIELDS];
+    PairEntry e[PAIR_MAX_FIELDS];
     gt4mi_overlap_axis ai, aj;  // (device pointers)
     int nk, nf;
     unsigned tiles_i, tiles_j;
@@ -181,7 +174,7 @@ horizontal_remap_kernel(const HRemapArgs a) {
 #pragma unroll
                 for (int n = 0; n < NF; ++n) {
                     if (n >= nf) continue;
-                    const HRemapEntry& e = a.e[n];
+                    const PairEntry& e = a.e[n];
                     const T* const s = reinterpret_cast<const T*>(e.src) + k * e.s[2];
                     const double q = (double)s[ca * e.s[0] + cb * e.s[1]];
                     double v = q;
@@ -213,10 +206,10 @@ const BoxChecks HREMAP_CHECKS = {"horizontal_remap", "extent", "only a src may b
 
 template <typename T, int METHOD>
 inline void hremap_launch(const HRemapArgs& a, int64_t blocks, hipStream_t stream) {
-    const dim3 grid((unsigned)blocks), block(HREMAP_TILE_I * HREMAP_TILE_J);
-    if (a.nf == 1) hipLaunchKernelGGL((horizontal_remap_kernel<T, METHOD, 1>), grid, block, 0, stream, a);
-    else if (a.nf <= 4) hipLaunchKernelGGL((horizontal_remap_kernel<T, METHOD, 4>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((horizontal_remap_kernel<T, METHOD, 8>), grid, block, 0, stream, a);
+    with_pair_entries(a.nf, [&](auto nf) {
+        hipLaunchKernelGGL((horizontal_remap_kernel<T, METHOD, decltype(nf)::value>), dim3((unsigned)blocks),
+                           dim3(HREMAP_TILE_I * HREMAP_TILE_J), 0, stream, a);
+    });
 }
 
 // one axis of a call: counts, pointers, alignment; its arrays' byte spans go to `spans` (for the overlap sweep)
@@ -276,28 +269,19 @@ inline int horizontal_remap(const gt4mi_field* dst, const gt4mi_field* src, int 
     const int64_t tiles_i = cdiv(d_ext[0], HREMAP_TILE_I), tiles_j = cdiv(d_ext[1], HREMAP_TILE_J);
     const int64_t blocks = tiles_i * tiles_j * cdiv(nk, HREMAP_CHUNK_K);
     if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "horizontal_remap: too many points for one launch");
-    if (launches) *launches = (int)cdiv(nfields, HREMAP_MAX_FIELDS);
+    if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
     if (flags & GT4MI_HREMAP_DRY_RUN) return GT4MI_OK;
     HRemapArgs a{};
     a.ai = *axis_i, a.aj = *axis_j;
     a.nk = (int)nk;
     a.tiles_i = (unsigned)tiles_i, a.tiles_j = (unsigned)tiles_j;
-    for (int first = 0; first < nfields; first += HREMAP_MAX_FIELDS) {
-        a.nf = nfields - first < HREMAP_MAX_FIELDS ? nfields - first : HREMAP_MAX_FIELDS;
-        for (int n = 0; n < HREMAP_MAX_FIELDS; ++n) {
-            HRemapEntry& e = a.e[n];
-            e = HRemapEntry{};
-            if (n >= a.nf) continue;
-            e.dst = origin_ptr(dst[first + n]), e.src = origin_ptr(src[first + n]);
-            item_strides(dst[first + n], elem_size, e.d), item_strides(src[first + n], elem_size, e.s);
-        }
-        if (elem_size == 8) {
-            if (method == GT4MI_HREMAP_PLM) hremap_launch<double, GT4MI_HREMAP_PLM>(a, blocks, stream);
-            else hremap_launch<double, GT4MI_HREMAP_PCM>(a, blocks, stream);
-        } else {
-            if (method == GT4MI_HREMAP_PLM) hremap_launch<float, GT4MI_HREMAP_PLM>(a, blocks, stream);
-            else hremap_launch<float, GT4MI_HREMAP_PCM>(a, blocks, stream);
-        }
+    int next = 0;
+    while (next_pair_batch(a, dst, src, &next, nfields, elem_size)) {
+        with_item_type(elem_size, [&](auto t) {
+            using T = decltype(t);
+            if (method == GT4MI_HREMAP_PLM) hremap_launch<T, GT4MI_HREMAP_PLM>(a, blocks, stream);
+            else hremap_launch<T, GT4MI_HREMAP_PCM>(a, blocks, stream);
+        });
         GT4MI_HIP_CHECK(hipGetLastError());
     }
     return GT4MI_OK;

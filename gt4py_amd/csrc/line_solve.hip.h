@@ -51,27 +51,15 @@
 
 namespace gt4mi {
 
-constexpr int LINE_MAX_FIELDS = 8;
 constexpr int LINE_BLOCK = 256;      // lanes (= lines) of a workgroup on the LANES / ITEMS paths
 constexpr int LINE_AHEAD = 4;        // steps whose loads are in flight on the LANES path
 constexpr int LINE_TILE_LINES = 64;  // TILES: lines of a tile = lanes of the wave that owns it
 constexpr int LINE_TILE_BYTES = 128; // TILES: the run along the line a tile covers
 
-// strides in ITEMS, permuted by the host: [0] the line axis, [1] the lane axis A, [2] the remaining axis B
-struct LineEntry {
-    char* out;        // first item of the box
-    const char* rhs;
-    int64_t o[3], r[3];
-};
-
-struct LineCoef {
-    const char* p;
-    int64_t s[3];  // 0 along A / B broadcasts a 1-d coefficient
-};
-
+// Every stride (ITEMS) is permuted by the host: [0] the line axis, [1] the lane axis A, [2] the remaining axis B.
 struct LineArgs {
-    LineEntry e[LINE_MAX_FIELDS];
-    LineCoef lo, di, up;
+    PairEntry e[PAIR_MAX_FIELDS];  // dst / d: out and its strides, src / s: rhs and its strides
+    SharedField lo, di, up;        // stride 0 along A / B broadcasts a 1-d coefficient
     char* cp;       // workspace: cp[m * pitch + line]
     char* q;        // periodic: q[m * pitch + line]
     int64_t pitch;  // items of a workspace row
@@ -100,8 +88,8 @@ line_solve_march_kernel(const LineArgs a) {
     for (int f = 0; f < NF; ++f) {
         rhs[f] = nullptr, out[f] = nullptr, dprev[f] = T(0);
         if (f < nf) {
-            rhs[f] = reinterpret_cast<const T*>(a.e[f].rhs) + ia * a.e[f].r[1] + ib * a.e[f].r[2];
-            out[f] = reinterpret_cast<T*>(a.e[f].out) + ia * a.e[f].o[1] + ib * a.e[f].o[2];
+            rhs[f] = reinterpret_cast<const T*>(a.e[f].src) + ia * a.e[f].s[1] + ib * a.e[f].s[2];
+            out[f] = reinterpret_cast<T*>(a.e[f].dst) + ia * a.e[f].d[1] + ib * a.e[f].d[2];
         }
     }
 
@@ -141,7 +129,7 @@ line_solve_march_kernel(const LineArgs a) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 vd[f][u] = T(0);
-                if (f < nf && m < n) vd[f][u] = rhs[f][(int64_t)m * a.e[f].r[0]];
+                if (f < nf && m < n) vd[f][u] = rhs[f][(int64_t)m * a.e[f].s[0]];
             }
         }
 #pragma unroll
@@ -160,7 +148,7 @@ line_solve_march_kernel(const LineArgs a) {
                 for (int f = 0; f < NF; ++f)
                     if (f < nf) {
                         dprev[f] = (vd[f][u] - va[u] * dprev[f]) / den;
-                        out[f][(int64_t)m * a.e[f].o[0]] = dprev[f];
+                        out[f][(int64_t)m * a.e[f].d[0]] = dprev[f];
                     }
                 if (periodic) {
                     const T um = last ? alpha : T(0);
@@ -190,7 +178,7 @@ line_solve_march_kernel(const LineArgs a) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 wd[f][u] = T(0);
-                if (f < nf && m >= 0) wd[f][u] = out[f][(int64_t)m * a.e[f].o[0]];
+                if (f < nf && m >= 0) wd[f][u] = out[f][(int64_t)m * a.e[f].d[0]];
             }
         }
 #pragma unroll
@@ -201,7 +189,7 @@ line_solve_march_kernel(const LineArgs a) {
                 for (int f = 0; f < NF; ++f)
                     if (f < nf) {
                         x[f] = wd[f][u] - wc[u] * x[f];
-                        out[f][(int64_t)m * a.e[f].o[0]] = x[f];
+                        out[f][(int64_t)m * a.e[f].d[0]] = x[f];
                     }
                 if (periodic) {
                     qx = wq[u] - wc[u] * qx;
@@ -227,7 +215,7 @@ line_solve_march_kernel(const LineArgs a) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 wy[f][u] = T(0);
-                if (f < nf && m < n) wy[f][u] = out[f][(int64_t)m * a.e[f].o[0]];
+                if (f < nf && m < n) wy[f][u] = out[f][(int64_t)m * a.e[f].d[0]];
             }
         }
 #pragma unroll
@@ -236,7 +224,7 @@ line_solve_march_kernel(const LineArgs a) {
             if (m < n) {
 #pragma unroll
                 for (int f = 0; f < NF; ++f)
-                    if (f < nf) out[f][(int64_t)m * a.e[f].o[0]] = wy[f][u] - fact[f] * wq[u];
+                    if (f < nf) out[f][(int64_t)m * a.e[f].d[0]] = wy[f][u] - fact[f] * wq[u];
             }
         }
     }
@@ -316,7 +304,7 @@ line_solve_tile_kernel(const LineArgs a) {
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         orhs[f] = oout[f] = 0, dprev[f] = T(0);
-        if (f < nf) orhs[f] = ia * a.e[f].r[1] + ib * a.e[f].r[2], oout[f] = ia * a.e[f].o[1] + ib * a.e[f].o[2];
+        if (f < nf) orhs[f] = ia * a.e[f].s[1] + ib * a.e[f].s[2], oout[f] = ia * a.e[f].d[1] + ib * a.e[f].d[2];
     }
     const int tiles = (n + R - 1) / R;
 
@@ -365,7 +353,7 @@ line_solve_tile_kernel(const LineArgs a) {
         for (int f = 0; f < NF; ++f) {
             if (f < nf) {
                 __syncthreads();  // (tf is free: the stores of the field before have read it)
-                line_tile_move<T, true>(tf, reinterpret_cast<const T*>(a.e[f].rhs), orhs[f], ok, m0, n);
+                line_tile_move<T, true>(tf, reinterpret_cast<const T*>(a.e[f].src), orhs[f], ok, m0, n);
                 __syncthreads();
                 if (ok) {
                     for (int r = 0; r < R && m0 + r < n; ++r) {
@@ -375,7 +363,7 @@ line_solve_tile_kernel(const LineArgs a) {
                     }
                 }
                 __syncthreads();
-                line_tile_move<T, false>(tf, reinterpret_cast<T*>(a.e[f].out), oout[f], ok, m0, n);
+                line_tile_move<T, false>(tf, reinterpret_cast<T*>(a.e[f].dst), oout[f], ok, m0, n);
             }
         }
     }
@@ -405,7 +393,7 @@ line_solve_tile_kernel(const LineArgs a) {
         for (int f = 0; f < NF; ++f) {
             if (f < nf) {
                 __syncthreads();
-                line_tile_move<T, true>(tf, reinterpret_cast<const T*>(a.e[f].out), oout[f], ok, m0, n);
+                line_tile_move<T, true>(tf, reinterpret_cast<const T*>(a.e[f].dst), oout[f], ok, m0, n);
                 __syncthreads();
                 if (ok) {
                     for (int r = R - 1; r >= 0; --r) {
@@ -416,7 +404,7 @@ line_solve_tile_kernel(const LineArgs a) {
                     }
                 }
                 __syncthreads();
-                line_tile_move<T, false>(tf, reinterpret_cast<T*>(a.e[f].out), oout[f], ok, m0, n);
+                line_tile_move<T, false>(tf, reinterpret_cast<T*>(a.e[f].dst), oout[f], ok, m0, n);
             }
         }
     }
@@ -436,12 +424,12 @@ line_solve_tile_kernel(const LineArgs a) {
         for (int f = 0; f < NF; ++f) {
             if (f < nf) {
                 __syncthreads();
-                line_tile_move<T, true>(tf, reinterpret_cast<const T*>(a.e[f].out), oout[f], ok, m0, n);
+                line_tile_move<T, true>(tf, reinterpret_cast<const T*>(a.e[f].dst), oout[f], ok, m0, n);
                 __syncthreads();
                 if (ok)
                     for (int r = 0; r < R && m0 + r < n; ++r) tf[lane][r] = tf[lane][r] - fact[f] * tc[lane][r];
                 __syncthreads();
-                line_tile_move<T, false>(tf, reinterpret_cast<T*>(a.e[f].out), oout[f], ok, m0, n);
+                line_tile_move<T, false>(tf, reinterpret_cast<T*>(a.e[f].dst), oout[f], ok, m0, n);
             }
         }
     }
@@ -451,31 +439,18 @@ line_solve_tile_kernel(const LineArgs a) {
 const BoxChecks LINE_CHECKS = {"line_solve", "extent", "only a rhs or a coefficient may be broadcast", false, false};
 const PairRoles LINE_ROLES = {"out", "rhs", true};  // an out may BE its own rhs (the same box), and meet nothing else
 
-inline LineCoef line_coef(const gt4mi_field& f, int elem_size, const int order[3]) {
-    LineCoef c{};
-    c.p = origin_ptr(f);
-    int64_t s[3];
-    item_strides(f, elem_size, s);
-    for (int x = 0; x < 3; ++x) c.s[x] = s[order[x]];
-    return c;
-}
-
-template <typename T, int NF>
-inline void line_launch_nf(const LineArgs& a, int path, hipStream_t stream) {
-    const int64_t lines = (int64_t)a.na * a.nb;
-    if (path == GT4MI_LINE_PATH_TILES)
-        hipLaunchKernelGGL((line_solve_tile_kernel<T, NF>), dim3((unsigned)cdiv(lines, LINE_TILE_LINES)), dim3(LINE_TILE_LINES), 0, stream, a);
-    else if (path == GT4MI_LINE_PATH_LANES)
-        hipLaunchKernelGGL((line_solve_march_kernel<T, NF, LINE_AHEAD>), dim3((unsigned)cdiv(lines, LINE_BLOCK)), dim3(LINE_BLOCK), 0, stream, a);
-    else
-        hipLaunchKernelGGL((line_solve_march_kernel<T, NF, 1>), dim3((unsigned)cdiv(lines, LINE_BLOCK)), dim3(LINE_BLOCK), 0, stream, a);
-}
-
 template <typename T>
 inline void line_launch(const LineArgs& a, int path, hipStream_t stream) {
-    if (a.nf == 1) line_launch_nf<T, 1>(a, path, stream);
-    else if (a.nf <= 4) line_launch_nf<T, 4>(a, path, stream);
-    else line_launch_nf<T, 8>(a, path, stream);
+    const int64_t lines = (int64_t)a.na * a.nb;
+    with_pair_entries(a.nf, [&](auto nf) {
+        constexpr int NF = decltype(nf)::value;
+        if (path == GT4MI_LINE_PATH_TILES)
+            hipLaunchKernelGGL((line_solve_tile_kernel<T, NF>), dim3((unsigned)cdiv(lines, LINE_TILE_LINES)), dim3(LINE_TILE_LINES), 0, stream, a);
+        else if (path == GT4MI_LINE_PATH_LANES)
+            hipLaunchKernelGGL((line_solve_march_kernel<T, NF, LINE_AHEAD>), dim3((unsigned)cdiv(lines, LINE_BLOCK)), dim3(LINE_BLOCK), 0, stream, a);
+        else
+            hipLaunchKernelGGL((line_solve_march_kernel<T, NF, 1>), dim3((unsigned)cdiv(lines, LINE_BLOCK)), dim3(LINE_BLOCK), 0, stream, a);
+    });
 }
 
 // The path of a call and its lane axis: `unit[ax]` = every field of the call has unit item stride along ax (a coefficient may
@@ -565,28 +540,18 @@ inline int line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfield
         for (int c = 0; c < 3; ++c)
             if (spans_overlap(w, shared[c].span)) return fail(GT4MI_ERR_UNSUPPORTED, "line_solve: workspace overlaps %s", coef_names[c]);
     }
-    if (launches) *launches = (int)cdiv(nfields, LINE_MAX_FIELDS);
+    if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
     if (dry) return GT4MI_OK;
     LineArgs a{};
-    a.lo = line_coef(*lower, elem_size, order), a.di = line_coef(*diag, elem_size, order), a.up = line_coef(*upper, elem_size, order);
+    a.lo = shared_field(*lower, elem_size, order), a.di = shared_field(*diag, elem_size, order), a.up = shared_field(*upper, elem_size, order);
     a.cp = static_cast<char*>(workspace);
     a.q = a.cp + (periodic ? pitch * n * elem_size : 0);
     a.pitch = pitch;
     a.n = (int)n, a.na = (int)extent[order[1]], a.nb = (int)extent[order[2]], a.periodic = periodic;
     // (a later launch of the call forms cp and q again, in the same workspace and to the same bits: launches are stream-ordered)
-    for (int first = 0; first < nfields; first += LINE_MAX_FIELDS) {
-        a.nf = nfields - first < LINE_MAX_FIELDS ? nfields - first : LINE_MAX_FIELDS;
-        for (int k = 0; k < LINE_MAX_FIELDS; ++k) {
-            LineEntry& e = a.e[k];
-            e = LineEntry{};
-            if (k >= a.nf) continue;
-            e.out = origin_ptr(out[first + k]), e.rhs = origin_ptr(rhs[first + k]);
-            int64_t o[3], r[3];
-            item_strides(out[first + k], elem_size, o), item_strides(rhs[first + k], elem_size, r);
-            for (int x = 0; x < 3; ++x) e.o[x] = o[order[x]], e.r[x] = r[order[x]];
-        }
-        if (elem_size == 8) line_launch<double>(a, which, stream);
-        else line_launch<float>(a, which, stream);
+    int next = 0;
+    while (next_pair_batch(a, out, rhs, &next, nfields, elem_size, order)) {
+        with_item_type(elem_size, [&](auto t) { line_launch<decltype(t)>(a, which, stream); });
         GT4MI_HIP_CHECK(hipGetLastError());
     }
     return GT4MI_OK;

@@ -39,23 +39,11 @@
 
 namespace gt4mi {
 
-constexpr int REMAP_MAX_FIELDS = 8;
 constexpr int REMAP_TILE_I = 64, REMAP_TILE_J = 4;
 
-struct RemapEntry {
-    char* dst;        // first item of the box
-    const char* src;
-    int64_t d[3], s[3];  // strides in ITEMS
-};
-
-struct RemapEdges {
-    const char* p;  // edge 0 of the box's first column
-    int64_t s[3];   // strides in ITEMS; 0 along I / J broadcasts
-};
-
 struct RemapArgs {
-    RemapEntry e[REMAP_MAX_FIELDS];
-    RemapEdges zs, zd;
+    PairEntry e[PAIR_MAX_FIELDS];
+    SharedField zs, zd;  // edge 0 of the box's first column; stride 0 along I / J broadcasts
     int ni, nj, ns, nd, nf;
     unsigned tiles_i;
 };
@@ -161,25 +149,12 @@ vertical_remap_kernel(const RemapArgs a) {
 const BoxChecks REMAP_CHECKS = {"vertical_remap", "extent", "only a src or an edge field may be broadcast", false, false};
 constexpr int REMAP_EDGE_FREE_AXES = 3;  // a Field[K] of edges: stride 0 along I / J, one item for every i / j, no shape to check
 
-inline RemapEdges remap_edges(const gt4mi_field& f, int elem_size) {
-    RemapEdges e{};
-    e.p = origin_ptr(f);
-    item_strides(f, elem_size, e.s);
-    return e;
-}
-
 template <typename T, typename E, int METHOD>
 inline void remap_launch(const RemapArgs& a, int64_t blocks, hipStream_t stream) {
-    const dim3 grid((unsigned)blocks), block(REMAP_TILE_I * REMAP_TILE_J);
-    if (a.nf == 1) hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, 1>), grid, block, 0, stream, a);
-    else if (a.nf <= 4) hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, 4>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, 8>), grid, block, 0, stream, a);
-}
-
-template <typename T, typename E>
-inline void remap_launch_method(const RemapArgs& a, int64_t blocks, int method, hipStream_t stream) {
-    if (method == GT4MI_REMAP_PLM) remap_launch<T, E, GT4MI_REMAP_PLM>(a, blocks, stream);
-    else remap_launch<T, E, GT4MI_REMAP_PCM>(a, blocks, stream);
+    with_pair_entries(a.nf, [&](auto nf) {
+        hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, decltype(nf)::value>), dim3((unsigned)blocks),
+                           dim3(REMAP_TILE_I * REMAP_TILE_J), 0, stream, a);
+    });
 }
 
 // every check, then (unless `flags` carries GT4MI_REMAP_DRY_RUN) the launches
@@ -218,25 +193,22 @@ inline int vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nf
     if (int rc = check_pairs_disjoint("vertical_remap", dst, src, nfields, d_ext, s_ext, elem_size, elem_size, nullptr, edges, 2)) return rc;
     const int64_t tiles_i = cdiv(extent_ij[0], REMAP_TILE_I), blocks = tiles_i * cdiv(extent_ij[1], REMAP_TILE_J);
     if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: too many columns for one launch");
-    if (launches) *launches = (int)cdiv(nfields, REMAP_MAX_FIELDS);
+    if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
     if (flags & GT4MI_REMAP_DRY_RUN) return GT4MI_OK;
     RemapArgs a{};
-    a.zs = remap_edges(*src_edges, edge_elem_size), a.zd = remap_edges(*dst_edges, edge_elem_size);
+    a.zs = shared_field(*src_edges, edge_elem_size), a.zd = shared_field(*dst_edges, edge_elem_size);
     a.ni = (int)extent_ij[0], a.nj = (int)extent_ij[1], a.ns = (int)ns, a.nd = (int)nd;
     a.tiles_i = (unsigned)tiles_i;
-    for (int first = 0; first < nfields; first += REMAP_MAX_FIELDS) {
-        a.nf = nfields - first < REMAP_MAX_FIELDS ? nfields - first : REMAP_MAX_FIELDS;
-        for (int n = 0; n < REMAP_MAX_FIELDS; ++n) {
-            RemapEntry& e = a.e[n];
-            e = RemapEntry{};
-            if (n >= a.nf) continue;
-            e.dst = origin_ptr(dst[first + n]), e.src = origin_ptr(src[first + n]);
-            item_strides(dst[first + n], elem_size, e.d), item_strides(src[first + n], elem_size, e.s);
-        }
-        if (elem_size == 8 && edge_elem_size == 8) remap_launch_method<double, double>(a, blocks, method, stream);
-        else if (elem_size == 8) remap_launch_method<double, float>(a, blocks, method, stream);
-        else if (edge_elem_size == 8) remap_launch_method<float, double>(a, blocks, method, stream);
-        else remap_launch_method<float, float>(a, blocks, method, stream);
+    int next = 0;
+    while (next_pair_batch(a, dst, src, &next, nfields, elem_size)) {
+        with_item_type(elem_size, [&](auto t) {
+            with_item_type(edge_elem_size, [&](auto e) {
+                using T = decltype(t);
+                using E = decltype(e);
+                if (method == GT4MI_REMAP_PLM) remap_launch<T, E, GT4MI_REMAP_PLM>(a, blocks, stream);
+                else remap_launch<T, E, GT4MI_REMAP_PCM>(a, blocks, stream);
+            });
+        });
         GT4MI_HIP_CHECK(hipGetLastError());
     }
     return GT4MI_OK;

@@ -106,3 +106,26 @@ def test_no_shipped_hot_kernel_spills():
     for shape in ("tridiag_pipe_kernelIdLi104ELi40ELi4E", "tridiag_pipe_kernelIdLi80ELi40ELi8E"):  # 104 + 40 and 80 + 40 levels
         deep = [v for n, v in hot.items() if shape in n]
         assert len(deep) == 1 and all(w == 1 for _, w in deep), (shape, deep)
+
+
+def test_pair_batch_plumbing_is_clean_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+    """What the pair entries share after their checks (csrc/field_args.hip.h: next_pair_batch, shared_field, with_pair_entries,
+    with_item_type) is host code that writes into the fixed-size argument block of a launch.  tests/selftest_pair_batch.hip runs
+    it as a stand-alone program, for 1, 4, 5, 8, 9, 16 and 17 pairs from every start and in every axis order, on descriptor arrays exactly as large
+    as the call says, under -fsanitize=address,undefined with recovery off.  No GPU and no HIP call."""
+    import shutil
+    import subprocess
+
+    hipcc = shutil.which("hipcc") or shutil.which("hipcc", path="/opt/rocm/bin")
+    if hipcc is None:
+        pytest.skip("no hipcc")
+    root = pathlib.Path(__file__).resolve().parent.parent
+    exe = tmp_path / "selftest_pair_batch"
+    build = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-Xarch_host", "-fsanitize=address,undefined",
+                            "-Xarch_host", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", f"-I{root / 'gt4py_amd' / 'csrc'}",
+                            f"-I{root / 'include'}", str(root / "tests" / "selftest_pair_batch.hip"), "-o", str(exe)],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "clean under the sanitizers" in run.stdout, (run.stdout + run.stderr)[-2000:]
+    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr

@@ -1,14 +1,16 @@
-"""The refusals of the six multi-field utility entries (``gt4mi_halo_fill``, ``gt4mi_field_stats``, ``gt4mi_level_stats``,
-``gt4mi_field_copy``, ``gt4mi_vertical_remap``, ``gt4mi_horizontal_interp``), byte for byte, without a GPU.
+"""The refusals of the eight multi-field utility entries (``gt4mi_halo_fill``, ``gt4mi_field_stats``, ``gt4mi_level_stats``,
+``gt4mi_field_copy``, ``gt4mi_vertical_remap``, ``gt4mi_horizontal_interp``, ``gt4mi_horizontal_remap``, ``gt4mi_line_solve``), byte
+for byte, without a GPU.
 
 The entries share their per-field checks (csrc/field_args.hip.h); what a call is refused with -- return code and the bytes of
-``gt4mi_last_error()`` -- and what an accepted call reports (``launches``, ``paths``, ``workspace_needed``) is behaviour, and
+``gt4mi_last_error()`` -- and what an accepted call reports (``launches``, ``paths`` / ``path``, ``workspace_needed``) is behaviour, and
 tests/golden/refusal_messages.json records it for a table of calls.  The table is generated: for every role of every entry
-(dst, src, edge and position fields, field and other) the same mutations of one base call -- null, misaligned, a stride that is
+(dst, src, edge, position and coefficient fields, field and other) the same mutations of one base call -- null, misaligned, a stride that is
 no multiple of the item size, stride 0 with an extent above 1 and of exactly 1, origins and shapes around every bound -- then
-the overlaps, the buffers of the stats entries, and accepted calls of 1, 8 and 9 fields.  Every call carries made-up device
-addresses and the entry's dry-run flag, so nothing is launched (the one exception: a stats call WITHOUT its buffers is only
-refused when it is not a dry run; the refusal is what keeps it from the GPU).
+the overlaps, the buffers of the stats entries, the overlap tables of horizontal_remap, the axes, flags and workspace of
+line_solve, and accepted calls of 1, 8 and 9 fields.  Every call carries made-up device addresses and the entry's dry-run flag, so
+nothing is launched (the one exception: a stats or line_solve call WITHOUT its buffers is only refused when it is not a dry run;
+the refusal is what keeps it from the GPU).
 
 The fixture is recorded from a build of the commit BEFORE a change to the checks, never from the code under test:
 
@@ -62,6 +64,7 @@ class Entry:
     name = ""
     roles = ()       # (role, written, axes that may be broadcast)
     nk = {}          # role -> levels of its fields
+    pair = None      # (written role, read role) of an entry that takes pairs and refuses a written box that meets anything read
 
     def base(self, n=1):
         state = {role: [_spec((r + 1) * 0x100000 + k * 0x2000, self.nk[role]) for k in range(n if self.many(role) else 1)]
@@ -127,6 +130,7 @@ class FieldCopy(Entry):
     name = "field_copy"
     roles = (("dst", True, ()), ("src", False, ()))
     nk = {"dst": 4, "src": 4}
+    pair = ("dst", "src")
 
     def run(self, s):
         launches = ctypes.c_int(77)
@@ -142,6 +146,7 @@ class VerticalRemap(Entry):
     name = "vertical_remap"
     roles = (("dst", True, ()), ("src", False, ()), ("src_edges", False, (0, 1)), ("dst_edges", False, (0, 1)))
     nk = {"dst": 6, "src": 6, "src_edges": 6, "dst_edges": 6}
+    pair = ("dst", "src")
 
     def many(self, role):
         return role in ("dst", "src")
@@ -168,6 +173,7 @@ class HorizontalInterp(Entry):
     name = "horizontal_interp"
     roles = (("dst", True, ()), ("src", False, ()), ("pos_i", False, (2,)), ("pos_j", False, (2,)))
     nk = {"dst": 4, "src": 4, "pos_i": 4, "pos_j": 4}
+    pair = ("dst", "src")
 
     def many(self, role):
         return role in ("dst", "src")
@@ -189,7 +195,77 @@ class HorizontalInterp(Entry):
         return [rc, launches.value]
 
 
-ENTRIES = (HaloFill(), Stats("field_stats"), Stats("level_stats"), FieldCopy(), VerticalRemap(), HorizontalInterp())
+TABLES = 0x6000000
+TABLE_ARRAYS = ("ptr", "cell", "w", "h", "c", "den")
+
+
+class HorizontalRemap(Entry):
+    """extent stands for (nd_i, nd_j, nk); ns = nd + 1 unless nd == 1 (then 1), so that the two sides differ.  The six arrays of
+    an axis are made-up device addresses like the fields: the host entry checks them and never reads through them.
+    ``state["axis_i"]`` / ``["axis_j"]``: members that replace those of the axis the extent gives, or None for a null axis."""
+
+    name = "horizontal_remap"
+    roles = (("dst", True, ()), ("src", False, ()))
+    nk = {"dst": 4, "src": 4}
+    pair = ("dst", "src")
+
+    def base(self, n=1):
+        state = super().base(n)
+        state.update(axis_i={}, axis_j={}, method=_lib.HREMAP_PLM, flags=_lib.HREMAP_DRY_RUN)
+        return state
+
+    def cells(self, state, ax):
+        nd = state["extent"][ax]
+        return (1 if nd == 1 else nd + 1), nd
+
+    def box(self, state, role):
+        ext = [self.cells(state, ax)[role == "dst"] for ax in (0, 1)] + [state["extent"][2]]
+        return ext, [0, 0, 0], [0, 0, 0]
+
+    def axis(self, state, ax):
+        over = state["axis_" + "ij"[ax]]
+        if over is None:
+            return None
+        ns, nd = self.cells(state, ax)
+        members = {"ns": ns, "nd": nd, "nnz": ns + nd - 1}
+        members.update({a: TABLES + ax * 0x100000 + n * 0x10000 for n, a in enumerate(TABLE_ARRAYS)})
+        members.update(over)
+        return ctypes.byref(_lib.OverlapAxis(**members))
+
+    def run(self, s):
+        launches = ctypes.c_int(77)
+        rc = _lib.load().gt4mi_horizontal_remap(_table(s["dst"]), _table(s["src"]), s["n"], self.axis(s, 0), self.axis(s, 1),
+                                                s["extent"][2], SIZE, s["method"], s["flags"], None, ctypes.byref(launches))
+        return [rc, launches.value]
+
+
+class LineSolve(Entry):
+    """The base call solves along K (lanes along I); ``state["axis"]`` moves the line axis.  A run reports ``launches``,
+    ``workspace_needed`` and ``path``."""
+
+    name = "line_solve"
+    roles = (("out", True, ()), ("rhs", False, ()), ("lower", False, (0, 1)), ("diag", False, (0, 1)), ("upper", False, (0, 1)))
+    nk = {"out": 4, "rhs": 4, "lower": 4, "diag": 4, "upper": 4}
+    pair = ("out", "rhs")
+
+    def many(self, role):
+        return role in ("out", "rhs")
+
+    def base(self, n=1):
+        state = super().base(n)
+        state.update(axis=2, flags=_lib.LINE_DRY_RUN, workspace=WORK, workspace_bytes=1 << 20)
+        return state
+
+    def run(self, s):
+        needed, path, launches = ctypes.c_int64(-5), ctypes.c_int(55), ctypes.c_int(77)
+        rc = _lib.load().gt4mi_line_solve(_table(s["out"]), _table(s["rhs"]), s["n"], _one(s["lower"]), _one(s["diag"]), _one(s["upper"]),
+                                          _i64(s["extent"]), s["axis"], SIZE, s["flags"], s["workspace"], s["workspace_bytes"], None,
+                                          ctypes.byref(needed), ctypes.byref(path), ctypes.byref(launches))
+        return [rc, launches.value, needed.value, path.value]
+
+
+ENTRIES = (HaloFill(), Stats("field_stats"), Stats("level_stats"), FieldCopy(), VerticalRemap(), HorizontalInterp(), HorizontalRemap(),
+           LineSolve())
 
 
 def _field_cases(entry, role):
@@ -230,28 +306,32 @@ def _field_cases(entry, role):
 
 
 def _overlap_cases():
-    for entry in ENTRIES[3:]:
-        for a, b in (("dst0", "src0"), ("dst1", "src0"), ("dst0", "src2"), ("dst0", "dst1"), ("dst1", "dst2"), ("dst2", "src2")):
+    for entry in ENTRIES:
+        if entry.pair is None:
+            continue
+        w, r = entry.pair  # the written and the read role: "dst" / "src", or "out" / "rhs"
+        for a, b in (((w, 0), (r, 0)), ((w, 1), (r, 0)), ((w, 0), (r, 2)), ((w, 0), (w, 1)), ((w, 1), (w, 2)), ((w, 2), (r, 2))):
             for gap in (0, 8):  # the last byte of one box against the first of the other: touching, and one item apart
                 state = entry.base(3)
-                fa, fb = state[a[:3]][int(a[3])], state[b[:3]][int(b[3])]
-                extent, lo, hi = entry.box(state, b[:3])
+                fa, fb = state[a[0]][a[1]], state[b[0]][b[1]]
+                extent, lo, hi = entry.box(state, b[0])
                 first = sum((fb["origin"][ax] - lo[ax]) * fb["strides"][ax] for ax in AXES)
-                ext_a = entry.box(state, a[:3])[0]
+                ext_a = entry.box(state, a[0])[0]
                 last = sum((fa["origin"][ax] + ext_a[ax] - 1) * fa["strides"][ax] for ax in AXES)
                 fb["ptr"] = fa["ptr"] + last - first + gap
-                yield f"{entry.name}/overlap/{a}-{b}/gap={gap}", state
-        for role, _, _ in entry.roles[2:]:  # edge and position fields
+                yield f"{entry.name}/overlap/{a[0]}{a[1]}-{b[0]}{b[1]}/gap={gap}", state
+        for role, _, _ in entry.roles[2:]:  # edge, position and coefficient fields
             for k in (0, 2):
                 state = entry.base(3)
-                state[role][0]["ptr"] = state["dst"][k]["ptr"]
-                yield f"{entry.name}/overlap/dst{k}-{role}", state
-            # two at once: the sweep goes dst by dst, and for one dst the shared fields come before the srcs
+                state[role][0]["ptr"] = state[w][k]["ptr"]
+                yield f"{entry.name}/overlap/{w}{k}-{role}", state
+            # two at once: the sweep goes dst by dst, and for one dst the shared fields come before the srcs (in line_solve out 0
+            # on rhs 0 is an in-place pair and only the shared field is refused)
             for k in (0, 1):
                 state = entry.base(3)
-                state["src"][0]["ptr"] = state["dst"][0]["ptr"]
-                state[role][0]["ptr"] = state["dst"][k]["ptr"]
-                yield f"{entry.name}/overlap/dst0-src0+dst{k}-{role}", state
+                state[r][0]["ptr"] = state[w][0]["ptr"]
+                state[role][0]["ptr"] = state[w][k]["ptr"]
+                yield f"{entry.name}/overlap/{w}0-{r}0+{w}{k}-{role}", state
     # the reach of a src alone makes it meet a dst: the dst ends one row below src's box
     entry = ENTRIES[5]
     for reach in ([1, 2, 2, 1], [1, 2, 0, 1]):
@@ -316,6 +396,164 @@ def _buffer_cases():
         yield name, state
 
 
+def _origin_item(f):
+    return f["ptr"] + sum(f["origin"][ax] * f["strides"][ax] for ax in AXES)
+
+
+def _scalar_cases(entry):
+    """The head checks that the generic generators cannot reach."""
+    state = entry.base(2)
+    state["n"] = 0
+    yield f"{entry.name}/scalars/nfields=0", state
+    state = entry.base(2)
+    state["flags"] |= 2
+    yield f"{entry.name}/scalars/unknown-flag", state
+    for role in entry.pair:
+        state = entry.base(2)
+        state[role] = None
+        yield f"{entry.name}/scalars/{role}-table-null", state
+
+
+def _horizontal_remap_cases():
+    entry = ENTRIES[6]
+
+    def variant(name, n=2):
+        return f"{entry.name}/tables/{name}", entry.base(n)
+
+    yield from _scalar_cases(entry)
+    for method in (_lib.HREMAP_PCM, _lib.HREMAP_PLM, 2):
+        name, state = variant(f"method={method}")
+        state["method"] = method
+        yield name, state
+    for nk in (0, -1, 1):
+        name, state = variant(f"nk={nk}")
+        state["extent"][2] = nk
+        yield name, state
+    for ax in "ij":
+        key = "axis_" + ax
+        name, state = variant(f"{key}-null")
+        state[key] = None
+        yield name, state
+        ns, nd = entry.cells(state, 0)
+        for member in ("ns", "nd"):
+            for value in (0, -1):
+                name, state = variant(f"{key}/{member}={value}")
+                state[key] = {member: value, "nnz": 1}
+                yield name, state
+        for tag, nnz in (("nd-1", nd - 1), ("nd", nd), ("ns+nd-1", ns + nd - 1), ("ns+nd", ns + nd)):
+            name, state = variant(f"{key}/nnz={tag}")
+            state[key] = {"nnz": nnz}
+            yield name, state
+        # with pcm the kernel does not read h, c and den, and the entry must not look at them
+        for mname, method in (("pcm", _lib.HREMAP_PCM), ("plm", _lib.HREMAP_PLM)):
+            for n, array in enumerate(TABLE_ARRAYS):
+                name, state = variant(f"{key}/{array}-null/{mname}")
+                state["method"], state[key] = method, {array: 0}
+                yield name, state
+                name, state = variant(f"{key}/{array}-misaligned/{mname}")
+                state["method"], state[key] = method, {array: TABLES + n * 0x10000 + (2 if n < 2 else 4)}
+                yield name, state
+                for k in (0, 2):  # a dst that meets a table array
+                    name, state = variant(f"{key}/{array}-on-dst{k}/{mname}", 3)
+                    state["method"], state[key] = method, {array: _origin_item(state["dst"][k])}
+                    yield name, state
+    # every array of one axis null at once: the first one is named
+    name, state = variant("axis_j/all-null")
+    state["axis_j"] = {array: 0 for array in TABLE_ARRAYS}
+    yield name, state
+
+
+def _line_solve_cases():
+    entry = ENTRIES[7]
+
+    def variant(name, n=2):
+        return f"{entry.name}/{name}", entry.base(n)
+
+    yield from _scalar_cases(entry)
+    for role in ("lower", "diag", "upper"):
+        name, state = variant(f"scalars/{role}-null")
+        state[role] = None
+        yield name, state
+    for axis in (-1, 3):
+        name, state = variant(f"scalars/axis={axis}")
+        state["axis"] = axis
+        yield name, state
+    # in place: out[k] IS rhs[k], the same origin item and the same strides
+    name, state = variant("inplace/every-pair")
+    state["rhs"] = copy.deepcopy(state["out"])
+    yield name, state
+    name, state = variant("inplace/out0-is-rhs1")
+    state["rhs"][1] = copy.deepcopy(state["out"][0])
+    yield name, state
+    name, state = variant("inplace/out0-on-rhs0-other-strides")  # the same origin item, I and J exchanged
+    state["rhs"][0] = copy.deepcopy(state["out"][0])
+    state["rhs"][0]["strides"] = [8 * SIZE, SIZE, 64 * SIZE]
+    yield name, state
+    name, state = variant("inplace/out0-on-rhs0-other-origin")  # the same strides, one item along
+    state["rhs"][0] = copy.deepcopy(state["out"][0])
+    state["rhs"][0]["origin"] = [3, 2, 0]
+    yield name, state
+    for axis in AXES:
+        for periodic in (0, _lib.LINE_PERIODIC):
+            tag = f"axis={axis}/periodic={periodic}"
+            name, state = variant(f"accepted/{tag}")
+            state["axis"], state["flags"] = axis, state["flags"] | periodic
+            yield name, state
+            for points in (0, 1, 2, 3):  # a periodic line needs 3 points; an empty box is accepted before that is asked
+                name, state = variant(f"points={points}/{tag}")
+                state["axis"], state["flags"] = axis, state["flags"] | periodic
+                state["extent"][axis] = points
+                yield name, state
+    # one call per path, as field_copy/accepted/paths: the line axis with unit stride, another one, none
+    name, state = variant("accepted/path=tiles")
+    state["axis"] = 0
+    yield name, state
+    name, state = variant("accepted/path=lanes")
+    yield name, state
+    name, state = variant("accepted/path=lanes-along-k")  # K fastest, the lines along I: the lanes run along K
+    for role, _, _ in entry.roles:
+        for f in state[role]:
+            f["strides"] = [4 * 8 * SIZE, 4 * SIZE, SIZE]
+    state["axis"] = 0
+    yield name, state
+    name, state = variant("accepted/path=items")
+    state["out"][1]["strides"] = [2 * SIZE, 16 * SIZE, 128 * SIZE]  # no unit stride
+    state["out"][1]["ptr"] = 0x3000000
+    yield name, state
+    name, state = variant("accepted/path=tiles-1d-coefficients")  # a coefficient broadcast along the two other axes
+    state["axis"] = 0
+    for role in ("lower", "diag", "upper"):
+        state[role][0]["strides"] = [SIZE, 0, 0]
+    yield name, state
+    # the workspace
+    for periodic in (0, _lib.LINE_PERIODIC):
+        tag = f"periodic={periodic}"
+        name, state = variant(f"workspace/null-dry/{tag}")
+        state["workspace"], state["flags"] = None, state["flags"] | periodic
+        yield name, state
+        # NOT a dry run, as in the stats entries the only such call: a missing workspace is refused only then, and the refusal is
+        # all that keeps these made-up addresses from the device
+        name, state = variant(f"workspace/null/{tag}")
+        state["workspace"], state["flags"] = None, periodic
+        yield name, state
+        for short in (0, 8):
+            name, state = variant(f"workspace/short-by-{short}/{tag}")
+            state["flags"] |= periodic
+            state["workspace_bytes"] = entry.run(copy.deepcopy(state))[2] - short
+            yield name, state
+    name, state = variant("workspace/misaligned")
+    state["workspace"] += 4
+    yield name, state
+    for role, _, _ in entry.roles:
+        for k in range(2 if entry.many(role) else 1):
+            name, state = variant(f"workspace/overlaps-{role}{k}")
+            state["workspace"] = _origin_item(state[role][k])
+            yield name, state
+            name, state = variant(f"workspace/ends-at-{role}{k}")  # its last byte is the one before the box
+            state["workspace"] = _origin_item(state[role][k]) - entry.run(entry.base(2))[2]
+            yield name, state
+
+
 def _accepted_cases():
     for entry in ENTRIES:
         for n in (1, 8, 9):
@@ -334,12 +572,12 @@ def cases():
         for role, _, _ in entry.roles:
             yield from ((name, entry, state) for name, state in _field_cases(entry, role))
     by_name = {e.name: e for e in ENTRIES}
-    for gen in (_overlap_cases, _buffer_cases, _accepted_cases):
+    for gen in (_overlap_cases, _buffer_cases, _accepted_cases, _horizontal_remap_cases, _line_solve_cases):
         yield from ((name, by_name[name.split("/")[0]], state) for name, state in gen())
 
 
 def observe():
-    """name -> [return code, message, launches (, paths or workspace_needed)]; the message of an accepted call is not looked at
+    """name -> [return code, message, launches (, paths or workspace_needed (, path))]; the message of an accepted call is not looked at
     (``gt4mi_last_error`` keeps the last refusal)."""
     out = {}
     lib = _lib.load()
@@ -363,7 +601,7 @@ def test_the_table_reaches_every_branch():
                 assert any(m.startswith(who) and needle in m for m in seen), (who, needle)
             if written or role == "field":
                 assert any(m.startswith(who) and "has stride 0 along axis" in m for m in seen), who
-    for name in ("field_copy", "vertical_remap", "horizontal_interp"):
+    for name in ("field_copy", "vertical_remap", "horizontal_interp", "horizontal_remap"):
         for needle in ("dst 0 and src 0 overlap", "dst 1 and src 0 overlap", "dst 0 and src 2 overlap", "dst 0 and dst 1 overlap",
                        "dst 1 and dst 2 overlap"):
             assert any(m.startswith(name) and needle in m for m in seen), (name, needle)
@@ -374,6 +612,30 @@ def test_the_table_reaches_every_branch():
         for needle in ("workspace is null", "result is null", "is too small", "workspace is not aligned", "result is not aligned",
                        "workspace overlaps field 1", "result overlaps other 0", "workspace overlaps result"):
             assert any(m.startswith(name) and needle in m for m in seen), (name, needle)
+    for needle in ("axis_i is null", "axis_j is null", "axis_i has ns = 0 source", "axis_j has ns = 5 source and nd = -1 destination",
+                   "axis_i has nnz = 3 terms", "axis_j has nnz = 9 terms", "nk = 0 levels", "unknown method 2", "unknown bits in flags",
+                   "nfields = 0", *(f"axis_{ax} {array} is null" for ax in "ij" for array in TABLE_ARRAYS),
+                   *(f"axis_{ax} {array} is not aligned to its item size" for ax in "ij" for array in TABLE_ARRAYS),
+                   *(f"dst {k} and axis_{ax} {array} overlap" for k in (0, 2) for ax in "ij" for array in TABLE_ARRAYS)):
+        assert any(m.startswith("horizontal_remap: ") and needle in m for m in seen), needle
+    for needle in ("out 0 and rhs 0 overlap", "out 1 and rhs 0 overlap", "out 0 and rhs 2 overlap", "out 0 and out 1 overlap",
+                   "out 1 and out 2 overlap", "out 0 and rhs 1 overlap", "out 0 and lower overlap", "out 2 and diag overlap",
+                   "out 1 and upper overlap", "lower is null", "diag is null", "upper is null", "out is null", "rhs is null",
+                   "axis -1 is not 0 (I), 1 (J) or 2 (K)", "axis 3 is not", "a periodic line needs at least 3 points, the extent along axis 0 is 2",
+                   "the extent along axis 1 is 1", "the extent along axis 2 is 2", "workspace is null", "is too small", "nfields = 0",
+                   "unknown bits in flags", "workspace is not aligned to 8 bytes", "workspace overlaps out 1", "workspace overlaps rhs 0",
+                   "workspace overlaps lower", "workspace overlaps diag", "workspace overlaps upper"):
+        assert any(m.startswith("line_solve: ") and needle in m for m in seen), needle
+    # what accepted line_solve calls report: every path, and a periodic workspace twice the plain one
+    cases = json.loads(GOLDEN.read_text())["cases"]
+    assert {cases[f"line_solve/accepted/path={p}"][-1] for p in ("lanes", "tiles", "items")} == \
+        {_lib.LINE_PATH_LANES, _lib.LINE_PATH_TILES, _lib.LINE_PATH_ITEMS}
+    for axis in AXES:
+        plain, periodic = (cases[f"line_solve/accepted/axis={axis}/periodic={p}"] for p in (0, _lib.LINE_PERIODIC))
+        assert plain[0] == periodic[0] == 0 and plain[3] > 0 and periodic[3] == 2 * plain[3]
+    for array in ("h", "c", "den"):  # pcm does not look at them
+        for what in ("null", "misaligned", "on-dst0"):
+            assert cases[f"horizontal_remap/tables/axis_i/{array}-{what}/pcm"][0] == 0
 
 
 def test_every_refusal_and_every_accepted_call_is_what_the_fixture_recorded():
