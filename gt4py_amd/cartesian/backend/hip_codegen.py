@@ -46,46 +46,25 @@ from .. import analysis, ir
 Extent2 = analysis.Extent2
 
 
-def _env_tuple(name: str, default: Tuple[int, ...]) -> Tuple[int, ...]:
-    import os
-
-    text = os.environ.get(name)
-    return tuple(int(x) for x in text.split(",")) if text else default
-
-
-#: launch geometry / unrolling of the generated kernels, from the sweep in
-#: profiles/r1_codegen_sweep.log (env overrides are for tuning experiments)
+#: launch geometry / unrolling of the generated kernels, from the sweep in profiles/r1_codegen_sweep.log.  Plain
+#: numbers: experiments patch them in-process.  The switches between whole emission paths that used to sit here
+#: were settled by measurement; each finding is quoted in the docstring of the function that emits the shipped path.
 TUNING = {
-    # threads along I, J; K levels per thread; consecutive J rows per thread (unrolled: the compiler
-    # then shares the row loads and the recomputed temporaries between neighbouring rows)
-    "block_ijk": _env_tuple("GT4MI_CODEGEN_BLOCK_IJK", (64, 4, 1, 1)),
-    "block_column": _env_tuple("GT4MI_CODEGEN_BLOCK_COLUMN", (64, 4)),
-    "unroll": _env_tuple("GT4MI_CODEGEN_UNROLL", (8,))[0],  # sequential K loops
-    # XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (private L2s); with R > 0 each
-    # XCD gets runs of R consecutive tile rows, so rows shared by neighbouring tiles hit in one L2
-    # (measured neutral-to-negative for thread-per-point kernels, profiles/r1_codegen_sweep.log: off)
-    "xcd_rows": _env_tuple("GT4MI_CODEGEN_XCD_ROWS", (0,))[0],
-    "nontemporal": _env_tuple("GT4MI_CODEGEN_NONTEMPORAL", (1,))[0],  # streaming stores for write-only outputs
+    "block_ijk": (64, 4),  # threads along I, J of the thread-per-point kernels
+    "block_column": (64, 4),
+    "unroll": 8,  # sequential K loops
     # column stages: issue the loads of up to this many K levels ahead of the dependent arithmetic (0 = off),
     # as long as the chunk needs no more than `prefetch_loads` values in flight per thread
-    "prefetch": _env_tuple("GT4MI_CODEGEN_PREFETCH", (8,))[0],
-    "prefetch_loads": _env_tuple("GT4MI_CODEGEN_PREFETCH_LOADS", (40,))[0],
-    "vector": _env_tuple("GT4MI_CODEGEN_VECTOR", (1,))[0],  # 16-byte lanes for horizontal stages
-    # ... and consecutive J rows per lane in those kernels: rows (and recomputed temporaries) shared by
-    # neighbouring output rows are loaded (computed) once per strip
-    "vector_rows": _env_tuple("GT4MI_CODEGEN_VECTOR_ROWS", (4,))[0],
-    # strip kernels of stages whose temporaries were inlined: compute every temporary ONCE per point and pass it to the
-    # neighbouring lanes with DPP shifts (waves overlap by a halo lane or two) instead of re-deriving it at every
-    # offset it is read at (1), or only the recomputing form (0)
-    "shared_temporaries": _env_tuple("GT4MI_CODEGEN_SHARED_TEMPORARIES", (1,))[0],
-    # J rows per lane of that kernel (0 = by element size: 4 rows for 8-byte elements, 8 for 4-byte ones) and its XCD-aware
-    # tile order (see xcd_rows).  Measured on the horizontal diffusion with XCD runs of 4, fp64 / fp32 GLUPS: rows 4 / 5 / 6 /
-    # 7 / 8 = 226 / 221 / 218 / 212 / 219 and 386 / 390 / 403 / 410 / 424; runs of 2 / 4 / 8 tile rows differ by < 1 %, no
-    # grouping costs 2 % (profiles/r2_codegen_shared_rows_xcd.log, r2_codegen_shared_xcd.log)
-    "shared_rows": _env_tuple("GT4MI_CODEGEN_SHARED_ROWS", (0,))[0],
-    "shared_xcd_rows": _env_tuple("GT4MI_CODEGEN_SHARED_XCD_ROWS", (4,))[0],
+    "prefetch": 8,
+    "prefetch_loads": 40,
+    # 16-byte-lane kernels of horizontal stages: consecutive J rows per lane -- rows (and recomputed temporaries) shared
+    # by neighbouring output rows are loaded (computed) once per strip
+    "vector_rows": 4,
+    # XCD-aware tile order of the `_vecs` kernels (gt_tile): each XCD gets runs of this many consecutive tile rows
+    "shared_xcd_rows": 4,
     # two-sweep column stages (stage_planner.TopCache): levels of the forward sweep's results kept in registers and,
-    # below those, in LDS for the backward sweep -- (register levels, LDS bytes per workgroup, cap on the LDS levels).
+    # below those, in LDS for the backward sweep -- (register levels, LDS bytes per workgroup, cap on the LDS levels;
+    # a shorter tuple is padded with 0, 0, 64).
     # Register levels < 0 (the default): one `_tc<n>` kernel per depth n = n_max, n_max - 8, n_max - 8 - step, ... and 16,
     # where n_max is what `top_cache_auto` = (register budget in dwords per lane, step in levels) allows for the cached
     # fields of the stage (vertical advection: 2 fp64 fields = 4 dwords per level -> 112, 104, 80, 56, 32, 16 levels + 40
@@ -95,34 +74,9 @@ TUNING = {
     # (hip_generic._Variant).  A lone wave per SIMD owns 512 registers; a cached level costs exactly its dwords once the
     # register levels are pinned (_pin_register_level) and the second sweep has its own bases (_second_sweep_bases) --
     # before that it cost three times as much and 24 levels already spilled (profiles/r2_codegen_top_cache_deep_*.log).
-    # (0, 0) = off; an explicit depth (GT4MI_CODEGEN_TOP_CACHE=80,163840) emits that one variant only.
-    "top_cache": _env_tuple("GT4MI_CODEGEN_TOP_CACHE", (-1, 160 * 1024, 64)),
-    "top_cache_auto": _env_tuple("GT4MI_CODEGEN_TOP_CACHE_AUTO", (448, 24)),
-    # register levels of a `_tc` kernel: 0 = batches, each batch's loads right before its own arithmetic; 1 = the loads
-    # of batch n + 1 issued before the arithmetic of batch n (+1..3 %, but a second batch of registers: as much as 10
-    # cached levels are worth, profiles/r2_codegen_top_cache_pipeline.log); 2 = rolling: level n issues the loads of
-    # level n + D and computes itself, D levels of loads always in flight for the registers of ONE more level --
-    # vertical advection +8 % at equal depth, +3..5 % with the ladder (its 112-level variant no longer fits, 104 runs),
-    # the generated tridiagonal solve unchanged (profiles/r2_codegen_top_cache_rolling.log, _onchip.log).
-    "top_cache_pipeline": _env_tuple("GT4MI_CODEGEN_TOP_CACHE_PIPELINE", (2,))[0],
-    "top_cache_lookahead": _env_tuple("GT4MI_CODEGEN_TOP_CACHE_LOOKAHEAD", (0,))[0],  # rolling prefetch distance (0: chunk depth)
-    # the LDS levels of a `_tc` kernel as straight-line code like the register levels (1) or as a loop (0): within the
-    # noise at K = 160 / 80 / 60 for 5x the source (profiles/r2_codegen_top_cache_onchip.log)
-    "top_cache_unroll_lds": _env_tuple("GT4MI_CODEGEN_TOP_CACHE_UNROLL_LDS", (0,))[0],
-    # `_tc` kernels: streaming (nontemporal) stores for what the kernel itself never reads back from memory -- the
-    # second sweep's results, and the store-through copies of cached in/out fields at the levels that stay on chip
-    "top_cache_streaming": _env_tuple("GT4MI_CODEGEN_TOP_CACHE_STREAMING", (1,))[0],
-    # column kernels: nontemporal LOADS for what a column kernel reads exactly once (level after level, planes apart: nothing worth
-    # keeping in the L1).  0 = plain loads; 1 = every load from memory; 2 = only of fields the stage reads at no horizontal offset;
-    # 3 = ... that, moreover, only ONE of the stage's sweeps reads from memory; 4 = ... and that the stage does not write;
-    # 5 (default) = 3 + fields BOTH sweeps read and nobody writes: cacheable in the first sweep, nontemporal in the last (their last use).
-    # Same process, same fields, 1024 x 1024 x 160 fp64 (profiles/r5_nt_loads_column_kernels.txt): vertical advection 0.588 (0) /
-    # 0.557 (1) / 0.584 (2) / **0.631 (3)** / 0.586 (4) of the HBM peak -- `u_pos`, which both sweeps read, must stay cacheable --;
-    # generated tridiagonal solve 0.686 / 0.730 / 0.730 / **0.730** / 0.698; hand-written solve (tridiag_stack.hip.h NTL) +5-9 %.
-    # 5 against 3 on another box: vertical advection 0.6456 -> 0.6476 (0.605 plain), the solve unchanged.
-    "column_nt_loads": _env_tuple("GT4MI_CODEGEN_COLUMN_NT_LOADS", (5,))[0],
-    # ... and in the 16-byte-lane strip kernels of horizontal stages: the arrays the stage reads at its own point only (_read_once_fields)
-    "strip_nt_loads": _env_tuple("GT4MI_CODEGEN_STRIP_NT_LOADS", (1,))[0],
+    # (0, 0) = off; an explicit depth, (80, 163840), emits that one variant only.
+    "top_cache": (-1, 160 * 1024, 64),
+    "top_cache_auto": (448, 24),
 }
 
 from .stage_planner import (Nest, Plan, Stage, Stmt, UnsupportedStencil, _field_reads, _stmt_field_reads,  # noqa: F401
@@ -326,8 +280,6 @@ class KernelSource:
     mapping: str
     extent: Extent2
     block: Tuple[int, int, int]
-    k_per_thread: int = 1
-    j_per_thread: int = 1
     vec: int = 0  # > 0: a `<name>_vec` kernel exists in which every lane owns `vec` consecutive I points
     vec_fields: Tuple[str, ...] = ()  # arrays whose alignment / strides decide whether it may be launched
     vec_rows: int = 1  # consecutive J rows per lane in the `_vec` kernel
@@ -379,8 +331,8 @@ class _Emitter:
         self.written = {s.target.name for _, _, s in plan.stencil.statements()}
         read = {e.name for _, _, s in plan.stencil.statements() for e in ir.stmt_reads(s) if isinstance(e, ir.FieldAccess)}
         api = {f.name for f in plan.api_fields}
-        # outputs nobody reads back: keep them out of the caches
-        self.streaming = (self.written & api) - read if TUNING["nontemporal"] else set()
+        # outputs nobody reads back: streaming (nontemporal) stores keep them out of the caches
+        self.streaming = (self.written & api) - read
         # state of the 16-byte-lane emission (vector_kernel)
         self.vec_rows: Optional[Dict[Tuple[str, int, int], Dict[int, str]]] = None
         self.vec_component = 0
@@ -584,7 +536,7 @@ class _Emitter:
         """In a `_tc` kernel: may this store bypass the caches?  Yes for a level the kernel never loads again: any store
         of the second sweep to a field that sweep does not read at another level, and the first sweep's store-through
         copy of a cached field at a level that stays on chip (the second sweep reads the slot, not memory)."""
-        if self.tc is None or not TUNING["top_cache_streaming"] or name in self.plan.scratch:
+        if self.tc is None or name in self.plan.scratch:
             return False
         first = self.tc[0].first_sweep_nests
         second_reads_elsewhere = any(
@@ -627,10 +579,7 @@ class _Emitter:
         cache, n_reg, n_lds, threads = self.tc
         c = _c_ident(name)
         if self.tc_mode[0] == "reg":
-            slot = self.tc_mode[1]
-            if slot < 0:  # an LDS level of the straight-line on-chip range (top_cache_unroll_lds): constant index
-                return f"tc_lds_{c}[{(slot + n_lds) * threads} + tc_tid]"
-            return f"tc_{c}_{slot}"
+            return f"tc_{c}_{self.tc_mode[1]}"
         return f"tc_lds_{c}[(({k}) - (a.dK - {n_reg + n_lds})) * {threads} + tc_tid]"
 
     def column_in_extent(self, name: str, stage: Stage) -> Optional[str]:
@@ -734,23 +683,19 @@ class _Emitter:
                         names.append(n)
         return names
 
-    def _kernel_header(self, stage: Stage, kname: str, block, j_per_thread: int) -> None:
-        """Signature, tile -> (i, j), base pointers of the fields the stage touches."""
+    def _kernel_header(self, stage: Stage, kname: str, block) -> None:
+        """Signature, tile -> (i, j), base pointers of the fields the stage touches.  The tile order is the hardware's
+        own (`gt_tile(0u, ...)`): giving each XCD runs of consecutive tile rows measured neutral-to-negative for
+        one-point-per-thread kernels (profiles/r1_codegen_sweep.log); only the strip kernels group (_strip_shape)."""
         L = self.lines
         (ilo, ihi), (jlo, jhi) = stage.extent
         L.append(f'extern "C" __global__ void __launch_bounds__({block[0] * block[1]}) {kname}(const gt_args a) {{')
         L.append("    unsigned gt_bx, gt_by, gt_bz;")
-        L.append(f"    gt_tile({TUNING['xcd_rows']}u, gt_bx, gt_by, gt_bz);")
+        L.append("    gt_tile(0u, gt_bx, gt_by, gt_bz);")
         L.append(f"    const gt_i64 i = (gt_i64)gt_bx * {block[0]} + threadIdx.x + ({ilo});")
         L.append(f"    if (i >= a.dI + ({ihi})) return;")
-        if j_per_thread > 1:
-            L.append("    #pragma unroll")
-            L.append(f"    for (int jv = 0; jv < {j_per_thread}; ++jv) {{")
-            L.append(f"    const gt_i64 j = ((gt_i64)gt_by * {block[1]} + threadIdx.y) * {j_per_thread} + jv + ({jlo});")
-            L.append(f"    if (j >= a.dJ + ({jhi})) break;")
-        else:
-            L.append(f"    const gt_i64 j = (gt_i64)gt_by * {block[1]} + threadIdx.y + ({jlo});")
-            L.append(f"    if (j >= a.dJ + ({jhi})) return;")
+        L.append(f"    const gt_i64 j = (gt_i64)gt_by * {block[1]} + threadIdx.y + ({jlo});")
+        L.append(f"    if (j >= a.dJ + ({jhi})) return;")
         for n in self.stage_globals(stage):
             if n in self.plan.register_only:
                 continue
@@ -820,7 +765,9 @@ class _Emitter:
     def _column_body(self, si: int, stage: Stage) -> None:
         """Thread per column: the nests of the stage one after the other, K serial per thread.  With ``self.tc`` set
         (the `_tc` variant of a two-sweep stage) every nest is cut into up to three ranges of levels -- memory, LDS,
-        registers -- and the cached fields are stored / read where the level lives (stage_planner.TopCache)."""
+        registers -- and the cached fields are stored / read where the level lives (stage_planner.TopCache).  The LDS
+        levels are a loop: emitting them as straight-line code like the register levels was within the noise at
+        K = 160 / 80 / 60 for 5x the source (profiles/r2_codegen_top_cache_onchip.log)."""
         L = self.lines
         stage_fwd = {n: d for (s_i, n), d in self.plan.forwarded.items() if s_i == si}
         for n in stage_fwd:  # r_<n>: the level behind the sweep, alive across the stage's nests
@@ -878,12 +825,9 @@ class _Emitter:
                 ranges = []  # in ascending order of levels
                 if lo_rel is None or lo_rel < -(n_reg + n_lds):
                     ranges.append((("mem",), "k0", f"gt_min(k1, a.dK - {n_reg + n_lds})"))
-                first_slot = 0
-                if n_lds and TUNING["top_cache_unroll_lds"]:
-                    first_slot = -n_lds  # the LDS levels are straight-line code too: slots -n_lds .. -1
-                elif n_lds and hi_rel > -(n_reg + n_lds) and (lo_rel is None or lo_rel < -n_reg):
+                if n_lds and hi_rel > -(n_reg + n_lds) and (lo_rel is None or lo_rel < -n_reg):
                     ranges.append((("lds",), f"gt_max(k0, a.dK - {n_reg + n_lds})", f"gt_min(k1, a.dK - {n_reg})"))
-                slots = [u for u in range(first_slot, n_reg) if -n_reg + u < hi_rel and (lo_rel is None or -n_reg + u >= lo_rel)]
+                slots = [u for u in range(n_reg) if -n_reg + u < hi_rel and (lo_rel is None or -n_reg + u >= lo_rel)]
                 if slots:
                     ranges.append((("reg", slots), None, None))
                 if nest.order is ir.LoopOrder.BACKWARD:
@@ -942,99 +886,34 @@ class _Emitter:
                 L.append(f"{pad}{'if (' + cond + ') ' if cond else ''}r_{c} = {load};")
 
     def _register_range(self, si: int, stage: Stage, nest: Nest, group, active, back: int, slots: Sequence[int], n_reg: int) -> None:
-        """The levels of a nest that live in register slots (compile-time indices): straight-line code, in sweep
-        order, in batches whose loads are issued ahead of the arithmetic exactly as in the loops (prefetch_chunk) -- and
-        one batch further: the loads of batch n + 1 are issued before the arithmetic of batch n, so that a lone wave per
-        SIMD always has a batch of loads in flight while it computes (hoisting them over the stores of batch n is safe
-        for the same reason hoisting within a batch is: prefetch_chunk only hoists reads of levels the sweep has not
-        stored yet)."""
+        """The levels of a nest that live in register slots (compile-time indices): straight-line code, in sweep order,
+        with a rolling prefetch: level n issues the loads of level n + D (D = the chunk depth of prefetch_chunk) and then
+        computes itself, so D levels of loads are always in flight and every level's arithmetic overlaps with them.
+        Hoisting them over the stores of the levels in between is safe for the same reason hoisting within a chunk is:
+        prefetch_chunk only hoists reads of levels the sweep has not stored yet.  Values the sweep already holds
+        (wcon[k + 1] of one level is wcon[k] of the next) are not fetched again.  Where prefetch_chunk gives no chunk, or
+        the nest runs statement by statement, nothing is hoisted: level by level.
+
+        Measured against batches of D levels, each batch's loads right before its own arithmetic: issuing the loads of
+        batch n + 1 before the arithmetic of batch n gave +1..3 %, but costs a second batch of registers -- as much as
+        10 cached levels are worth; rolling needs the registers of ONE more level: vertical advection +8 % at equal
+        depth, +3..5 % with the ladder of depths (its 112-level variant no longer fits, 104 runs), the generated
+        tridiagonal solve unchanged.  Prefetch distances of 2 .. 8 levels instead of the chunk depth: the chunk depth stays
+        the best.  (profiles/r2_codegen_top_cache_rolling.log and, named alike, _pipeline.log, _lookahead.log, _onchip.log;
+        r5_nt_loads_column_kernels.txt, section 10.)"""
         L = self.lines
         backward = nest.order is ir.LoopOrder.BACKWARD
         order = list(reversed(slots)) if backward else list(slots)
         self.tc_mode = ("reg", order[0])
         chunk = None if nest.split_statements else self.prefetch_chunk(group, stage, nest, active, back)
-        depth = chunk[0] if chunk is not None else 1
-        batches = [order[pos:pos + depth] for pos in range(0, len(order), depth)]
-        sign = "-" if backward else "+"
-
-        def base(batch) -> str:
-            return f"(a.dK - {n_reg - batch[0]})"
-
-        def full(batch) -> bool:
-            return chunk is not None and len(batch) == depth
-
-        nest_writes = {s.target.name for s in nest.stmts}
-        loaded: Dict[Tuple, str] = {}  # (field, (di, dj), slot of the level, data index) -> register that holds it
-
-        def issue_loads(bi: int) -> Dict[Tuple, str]:
-            """Declare and issue the hoisted loads of batch `bi` (names unique per batch: one scope holds them all).
-            A value an earlier batch of this range already fetched (wcon[k+1] of one batch is wcon[k] of the next)
-            is taken from its register when nothing in the nest writes the field."""
-            _, loads, _ = chunk
-            named = {}
-            self.tc_written = set()  # hoisted loads see what memory held BEFORE the batch's levels are assigned
-            for (name, off, rel, data), var in loads.items():
-                where = (name, off, batches[bi][0] + rel, data)  # slots count levels from a.dK - n_reg, in K order
-                if name not in nest_writes and where in loaded:
-                    named[(name, off, rel, data)] = loaded[where]
-                    continue
-                e = ir.FieldAccess(name, (off[0], off[1], rel), None, None, data)
-                L.append(f"            const {_CTYPE[self.decl_dtype[name].name]} q{bi}_{var} = {self.access(e, base(batches[bi]), -1, {})};")
-                named[(name, off, rel, data)] = loaded[where] = f"q{bi}_{var}"
-            return named
-
-        if chunk is not None and TUNING["top_cache_pipeline"] == 2:
-            self._register_range_rolling(si, stage, nest, group, active, back, order, n_reg, chunk, nest_writes)
-            return
-        L.append("        {")
-        pending = issue_loads(0) if full(batches[0]) and TUNING["top_cache_pipeline"] else None
-        for bi, batch in enumerate(batches):
-            # a fence per batch: otherwise the scheduler hoists the loads of ALL unrolled levels to the top of the
-            # straight-line region and runs out of registers
-            L.append("        __builtin_amdgcn_sched_barrier(0);")
-            named, pending = pending, None
-            if not TUNING["top_cache_pipeline"]:
-                named = issue_loads(bi) if full(batch) else None
-            elif bi + 1 < len(batches) and full(batches[bi + 1]):
-                pending = issue_loads(bi + 1)
-            if named is not None:
-                _, _, per_statement = chunk
-                for u, slot in enumerate(batch):
-                    step = -u if backward else u
-                    self.prefetch_for = {sid: {key: named[(key[0], key[1][:2], key[1][2] + step, key[2])] for key in keys}
-                                         for sid, keys in per_statement.items()}
-                    self.tc_mode = ("reg", slot)
-                    L.append("            {")
-                    self._emit_level(si, stage, nest, group, active, back, f"({base(batch)} {sign} {u})", "                ")
-                    L.append("            }")
-                    self._pin_register_level(slot)
-                self.prefetch_for = {}
-            else:  # the levels that do not fill a batch: one at a time
-                for u, slot in enumerate(batch):
-                    self.tc_mode = ("reg", slot)
-                    L.append("            {")
-                    self._emit_level(si, stage, nest, group, active, back, f"({base(batch)} {sign} {u})", "                ")
-                    L.append("            }")
-                    self._pin_register_level(slot)
-        L.append("        }")
-        L.append("        __builtin_amdgcn_sched_barrier(0);")
-
-    def _register_range_rolling(self, si: int, stage: Stage, nest: Nest, group, active, back: int, order: Sequence[int],
-                                n_reg: int, chunk, nest_writes: Set[str]) -> None:
-        """Register levels with a rolling prefetch: level n issues the loads of level n + D (D = the chunk depth of
-        prefetch_chunk) and then computes itself, so D levels of loads are always in flight and every level's arithmetic
-        overlaps with them -- the registers of one more level instead of a second batch buffer.  Values the sweep
-        already holds (wcon[k + 1] of one level is wcon[k] of the next) are not fetched again."""
-        L = self.lines
-        depth, _, per_statement = chunk
-        if TUNING["top_cache_lookahead"] > 0:
-            depth = int(TUNING["top_cache_lookahead"])
+        depth, per_statement = (chunk[0], chunk[2]) if chunk is not None else (0, {})
         keys = []  # (field, (di, dj, dk), data index) read through hoisted loads, in statement order
         for ks in per_statement.values():
             for key in ks:
                 if key not in keys:
                     keys.append(key)
-        loaded: Dict[Tuple, str] = {}
+        nest_writes = {s.target.name for s in nest.stmts}
+        loaded: Dict[Tuple, str] = {}  # (field, (di, dj), slot of the level, data index) -> register that holds it
 
         def kexpr(slot: int) -> str:
             return f"(a.dK - {n_reg - slot})"
@@ -1054,6 +933,8 @@ class _Emitter:
         for slot in order[:depth]:
             issue(slot)
         for n, slot in enumerate(order):
+            # a fence per level: otherwise the scheduler hoists the loads of ALL unrolled levels to the top of the
+            # straight-line region and runs out of registers
             L.append("        __builtin_amdgcn_sched_barrier(0);")
             if n + depth < len(order):
                 issue(order[n + depth])
@@ -1061,7 +942,9 @@ class _Emitter:
                                  for sid, ks in per_statement.items()}
             self.tc_mode = ("reg", slot)
             L.append("            {")
-            self._emit_level(si, stage, nest, group, active, back, kexpr(slot), "                ")
+            # (without a chunk the level is spelled as an offset of 0 from itself, as that path always spelled it)
+            level = kexpr(slot) if chunk is not None else f"({kexpr(slot)} {'-' if backward else '+'} 0)"
+            self._emit_level(si, stage, nest, group, active, back, level, "                ")
             L.append("            }")
             self._pin_register_level(slot)
         self.prefetch_for = {}
@@ -1074,17 +957,25 @@ class _Emitter:
         order the scheduler, not the selector).  All loads of all register levels would then stay live until the second
         sweep starts (measured: 12 registers per cached level instead of 4, spills from 24 levels on).  An empty
         volatile asm that takes the slots as inputs pins the arithmetic to the level it belongs to."""
-        if self.tc_sweep2 or not self.tc_written or slot < 0:  # (an LDS level's store is its own anchor)
+        if self.tc_sweep2 or not self.tc_written:
             return
         names = sorted(self.tc_written)
         constraints = ", ".join(f'"v"(tc_{_c_ident(n)}_{slot})' for n in names)
         self.lines.append(f"            asm volatile(\"\" :: {constraints});")
 
-    def _nt_load_fields(self, stage: Stage) -> Optional[Set[str]]:
-        """Fields of a column stage whose loads from memory are nontemporal (TUNING["column_nt_loads"])."""
-        mode = int(TUNING["column_nt_loads"])
-        if mode <= 0:
-            return None
+    def _nt_load_fields(self, stage: Stage) -> Set[str]:
+        """Fields of a column stage whose loads from memory are nontemporal: what a column kernel reads exactly once (level
+        after level, planes apart: nothing worth keeping in the L1).  These are the fields the stage reads at no horizontal
+        offset and that only ONE of its sweeps reads from memory; fields BOTH sweeps read and nobody writes go to
+        ``nt_loads_last``: cacheable in the first sweep, nontemporal in the last (their last use).
+
+        Same process, same fields, 1024 x 1024 x 160 fp64 (profiles/r5_nt_loads_column_kernels.txt), share of the HBM peak
+        with plain loads / every load nontemporal / only fields read at no horizontal offset / ... that only one sweep reads
+        (mode 3) / ... and that the stage does not write: vertical advection 0.588 / 0.557 / 0.584 / **0.631** / 0.586 --
+        `u_pos`, which both sweeps read, must stay cacheable in the first --; generated tridiagonal solve 0.686 / 0.730 /
+        0.730 / **0.730** / 0.698; hand-written solve (tridiag_stack.hip.h NTL) +5-9 %.  Adding the last use of what both
+        sweeps read (what ships) to mode 3, on another box: vertical advection 0.6456 -> 0.6476 (0.605 plain), the solve
+        unchanged."""
         names, shifted, orders = set(), set(), {}
         cached = set(self.tc[0].names) if self.tc is not None else set()
         for nest in stage.nests:
@@ -1098,42 +989,22 @@ class _Emitter:
                             if not (e.name in cached and nest.order is ir.LoopOrder.BACKWARD):  # (served on chip in the second sweep)
                                 orders.setdefault(e.name, set()).add(nest.order)
         ok = {n for n in names if n in self.decl_dtype and self.decl_dtype[n].kind in "fiu" and self.decl_dtype[n].itemsize >= 4}
-        if mode == 1:
-            return ok
         ok -= shifted
-        if mode == 2:
-            return ok
-        both = {n for n in ok if len(orders.get(n, ())) > 1 and n not in stage.written}
-        ok = {n for n in ok if len(orders.get(n, ())) <= 1}  # 3: ... and read from memory by ONE sweep only
-        if mode == 3:
-            return ok
-        if mode == 5:  # 3 + what BOTH sweeps read (and nobody writes): cacheable in the first sweep, nontemporal in the last
-            last = [n.order for n in stage.nests][-1]
-            self.nt_loads_last = {n: last for n in both}
-            return ok
-        return ok - set(stage.written)  # 4: ... and never written by the stage
+        last = stage.nests[-1].order
+        self.nt_loads_last = {n: last for n in ok if len(orders.get(n, ())) > 1 and n not in stage.written}
+        return {n for n in ok if len(orders.get(n, ())) <= 1}
 
     def kernel(self, si: int, stage: Stage, kname: str) -> KernelSource:
         L = self.lines
-        if stage.mapping == "ijk":
-            bi, bj, k_per_thread, j_per_thread = (tuple(TUNING["block_ijk"]) + (1,))[:4]
-        else:
-            (bi, bj), k_per_thread, j_per_thread = TUNING["block_column"], 1, 1
+        bi, bj = TUNING["block_ijk"] if stage.mapping == "ijk" else TUNING["block_column"]
         block = (bi, bj, 1)
-        self._kernel_header(stage, kname, block, j_per_thread)
+        self._kernel_header(stage, kname, block)
         if stage.mapping == "ijk":
-            if k_per_thread > 1:
-                L.append(f"    #pragma unroll")
-                L.append(f"    for (int kk = 0; kk < {k_per_thread}; ++kk) {{")
-                L.append(f"    const gt_i64 k = a.k_lo + (gt_i64)gt_bz * {k_per_thread} + kk;")
-            else:
-                L.append("    const gt_i64 k = a.k_lo + gt_bz;")
+            L.append("    const gt_i64 k = a.k_lo + gt_bz;")
             for nest in stage.nests:
                 L.append(f"    if (k >= {self.bound(nest.interval.start)} && k < {self.bound(nest.interval.end)} && k < a.k_hi) {{")
                 self.local_decls(nest, "        ")
                 self.statements(nest.stmts, stage, si, "k", {}, "        ")
-                L.append("    }")
-            if k_per_thread > 1:
                 L.append("    }")
         else:
             self.nt_loads = self._nt_load_fields(stage)
@@ -1141,8 +1012,6 @@ class _Emitter:
                 self._column_body(si, stage)
             finally:
                 self.nt_loads, self.nt_loads_last, self.nt_nest_order = None, {}, None
-        if j_per_thread > 1:
-            L.append("    }")
         L.append("}")
         L.append("")
         top_cache = None
@@ -1155,7 +1024,7 @@ class _Emitter:
             if n_reg_cfg >= 0:
                 depths = [int(n_reg_cfg)]
             else:
-                budget, step = (tuple(TUNING["top_cache_auto"]) + (448, 24)[len(TUNING["top_cache_auto"]):])[:2]
+                budget, step = TUNING["top_cache_auto"]
                 n_max = min(int(budget) // sum(self.decl_dtype[n].itemsize // 4 for n in cache.names), 128)
                 n_max -= n_max % 8
                 # the deepest one is the likeliest to spill (the host then takes the next): a close second, then coarse steps
@@ -1169,7 +1038,7 @@ class _Emitter:
                 # statically empty must hold at least one level there -> the smallest domain the variant may run on
                 variants.append((int(n_reg), int(n_lds), int(n_reg) + int(n_lds) + cache.start_margin + 1))
                 L.append("#if GT4MI_NO_ALIAS")  # the cached copies stand in for memory: only with disjoint arguments
-                self._kernel_header(stage, f"{kname}_tc{n_reg}", block, 1)
+                self._kernel_header(stage, f"{kname}_tc{n_reg}", block)
                 self.tc = (cache, int(n_reg), int(n_lds), threads)
                 self.nt_loads = self._nt_load_fields(stage)
                 try:
@@ -1181,24 +1050,28 @@ class _Emitter:
                 L.append("#endif")
                 L.append("")
             top_cache = tuple(variants) or None
-        vec = _vector_width(self, stage) if j_per_thread == 1 and block[0] % 64 == 0 else 0
+        vec = _vector_width(self, stage) if block[0] % 64 == 0 else 0
         vec_fields: Tuple[str, ...] = ()
-        vec_rows, xcd_rows, vec_block = _strip_shape(self, stage, block) if vec else (max(1, TUNING["vector_rows"]), TUNING["xcd_rows"], block)
+        vec_rows, vec_block = 1, block
         if vec:
-            vec_fields = _emit_vector_kernel(self, si, stage, kname, vec, vec_rows, vec_block, k_per_thread, xcd_rows)
+            vec_rows, xcd_rows, vec_block = _strip_shape(self, stage, block)
+            vec_fields = _emit_vector_kernel(self, si, stage, kname, vec, vec_rows, vec_block, xcd_rows)
         shared_halo, shared_vec, shared_fields, shared_rows, shared_preferred = 0, 0, (), 0, False
-        svec = vec or (_vector_width(self, stage, any_reach=True) if j_per_thread == 1 and block[0] % 64 == 0 else 0)
+        svec = vec or (_vector_width(self, stage, any_reach=True) if block[0] % 64 == 0 else 0)
         if svec:
-            form = _shared_form(self, stage, svec, k_per_thread)
+            form = _shared_form(self, stage, svec)
             if form is not None:
                 shared_vec = svec
-                shared_rows = int(TUNING["shared_rows"]) or (8 if svec >= 4 else 4)
+                # J rows per lane by element size.  Horizontal diffusion with XCD runs of 4, fp64 / fp32 GLUPS at 4 / 5 / 6 /
+                # 7 / 8 rows: 226 / 221 / 218 / 212 / 219 and 386 / 390 / 403 / 410 / 424; XCD runs of 2 / 4 / 8 tile rows
+                # differ by < 1 %, no grouping costs 2 % (profiles/r2_codegen_shared_rows_xcd.log, r2_codegen_shared_xcd.log)
+                shared_rows = 8 if svec >= 4 else 4
                 shared_halo, shared_fields = _emit_shared_kernel(self, si, stage, kname, svec, shared_rows, block, form)
                 shared_preferred = not vec or any(np.dtype(defs[v].dtype).itemsize == 8 for _, _, defs, need in form[0] for v in need)
         plane = None if stage.plane is None else (stage.plane[0], stage.plane[1].value, stage.plane[2])
-        return KernelSource(kname, stage.mapping, stage.extent, block, k_per_thread, j_per_thread, vec, vec_fields,
-                            vec_rows if vec else 1, plane, top_cache, shared_halo, shared_rows if shared_halo else 0,
-                            shared_vec, shared_fields, shared_preferred, vec_block if vec and vec_block != block else None)
+        return KernelSource(kname, stage.mapping, stage.extent, block, vec, vec_fields, vec_rows, plane, top_cache,
+                            shared_halo, shared_rows if shared_halo else 0, shared_vec, shared_fields, shared_preferred,
+                            vec_block if vec_block != block else None)
 
 
 def _vector_width(em: "_Emitter", stage: Stage, any_reach: bool = False) -> int:
@@ -1209,7 +1082,7 @@ def _vector_width(em: "_Emitter", stage: Stage, any_reach: bool = False) -> int:
     Needs: thread-per-point mapping, the stage starting at the domain's first column, reads only of arrays
     the stage does not write (so rows can be loaded once, up front), every statement on the full stage
     extent and outside horizontal regions, I offsets within one lane's reach, 4- or 8-byte elements."""
-    if stage.mapping != "ijk" or stage.extent[0][0] != 0 or not TUNING["vector"]:
+    if stage.mapping != "ijk" or stage.extent[0][0] != 0:
         return 0
     sizes = set()
     for nest in stage.nests:
@@ -1253,13 +1126,7 @@ def _strip_shape(em: "_Emitter", stage: Stage, block=(64, 4, 1)) -> Tuple[int, i
     is for LIGHT stages only: one statement reading one 8-byte array within one row / column of the point.  Round 3: those
     stages also get the hand-written kernel's workgroup, 256 lanes along I x 1 (a tile of 512 columns x 8 rows instead of
     128 x 32: the wave edges' neighbour columns are then mostly inside the workgroup) -- 364 -> 368 GLUPS on the 512^3
-    Laplacian (profiles/r3_codegen_strip_blocks.log).  Explicit settings of GT4MI_CODEGEN_VECTOR_ROWS / _XCD_ROWS /
-    _BLOCK_IJK win."""
-    import os
-
-    rows, xcd = max(1, TUNING["vector_rows"]), TUNING["xcd_rows"]
-    if "GT4MI_CODEGEN_VECTOR_ROWS" in os.environ or "GT4MI_CODEGEN_XCD_ROWS" in os.environ:
-        return rows, xcd, tuple(block)
+    Laplacian (profiles/r3_codegen_strip_blocks.log)."""
     stmts = [s for nest in stage.nests for s in nest.stmts]
     reads = [e for s in stmts for e in _stmt_field_reads(s) if e.name not in em.plan.locals]
     arrays = {e.name for e in reads}
@@ -1267,17 +1134,17 @@ def _strip_shape(em: "_Emitter", stage: Stage, block=(64, 4, 1)) -> Tuple[int, i
              and all(max(abs(e.offset[0]), abs(e.offset[1])) <= 1 and e.offset[2] == 0 for e in reads)
              and all(em.decl_dtype[n].itemsize == 8 for n in arrays | {stmts[0].target.name}))
     if not light:
-        return rows, xcd, tuple(block)
-    return 8, 4, (tuple(block) if "GT4MI_CODEGEN_BLOCK_IJK" in os.environ else (256, 1, 1))
+        return max(1, TUNING["vector_rows"]), 0, tuple(block)
+    return 8, 4, (256, 1, 1)
 
 
-def _shared_form(em: "_Emitter", stage: Stage, vec: int, k_per_thread: int):
+def _shared_form(em: "_Emitter", stage: Stage, vec: int):
     """([(nest, order, defs, rows needed per version), ...], halo lanes) when the stage may get a `_vecs` kernel -- a
     strip kernel whose inlined temporaries are computed ONCE per point and handed to the neighbouring lanes --, else
     None.  Eligible: PARALLEL interval blocks the stage holds completely, at least one of them with inlined temporaries;
     plain (unmasked, unshifted) assignments to arrays nobody in the stage reads; every operand a full I, J, K array read
     at a compile-time offset of at most `vec` points in I."""
-    if not TUNING["shared_temporaries"] or vec <= 0 or k_per_thread != 1 or not stage.nests:
+    if vec <= 0 or not stage.nests:
         return None
     if stage.extent != analysis.ZERO_EXTENT:
         return None
@@ -1439,12 +1306,10 @@ def _emit_shared_kernel(em: "_Emitter", si: int, stage: Stage, kname: str, vec: 
 
 
 def _read_once_fields(em: "_Emitter", stage: Stage) -> Set[str]:
-    """Strip kernels (TUNING["strip_nt_loads"]): the arrays a horizontal stage reads at its own point only -- every element exactly
+    """Strip kernels: the arrays a horizontal stage reads at its own point only -- every element exactly
     once, by one lane (horizontal diffusion's `coeff`).  Their 16-byte loads are nontemporal: hand-written kernel, same box A-B-A x 3,
     fp32 0.707 -> 0.728 of the HBM peak, fp64 0.707 -> 0.713; the same hint on `in`, whose halo rows other strips re-read, costs 18 %
     (profiles/r5_nt_loads_column_kernels.txt)."""
-    if not int(TUNING["strip_nt_loads"]):
-        return set()
     offsets: Dict[str, Set[Tuple[int, int, int]]] = {}
     for nest in stage.nests:
         for st in nest.stmts:
@@ -1606,7 +1471,7 @@ def _emit_shared_nest(em: "_Emitter", si: int, stage: Stage, nest: Nest, order, 
 
 
 def _emit_vector_kernel(em: "_Emitter", si: int, stage: Stage, kname: str, vec: int, rows_per_lane: int, block,
-                        k_per_thread: int, xcd_rows: int = 0) -> Tuple[str, ...]:
+                        xcd_rows: int) -> Tuple[str, ...]:
     """``<kname>_vec``: a lane owns ``vec`` consecutive I points times ``rows_per_lane`` consecutive J rows.
     Returns the arrays it touches."""
     L = em.lines
@@ -1640,12 +1505,7 @@ def _emit_vector_kernel(em: "_Emitter", si: int, stage: Stage, kname: str, vec: 
         L.append(f"    {const}{ct}* const{qual} b_{c} = a.{c} + {off};")
     L.append(f"    const bool whole = i0 >= 0 && i0 + {vec} <= iend && j0 + {JT} <= jend;  // else: a partial vector / strip")
     L.append(f"    const bool edge_lo = lane == 0 || i0 < {vec}, edge_hi = lane == 63 || i0 + {2 * vec} > iend;")
-    if k_per_thread > 1:
-        L.append("    #pragma unroll")
-        L.append(f"    for (int kk = 0; kk < {k_per_thread}; ++kk) {{")
-        L.append(f"    const gt_i64 k = a.k_lo + (gt_i64)gt_bz * {k_per_thread} + kk;")
-    else:
-        L.append("    const gt_i64 k = a.k_lo + gt_bz;")
+    L.append("    const gt_i64 k = a.k_lo + gt_bz;")
     for nest in stage.nests:
         L.append(f"    if (k >= {em.bound(nest.interval.start)} && k < {em.bound(nest.interval.end)} && k < a.k_hi) {{")
         L.append("      if (whole) {")
@@ -1752,8 +1612,6 @@ def _emit_vector_kernel(em: "_Emitter", si: int, stage: Stage, kname: str, vec: 
         L.append("          }")
         L.append("        }")
         L.append("      }")
-        L.append("    }")
-    if k_per_thread > 1:
         L.append("    }")
     L.append("}")
     L.append("")

@@ -432,8 +432,7 @@ class HipGenericStencilObject(StencilObject):
             ni, nj = dI + ihi - ilo, dJ + jhi - jlo
             if ni <= 0 or nj <= 0 or levels <= 0:
                 return None
-            nk = -(-levels // kern.k_per_thread) if kern.mapping == "ijk" else 1
-            lanes = rows = 1
+            nk = levels if kern.mapping == "ijk" else 1
             if sfn is not None and no_alias and (kern.shared_preferred or vfn is None) and args.lead < kern.shared_vec and all(
                     (geometry[n][0] - args.lead * geometry[n][3]) % (kern.shared_vec * geometry[n][3]) == 0
                     and geometry[n][1] % kern.shared_vec == 0 and geometry[n][2] % kern.shared_vec == 0 for n in kern.shared_fields):
@@ -444,14 +443,13 @@ class HipGenericStencilObject(StencilObject):
             if vfn is not None and no_alias and args.lead < kern.vec and all(
                     (geometry[n][0] - args.lead * geometry[n][3]) % (kern.vec * geometry[n][3]) == 0 and geometry[n][1] % kern.vec == 0
                     and geometry[n][2] % kern.vec == 0 for n in kern.vec_fields):
-                fn, lanes, rows = vfn, kern.vec, kern.vec_rows  # every lane's vector is naturally aligned (after the lead)
+                # every lane's vector is naturally aligned (after the lead)
                 block = kern.vec_block or kern.block
-                need = -(-(ni + args.lead) // lanes)  # lanes along I
+                need = -(-(ni + args.lead) // kern.vec)  # lanes along I
                 if block[1] == 1 and block[0] == 256 and -(-need // 320) * 320 < -(-need // 256) * 256:
                     block = (320, 1, 1)  # five waves: fewer idle lanes than a second workgroup per row
-                return fn, _U3(-(-need // block[0]), -(-nj // (block[1] * rows)), nk), _U3(*block)
-            grid = _U3(-(-ni // (kern.block[0] * lanes)), -(-nj // (kern.block[1] * kern.j_per_thread * rows)), nk)
-            return fn, grid, _U3(*kern.block)
+                return vfn, _U3(-(-need // block[0]), -(-nj // (block[1] * kern.vec_rows)), nk), _U3(*block)
+            return fn, _U3(-(-ni // kern.block[0]), -(-nj // kern.block[1]), nk), _U3(*kern.block)
 
         triples = list(zip(program.kernels, variant.functions, variant.vec_functions, variant.tc_functions,
                            variant.shared_functions))

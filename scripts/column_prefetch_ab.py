@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Run on the GPU box: rolling-prefetch distance of the generated column kernels' register levels (GT4MI_CODEGEN_TOP_CACHE_LOOKAHEAD) with
-the nontemporal loads, ONE process, SAME fields.   python3 scripts/column_lookahead_ab.py"""
+"""Run on the GPU box: chunk depth of the generated column kernels' prefetch (hip_codegen.TUNING["prefetch"], which is also the
+distance of the register levels' rolling prefetch), ONE process, SAME fields.   python3 scripts/column_prefetch_ab.py"""
 import pathlib
 import sys
 
@@ -15,7 +15,7 @@ from gt4py_amd.cartesian import gtscript  # noqa: E402
 from gt4py_amd.cartesian.backend import hip_codegen  # noqa: E402
 from gt4py_amd.storage import placement  # noqa: E402
 
-CASES = (("lookahead", 0), ("lookahead", 2), ("lookahead", 6), ("lookahead", 8), ("prefetch", 4), ("prefetch", 16))
+CASES = (8, 4, 16)  # the default first
 
 
 def main() -> int:
@@ -32,19 +32,18 @@ def main() -> int:
 
     vf = {n: field() for n in ("utens_stage", "u_stage", "wcon", "u_pos", "utens")}
     frozen = {}
-    for what, value in CASES:
-        key = "top_cache_lookahead" if what == "lookahead" else "prefetch"
-        saved = hip_codegen.TUNING[key]
-        hip_codegen.TUNING[key] = value
+    for value in CASES:
+        saved = hip_codegen.TUNING["prefetch"]
+        hip_codegen.TUNING["prefetch"] = value
         try:
             st = gtscript.stencil(backend="hip:mi300", definition=bench._vertical_advection_dycore, externals={"BET_M": 0.5, "BET_P": 0.5}, device_sync=False,
-                                  rebuild=True, name=f"vadv_{what}_{value}")
+                                  rebuild=True, name=f"vadv_prefetch_{value}")
         finally:
-            hip_codegen.TUNING[key] = saved
-        frozen[(what, value)] = st.freeze(origin={k: (0, 0, 0) for k in vf}, domain=dom)
+            hip_codegen.TUNING["prefetch"] = saved
+        frozen[value] = st.freeze(origin={k: (0, 0, 0) for k in vf}, domain=dom)
     for rep in range(4):
         row = []
-        for key, fz in frozen.items():
+        for value, fz in frozen.items():
             for _ in range(3):
                 fz(**vf, dtr_stage=0.15)
             torch.cuda.synchronize()
@@ -55,7 +54,7 @@ def main() -> int:
             b.record()
             b.synchronize()
             ms = a.elapsed_time(b) / 20
-            row.append(f"{key[0]} {key[1]}: {ms:.4f} {48.0 * np.prod(dom) / (ms * 1e-3) / 8e12:.4f}")
+            row.append(f"prefetch {value}: {ms:.4f} {48.0 * np.prod(dom) / (ms * 1e-3) / 8e12:.4f}")
         print("   ".join(row), flush=True)
     return 0
 

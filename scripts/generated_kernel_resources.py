@@ -2,10 +2,9 @@
 """Registers / LDS / scratch of the kernels hip_codegen generates for a stencil of tests/stencil_zoo.py, from the
 compiler's metadata -- no GPU needed (hipcc cross-compiles the generated source to gfx950 assembly).
 
-    GT4MI_CODEGEN_TOP_CACHE=32,163840 python scripts/generated_kernel_resources.py vertical_advection_dycore [-k]
+    python scripts/generated_kernel_resources.py vertical_advection_dycore [--top-cache 32,163840] [-k]
 
--k keeps the source and the assembly next to each other under /tmp/gt4mi_gen_<name>.{hip,s}."""
-import os
+--top-cache patches hip_codegen.TUNING["top_cache"] (register levels, LDS bytes[, cap on the LDS levels]); -k keeps the source and the assembly next to each other under /tmp/gt4mi_gen_<name>.{hip,s}."""
 import pathlib
 import re
 import subprocess
@@ -17,11 +16,14 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 import stencil_zoo as zoo  # noqa: E402
 from gt4py_amd.cartesian import gtscript  # noqa: E402
+from gt4py_amd.cartesian.backend import hip_codegen  # noqa: E402
 
 
 def main():
     name = sys.argv[1]
     defn, externals, _, _ = zoo.ZOO[name]
+    if "--top-cache" in sys.argv:
+        hip_codegen.TUNING["top_cache"] = tuple(int(x) for x in sys.argv[sys.argv.index("--top-cache") + 1].split(","))
     # building the stencil class generates the source; nothing is compiled by hiprtc or launched before the first call
     obj = gtscript.stencil(backend="hip:mi300", definition=defn, externals=externals, use_kernel_library=False, rebuild=True)
     prog = type(obj)._gt_program_

@@ -355,27 +355,28 @@ def test_elements_disjoint_never_claims_more_than_brute_force():
 def test_column_kernels_load_read_once_streams_nontemporally():
     """Round 5 (profiles/r5_nt_loads_column_kernels.txt): in a column kernel the fields read at no horizontal offset that only ONE
     sweep reads from memory are loaded with `__builtin_nontemporal_load` (+7 % on the vertical advection); `wcon`, which the
-    neighbouring lane reads too, never is, and `u_pos`, which both sweeps read, only at its last use; mode 0 emits plain loads."""
+    neighbouring lane reads too, never is, and `u_pos`, which both sweeps read, only at its last use: plain loads in the first
+    sweep, nontemporal ones in the last."""
     import re
 
     import stencil_zoo as zoo
     from gt4py_amd.cartesian import gtscript
-    from gt4py_amd.cartesian.backend import hip_codegen
 
     defn, ext, _, opts = zoo.ZOO["vertical_advection_dycore"]
-    saved = hip_codegen.TUNING["column_nt_loads"]
-    try:
-        found = {}
-        for mode in (0, 3, 5):
-            hip_codegen.TUNING["column_nt_loads"] = mode
-            st = gtscript.stencil(backend="hip:mi300", definition=defn, externals=ext, rebuild=True, name=f"vadv_nt_mode_{mode}", **opts)
-            src = type(st)._gt_program_.source
-            found[mode] = set(re.findall(r"__builtin_nontemporal_load\(&\w*?b2?_(\w+?)\[", src))
-    finally:
-        hip_codegen.TUNING["column_nt_loads"] = saved
-    assert found[0] == set()
-    assert {"u_stage", "utens", "utens_stage"} <= found[3] and "wcon" not in found[3] and "u_pos" not in found[3]
-    assert found[5] == found[3] | {"u_pos"}
+    st = gtscript.stencil(backend="hip:mi300", definition=defn, externals=ext, rebuild=True, name="vadv_nt_loads", **opts)
+    program = type(st)._gt_program_
+    src = program.source
+    found = set(re.findall(r"__builtin_nontemporal_load\(&\w*?b2?_(\w+?)\[", src))
+    assert found == {"ccol", "dcol", "u_pos", "u_stage", "utens", "utens_stage"}
+    assert "wcon" not in found
+    # the kernel without the top-of-column cache: from its signature to the next kernel's
+    start = src.index(f"{program.kernels[0].name}(const gt_args a)")
+    kernel = src[start:src.index('extern "C" __global__', start)]
+    streamed = [m.start() for m in re.finditer(r"__builtin_nontemporal_load\(&b_u_pos\[", kernel)]
+    plain = [m.start() for m in re.finditer(r"(?<!__builtin_nontemporal_load\(&)b_u_pos\[", kernel)]
+    print(f"u_pos in {program.kernels[0].name}: {len(plain)} plain loads, {len(streamed)} nontemporal ones")
+    assert plain and streamed
+    assert max(plain) < min(streamed)
 
 
 def test_strip_kernels_load_arrays_read_at_their_own_point_only_nontemporally():
