@@ -17,11 +17,13 @@ from typing import Callable, Dict, Sequence
 import numpy as np
 import torch
 
+from device_layouts import SENTINEL
+
 _UINT = {np.dtype(np.float64): np.uint64, np.dtype(np.float32): np.uint32}
 _TINT = {8: torch.int64, 4: torch.int32}
 _NP = {torch.float64: np.float64, torch.float32: np.float32}
 # what the elements a kernel must not write hold: NaNs with a payload no arithmetic produces
-SENTINEL_BITS = {8: 0x7FF4_DEAD_BEEF_0001, 4: 0x7FA0_BEEF}
+SENTINEL_BITS = {isz: SENTINEL[isz] for isz in (8, 4)}
 
 
 def oracle_threads() -> int:

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import torch
 
+from device_layouts import geometry
 from gt4py_amd import _lib
 
 TORCH_DT = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32}
@@ -15,48 +16,21 @@ TORCH_DT = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float
 class DevArray:
     """A device copy of a numpy IJK array with a selectable layout.
 
+    The geometry is tests/device_layouts.py's:
     layout "ifirst"  : I contiguous, rows padded so that element [align_index[0], j, k] is aligned to
-                       ``align_bytes`` (what gt4py storages for gt:gpu / hip:mi300 look like)
+                       256 bytes (what gt4py storages for gt:gpu / hip:mi300 look like)
     layout "ifirst_unaligned": I contiguous, rows padded to an odd pitch and base offset by one item
     layout "kfirst"  : C order of (I, J, K) -- K contiguous (numpy backend default)
     layout "jfirst"  : J contiguous
     """
 
-    def __init__(self, host: np.ndarray, layout: str = "ifirst", align_index=(0, 0, 0), align_bytes=256):
+    def __init__(self, host: np.ndarray, layout: str = "ifirst", align_index=(0, 0, 0)):
         assert host.ndim == 3
         self.host_shape = host.shape
         self.dtype = host.dtype
-        isz = host.dtype.itemsize
-        ni, nj, nk = host.shape
-        tdt = TORCH_DT[host.dtype]
-        if layout == "ifirst":
-            items = align_bytes // isz
-            pitch = -(-ni // items) * items
-            lead = (items - align_index[0] % items) % items
-            # over-allocate; find an aligned base inside
-            flat = torch.empty(pitch * nj * nk + 2 * items, dtype=tdt, device="cuda")
-            base_off = (-(flat.data_ptr() // isz) % items + lead) % items
-            self.strides = (1, pitch, pitch * nj)
-            self._flat = flat
-            self.offset = base_off
-        elif layout == "ifirst_unaligned":
-            pitch = ni + 3 if (ni + 3) % 2 else ni + 4
-            flat = torch.empty(pitch * nj * nk + 8, dtype=tdt, device="cuda")
-            self.strides = (1, pitch, pitch * nj)
-            self._flat = flat
-            self.offset = 1 if (flat.data_ptr() // isz) % 2 == 0 else 2
-        elif layout == "kfirst":
-            flat = torch.empty(ni * nj * nk, dtype=tdt, device="cuda")
-            self.strides = (nj * nk, nk, 1)
-            self._flat = flat
-            self.offset = 0
-        elif layout == "jfirst":
-            flat = torch.empty(ni * nj * nk, dtype=tdt, device="cuda")
-            self.strides = (nj, 1, ni * nj)
-            self._flat = flat
-            self.offset = 0
-        else:
-            raise ValueError(layout)
+        numel, self.strides, offset = geometry(host.shape, layout, host.dtype.itemsize, align_index[0])
+        self._flat = torch.empty(numel, dtype=TORCH_DT[host.dtype], device="cuda")  # (over-allocated: the aligned base is inside)
+        self.offset = offset(self._flat.data_ptr())
         self._flat.fill_(float("nan"))
         self.view = torch.as_strided(self._flat, host.shape, self.strides, self.offset)
         self.view.copy_(torch.from_numpy(np.ascontiguousarray(host)))
@@ -72,6 +46,27 @@ class DevArray:
     def get(self) -> np.ndarray:
         torch.cuda.synchronize()
         return self.view.cpu().numpy()
+
+
+def device(box, layout, halo, align_i=None):
+    """A DevArray of the box inside `halo` ghost cells in I and J, NaN everywhere outside the box."""
+    host = np.full((box.shape[0] + 2 * halo, box.shape[1] + 2 * halo, box.shape[2]), np.nan, dtype=box.dtype)
+    host[halo: halo + box.shape[0], halo: halo + box.shape[1]] = box
+    return DevArray(host, layout, align_index=(halo if align_i is None else align_i, 0, 0))
+
+
+def wrap(dev):
+    from gt4py_amd.storage.device_array import DeviceArray
+
+    return DeviceArray(dev.view)
+
+
+def bits(t):
+    return t.view({4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def data(rng, domain, dtype):
+    return (rng.standard_normal(domain) * 10.0 ** rng.integers(-2, 3, domain)).astype(dtype)
 
 
 def stream_ptr() -> int:

@@ -13,10 +13,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import boundary_ref as R  # noqa: E402
+import device_layouts as L  # noqa: E402  (the layouts; test infrastructure)
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
-DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2)]  # test_gpu_kernels.py's
-LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
 WIDTHS = [(1, 1, 1, 1), (2, 2, 2, 2), (2, 3, 0, 2)]
 ITEMSIZES = [1, 4, 8]
 #: all four; one side; the high sides; J sides only (over I ghosts the caller filled: the corner rule's last branch); a channel's
@@ -28,53 +27,15 @@ MODE_PAIRS = R.mode_pairs(with_none=True)  # 6 x 6
 #   (3, 5, 2)  REFLECT in I does not take the high I width 3 of (2, 3, 0, 2): 36 - 6 there.
 # Each runs on 4 layouts x 3 item sizes x 5 side masks.
 ADMISSIBLE = {(1, 1, 1): 25 + 9 + 9, (3, 5, 2): 36 + 36 + 30}
-SENTINEL = {1: 0xA5, 4: 0x7FA0_BEEF, 8: 0x7FF4_DEAD_BEEF_0001}  # (4, 8: tests/fullsize_util.py's NaNs with a payload)
-NP_INT = {1: np.uint8, 4: np.int32, 8: np.int64}  # (what torch has)
-NP_UINT = {1: np.uint8, 4: np.uint32, 8: np.uint64}
 CONSTANT = {1: 0x3C, 4: 0x7FC1_2345, 8: 0x7FF8_0000_0BAD_F00D}  # NaNs with payload as integers
-
-
-class Layout:
-    """A device buffer of integers with one of tests/gpu_util.py's four layouts (``DevArray`` itself takes floats only), kept
-    as a FLAT tensor so that every byte of it can be compared."""
-
-    def __init__(self, shape, layout, itemsize, align_i):
-        import torch
-
-        tdt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}[itemsize]
-        ni, nj, nk = shape
-        if layout == "ifirst":
-            items = 256 // itemsize
-            pitch = -(-ni // items) * items
-            self.flat = torch.empty(pitch * nj * nk + 2 * items, dtype=tdt, device="cuda")
-            self.strides = (1, pitch, pitch * nj)
-            lead = (items - align_i % items) % items
-            self.offset = (-(self.flat.data_ptr() // itemsize) % items + lead) % items
-        elif layout == "ifirst_unaligned":
-            pitch = ni + 3 if (ni + 3) % 2 else ni + 4
-            self.flat = torch.empty(pitch * nj * nk + 8, dtype=tdt, device="cuda")
-            self.strides = (1, pitch, pitch * nj)
-            self.offset = 1 if (self.flat.data_ptr() // itemsize) % 2 == 0 else 2
-        elif layout == "kfirst":
-            self.flat = torch.empty(ni * nj * nk, dtype=tdt, device="cuda")
-            self.strides, self.offset = (nj * nk, nk, 1), 0
-        else:  # jfirst
-            self.flat = torch.empty(ni * nj * nk, dtype=tdt, device="cuda")
-            self.strides, self.offset = (nj, 1, ni * nj), 0
-        self.shape = shape
-        self.view = torch.as_strided(self.flat, shape, self.strides, self.offset)
-
-    def host_view(self, host_flat):
-        isz = host_flat.itemsize
-        return np.lib.stride_tricks.as_strided(host_flat[self.offset:], self.shape, tuple(s * isz for s in self.strides))
 
 
 def _initial(lay, itemsize, origin, domain, rng):
     """Host image of the flat buffer: the sentinel everywhere, random bits in the domain box."""
-    host = np.full(lay.flat.numel(), SENTINEL[itemsize], dtype=NP_UINT[itemsize]).view(NP_INT[itemsize])
+    host = L.sentinel_image(lay.flat.numel(), itemsize)
     box = tuple(slice(o, o + d) for o, d in zip(origin, domain))
-    info = np.iinfo(NP_INT[itemsize])
-    lay.host_view(host)[box] = rng.integers(info.min, info.max, size=domain, dtype=NP_INT[itemsize], endpoint=True)
+    info = np.iinfo(L.NP_INT[itemsize])
+    lay.host_view(host)[box] = rng.integers(info.min, info.max, size=domain, dtype=L.NP_INT[itemsize], endpoint=True)
     return host
 
 
@@ -84,16 +45,16 @@ def _grid_case(domain, layout):
     from gt4py_amd import boundary
     from gt4py_amd.storage.device_array import DeviceArray
 
-    rng = np.random.default_rng(sum(domain) * 4 + LAYOUTS.index(layout))
+    rng = np.random.default_rng(sum(domain) * 4 + L.LAYOUTS.index(layout))
     ran = refused = 0
     for widths, itemsize in itertools.product(WIDTHS, ITEMSIZES):
         origin = (widths[0] + 1, widths[2] + 1, 0)  # one ghost cell beyond the widths: it must stay as it is
         shape = (origin[0] + domain[0] + widths[1] + 1, origin[1] + domain[1] + widths[3] + 1, domain[2])
-        lay = Layout(shape, layout, itemsize, origin[0])
+        lay = L.Layout(shape, layout, itemsize, origin[0])
         initial = _initial(lay, itemsize, origin, domain, rng)
         pristine = torch.from_numpy(initial).cuda()
         arr = DeviceArray(lay.view)
-        value = np.array(CONSTANT[itemsize], dtype=NP_UINT[itemsize]).view(NP_INT[itemsize])[()]
+        value = np.array(CONSTANT[itemsize], dtype=L.NP_UINT[itemsize]).view(L.NP_INT[itemsize])[()]
         halo = ((widths[0], widths[1]), (widths[2], widths[3]))
         for modes, sides in itertools.product(MODE_PAIRS, SIDE_MASKS):
             kwargs = dict(halo=halo, mode=modes, origin=origin, domain=domain, value=value, sides=sides)
@@ -120,8 +81,8 @@ def _admissible_count(domain):
     return ADMISSIBLE.get(domain, len(WIDTHS) * len(MODE_PAIRS))
 
 
-@pytest.mark.parametrize("layout", LAYOUTS)
-@pytest.mark.parametrize("domain", DOMAINS)
+@pytest.mark.parametrize("layout", L.LAYOUTS)
+@pytest.mark.parametrize("domain", L.DOMAINS)
 def test_fill_grid(domain, layout):
     ran, refused = _grid_case(domain, layout)
     per = len(ITEMSIZES) * len(SIDE_MASKS)
@@ -131,7 +92,7 @@ def test_fill_grid(domain, layout):
 
 
 def test_grid_size():
-    assert sum(_admissible_count(d) for d in DOMAINS) * len(LAYOUTS) * len(ITEMSIZES) * len(SIDE_MASKS) == (43 + 102 + 5 * 108) * 4 * 3 * 5 == 41100
+    assert sum(_admissible_count(d) for d in L.DOMAINS) * len(L.LAYOUTS) * len(ITEMSIZES) * len(SIDE_MASKS) == (43 + 102 + 5 * 108) * 4 * 3 * 5 == 41100
 
 
 def test_special_values_survive_as_bit_patterns():
@@ -147,8 +108,8 @@ def test_special_values_survive_as_bit_patterns():
         u = np.dtype(dtype).itemsize
         utype = {4: np.uint32, 8: np.uint64}[u]
         host = np.resize(np.array(bits, dtype=utype), (12, 10, 3)).copy()  # every special value on every edge, cyclically
-        host[0:2] = host[-2:] = SENTINEL[u]
-        host[:, 0:2] = host[:, -2:] = SENTINEL[u]
+        host[0:2] = host[-2:] = L.SENTINEL[u]
+        host[:, 0:2] = host[:, -2:] = L.SENTINEL[u]
         for modes in (("periodic", "symmetric"), ("reflect", "zero_gradient"), ("constant", "periodic")):
             d = gt_storage.empty(host.shape, dtype, backend="hip:mi300", aligned_index=(2, 2, 0))
             d.tensor.view({4: torch.int32, 8: torch.int64}[u]).copy_(torch.from_numpy(host.view({4: np.int32, 8: np.int64}[u])))
@@ -203,7 +164,7 @@ def test_nine_fields_of_mixed_lanes_are_two_launches():
     shape = (origin[0] + domain[0] + widths[1] + 1, origin[1] + domain[1] + widths[3] + 1, domain[2])
     layouts = ["ifirst", "ifirst", "ifirst_unaligned", "ifirst", "kfirst", "ifirst", "ifirst", "ifirst", "ifirst_unaligned"]
     rng = np.random.default_rng(17)
-    lays = [Layout(shape, name, 4, origin[0]) for name in layouts]
+    lays = [L.Layout(shape, name, 4, origin[0]) for name in layouts]
     initial = [_initial(lay, 4, origin, domain, rng) for lay in lays]
     for lay, host in zip(lays, initial):
         lay.flat.copy_(torch.from_numpy(host).cuda())

@@ -13,44 +13,19 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import gpu_util as G  # noqa: E402
 import stats_ref as R  # noqa: E402
+from device_layouts import DOMAINS, LAYOUTS  # noqa: E402
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
-DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2)]  # test_gpu_kernels.py's
-DOMAINS += [(128, 128, 64), (700, 5, 3)]  # (700 columns: more than the 256 a wave covers at once; all of them: one row per wave)
-LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
+DOMAINS = DOMAINS + [(128, 128, 64), (700, 5, 3)]  # (700 columns: more than the 256 a wave covers at once; all of them: one row per wave)
 U = 2.0 ** -53
-
-
-def _device(box, layout, halo, align_i=None):
-    """tests/gpu_util.py's DevArray of the box inside `halo` ghost cells in I and J, NaN everywhere outside the box."""
-    import gpu_util as G
-
-    host = np.full((box.shape[0] + 2 * halo, box.shape[1] + 2 * halo, box.shape[2]), np.nan, dtype=box.dtype)
-    host[halo: halo + box.shape[0], halo: halo + box.shape[1]] = box
-    return G.DevArray(host, layout, align_index=(halo if align_i is None else align_i, 0, 0))
-
-
-def _wrap(dev):
-    from gt4py_amd.storage.device_array import DeviceArray
-
-    return DeviceArray(dev.view)
-
-
-def _bits(t):
-    import torch
-
-    return t.view({4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
 def _rows(frozen):
     frozen()
     frozen.get()
     return frozen.result.get()
-
-
-def _data(rng, domain, dtype):
-    return (rng.standard_normal(domain) * 10.0 ** rng.integers(-2, 3, domain)).astype(dtype)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -64,13 +39,13 @@ def test_every_slot_bit_for_bit_against_the_restatement(dtype, halo):
 
     rng = np.random.default_rng(40 + halo)
     for domain in DOMAINS:
-        a, b = _data(rng, domain, dtype), _data(rng, domain, dtype)
+        a, b = G.data(rng, domain, dtype), G.data(rng, domain, dtype)
         w = rng.uniform(0.5, 2.0, domain[:2] + (1,)).astype(dtype)
         want = [R.stats(a), R.stats(a, b), R.stats(a, w)]
         for layout in LAYOUTS:
-            da, db, dw = (_device(x, layout, halo) for x in (a, b, w))
-            before = [_bits(d._flat).clone() for d in (da, db, dw)]
-            arrays = [_wrap(da), _wrap(db), _wrap(dw)]
+            da, db, dw = (G.device(x, layout, halo) for x in (a, b, w))
+            before = [G.bits(d._flat).clone() for d in (da, db, dw)]
+            arrays = [G.wrap(da), G.wrap(db), G.wrap(dw)]
             weight = arrays[2][:, :, 0] if domain[2] > 1 else arrays[2]  # Field[IJ] against Field[IJK]
             frozen = diagnostics.FieldStats([arrays[0]] * 3, others=[None, arrays[1], weight], halo=halo)
             assert frozen.domain == domain and frozen.launches == 2
@@ -78,7 +53,7 @@ def test_every_slot_bit_for_bit_against_the_restatement(dtype, halo):
             for n, what in enumerate(("field", "pair", "weight")):
                 assert R.same_bits(got[n], want[n]), f"{domain} {dtype.__name__} {layout} halo {halo} {what}: {got[n]} != {want[n]}"
             torch.cuda.synchronize()
-            assert all(torch.equal(_bits(d._flat), x) for d, x in zip((da, db, dw), before)), "a field buffer changed"
+            assert all(torch.equal(G.bits(d._flat), x) for d, x in zip((da, db, dw), before)), "a field buffer changed"
 
 
 # domain -> (rows, rows per wave, tiles, tiles per finish leaf, finish leaves): 2 and 3 rows per wave, 17 and 22 tiles per leaf, an odd
@@ -98,12 +73,12 @@ def test_every_slot_bit_for_bit_with_several_rows_per_wave(dtype, halo):
     for domain, geometry in SEVERAL_ROWS_PER_WAVE.items():
         rows, rw, tiles, _, per_leaf, leaves = R.geometry(domain)
         assert (rows, rw, tiles, per_leaf, leaves) == geometry and rw > 1, R.geometry(domain)
-        a, b = _data(rng, domain, dtype), _data(rng, domain, dtype)
+        a, b = G.data(rng, domain, dtype), G.data(rng, domain, dtype)
         w = rng.uniform(0.5, 2.0, domain[:2] + (1,)).astype(dtype)
         want = [R.stats(a), R.stats(a, b), R.stats(a, w)]
         assert len({x.tobytes() for x in want}) == 3
         for layout in ("ifirst", "kfirst"):
-            arrays = [_wrap(_device(x, layout, halo)) for x in (a, b, w)]
+            arrays = [G.wrap(G.device(x, layout, halo)) for x in (a, b, w)]
             weight = arrays[2][:, :, 0]  # Field[IJ] against Field[IJK]; (the frozen call holds its arrays weakly: keep it)
             frozen = diagnostics.FieldStats([arrays[0]] * 3, others=[None, arrays[1], weight], halo=halo)
             assert frozen.domain == domain and frozen.launches == 2
@@ -124,8 +99,8 @@ def test_identical_bits_whatever_the_geometry(dtype):
     rng = np.random.default_rng(7)
     halo = 2
     for domain in [(65, 63, 7), (300, 37, 2), (128, 128, 64), (700, 5, 3)]:
-        a, b = _data(rng, domain, dtype), _data(rng, domain, dtype)
-        fillers = [_wrap(_device(_data(rng, domain, dtype), "ifirst", halo)) for _ in range(8)]
+        a, b = G.data(rng, domain, dtype), G.data(rng, domain, dtype)
+        fillers = [G.wrap(G.device(G.data(rng, domain, dtype), "ifirst", halo)) for _ in range(8)]
         seen = {}
 
         def run(tag, fields, others, entry, **kwargs):
@@ -138,7 +113,7 @@ def test_identical_bits_whatever_the_geometry(dtype):
 
         for layout in LAYOUTS:
             for align in (halo, halo + 1):  # the origin column on a 256-byte boundary / one item past it (no 16-byte lanes)
-                da, db = _wrap(_device(a, layout, halo, align)), _wrap(_device(b, layout, halo, align))
+                da, db = G.wrap(G.device(a, layout, halo, align)), G.wrap(G.device(b, layout, halo, align))
                 run((layout, align, "alone"), [da], [db], 0, halo=halo)
                 if layout == "ifirst" or align == halo:
                     for position in (0, 4, 7):
@@ -220,13 +195,13 @@ def test_special_values(dtype):
     tiny = np.finfo(dtype).tiny
 
     def both(a, b=None):
-        fields = [_wrap(_device(x, "ifirst", 1)) for x in ((a,) if b is None else (a, b))]
+        fields = [G.wrap(G.device(x, "ifirst", 1)) for x in ((a,) if b is None else (a, b))]
         got = diagnostics.field_stats(fields[0], other=None if b is None else fields[1], halo=1)[0]
         want = R.stats(a, b)
         assert R.same_bits(tuple(got), want), (tuple(got), want)
         return got
 
-    a = _data(rng, domain, dtype)
+    a = G.data(rng, domain, dtype)
     a[-1, -1, -1] = np.nan  # the last point of the last tile
     s = both(a)
     assert s.nonfinite == 1 and s.count == a.size and all(math.isnan(v) for v in (s.sum, s.sum_abs, s.sum_sq, s.min, s.max))

@@ -18,10 +18,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from device_layouts import LAYOUTS  # noqa: E402
 from oracle import ref_numpy as R  # noqa: E402  (oracle = checker only)
 
 GOLD = np.load(pathlib.Path(__file__).parent / "golden" / "stencils_small.npz")
-LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
 
 
 def _same(a, b):

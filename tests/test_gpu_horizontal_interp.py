@@ -1,6 +1,6 @@
 """``gt4py_amd.horizontal`` on the GPU: bit for bit against the contract's restatement (tests/horizontal_interp_ref.py), NaN
 compared as NaN, over EVERY byte of each destination buffer -- row padding, ghost cells and the allocation's slack keep a
-NaN-payload sentinel, compared as integers --, in the four layouts of tests/transfer_ref.py, for float32 / float64 fields against
+NaN-payload sentinel, compared as integers --, in the four layouts of tests/device_layouts.py, for float32 / float64 fields against
 float32 / float64 positions, the four methods, absolute and relative positions, four reaches, IJ and IJK position fields, 1 to 9
 fields per call, at wave, workgroup and level-chunk boundaries, with positions on integers, halves, the ends of the readable box,
 beyond them, -0.0, +-inf, 1e300 and NaN, with an inf and a NaN planted in the fields, and handed over from and to a stencil in
@@ -13,8 +13,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import device_layouts as L  # noqa: E402  (the layouts; test infrastructure)
 import horizontal_interp_ref as H  # noqa: E402
-import transfer_ref as L  # noqa: E402  (the layouts; test infrastructure)
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
 CHUNK_K = 8  # INTERP_CHUNK_K of csrc/horizontal_interp.hip.h: the levels one thread walks
@@ -26,47 +26,6 @@ COUNTS = [1, 4, 8, 9]
 
 def _reach4(reach):
     return (reach,) * 4 if isinstance(reach, int) else (reach[0][0], reach[0][1], reach[1][0], reach[1][1])
-
-
-class Dev:
-    """An array on the device in one of the four layouts, as a FLAT buffer whose every byte is known: ``values`` in the view, a
-    NaN-payload sentinel everywhere else (``values=None``: everywhere).  One ghost row / column behind the high I / J end of what
-    the product is given (``given``): the array ends there for the product, the buffer does not."""
-
-    def __init__(self, shape, dtype, layout, values=None, align_i=0):
-        import torch
-
-        self.dtype = np.dtype(dtype)
-        isz = self.dtype.itemsize
-        self.lay = L.Layout(shape, layout, isz, align_i)
-        self.image = L.sentinel_image(self.lay.flat.numel(), isz)
-        if values is not None:
-            self.host(self.image)[...] = values
-        self.lay.upload(self.image)
-        self.given = self.lay.view.view({4: torch.float32, 8: torch.float64}[isz])[:-1, :-1]
-
-    def host(self, image):
-        """The view of a host image of the flat buffer, as floats."""
-        return self.lay.host_view(image.view(self.dtype))
-
-    def assert_unchanged(self, what):
-        assert np.array_equal(self.lay.download(), self.image), f"{what} changed"
-
-    def assert_box(self, box, want_box, what):
-        """The box holds ``want_box`` (NaN as NaN), every other byte of the buffer its sentinel.  Returns the box as it is."""
-        got = self.lay.download()
-        want = self.image.copy()
-        self.host(want)[box] = want_box
-        inside = np.zeros(want.shape, dtype=bool)
-        self.lay.host_view(inside)[box] = True
-        both_nan = np.isnan(got.view(self.dtype)) & np.isnan(want.view(self.dtype))
-        ok = (got == want) | (inside & both_nan)
-        if not ok.all():
-            bad = np.flatnonzero(~ok)
-            raise AssertionError(f"{what}: {bad.size} items of the whole buffer differ ({int((~ok & inside).sum())} of them in the box), "
-                                 f"first at flat index {bad[:6].tolist()} (view offset {self.lay.offset}, strides {self.lay.strides}); "
-                                 f"got {got.view(self.dtype)[bad[:6]].tolist()}, want {want.view(self.dtype)[bad[:6]].tolist()}")
-        return np.array(self.host(got)[box])
 
 
 # ---- inputs: float64 arrays that hold values of the dtype the device gets, so that the restatement sees what the device sees ------
@@ -137,10 +96,10 @@ def _run(domain, method, *, fdtype=np.float64, pdtype=np.float64, layout="ifirst
     for p in (pi, pj):
         full = np.full(pshape, 7.25, dtype=pdtype)
         full[box] = p if pos3d else p[:, :, None]
-        d_pos.append(Dev(pshape, pdtype, layout, full, align))
+        d_pos.append(L.Dev(pshape, pdtype, layout, full, align))
     given_pos = [d.given if pos3d else d.given[:, :, 0] for d in d_pos]
-    srcs = [Dev(shape, fdtype, layout, qs[n], align) for n in order]
-    dsts = [Dev(shape, fdtype, dst_layout or layout, None, align) for _ in order]
+    srcs = [L.Dev(shape, fdtype, layout, qs[n], align) for n in order]
+    dsts = [L.Dev(shape, fdtype, dst_layout or layout, None, align) for _ in order]
     hi = horizontal.HorizontalInterp([d.given for d in dsts], [s.given for s in srcs], pos_i=given_pos[0], pos_j=given_pos[1], method=method,
                                      relative=relative, halo=reach, origin=origin)
     assert (hi.domain, hi.launches, hi.method) == (domain, -(-len(order) // 8), method)
@@ -261,7 +220,7 @@ def test_a_field_of_ij_equals_an_ijk_field_with_the_same_items():
         for pdtype in (np.float32, np.float64):
             q = rng.uniform(-1, 1, shape).astype(np.float32)
             pi, pj = _positions(rng, (ni, nj, nk), (1, 1, 1, 1), False, True, pdtype)
-            src = Dev(shape, np.float32, "ifirst", q, 1)
+            src = L.Dev(shape, np.float32, "ifirst", q, 1)
             got = []
             for pos3d in (False, True):
                 pshape = shape if pos3d else shape[:2] + (1,)
@@ -269,9 +228,9 @@ def test_a_field_of_ij_equals_an_ijk_field_with_the_same_items():
                 for p in (pi, pj):
                     full = np.zeros(pshape, dtype=pdtype)
                     full[1:1 + ni, 1:1 + nj] = p[:, :, None]
-                    d_pos.append(Dev(pshape, pdtype, "ifirst", full, 1))
+                    d_pos.append(L.Dev(pshape, pdtype, "ifirst", full, 1))
                 given = [d.given if pos3d else d.given[:, :, 0] for d in d_pos]
-                dst = Dev(shape, np.float32, "ifirst", None, 1)
+                dst = L.Dev(shape, np.float32, "ifirst", None, 1)
                 horizontal.interpolate(dst.given, src.given, pos_i=given[0], pos_j=given[1], method=method, relative=True, halo=reach)
                 want = H.interp(q[:-1, :-1], pi, pj, method, True, (1, 1, 1, 1))
                 got.append(dst.assert_box((slice(1, 1 + ni), slice(1, 1 + nj)), want, f"{method} {'IJK' if pos3d else 'IJ'} positions"))
@@ -328,9 +287,9 @@ def test_the_c_entry_counts_what_it_enqueued():
 
     shape = (9, 4, 2)
     rng = np.random.default_rng(9)
-    srcs = [Dev(shape, np.float64, "ifirst", q) for q in _field_values(rng, shape, 9, np.float64)]
-    dsts = [Dev(shape, np.float64, "ifirst", None) for _ in srcs]
-    pos = Dev(shape, np.float64, "ifirst", rng.uniform(0, 3, shape))
+    srcs = [L.Dev(shape, np.float64, "ifirst", q) for q in _field_values(rng, shape, 9, np.float64)]
+    dsts = [L.Dev(shape, np.float64, "ifirst", None) for _ in srcs]
+    pos = L.Dev(shape, np.float64, "ifirst", rng.uniform(0, 3, shape))
     hi = horizontal.HorizontalInterp([d.given for d in dsts], [s.given for s in srcs], pos_i=pos.given, pos_j=pos.given)
     launches = ctypes.c_int(-1)
     rc = _lib.load().gt4mi_horizontal_interp(hi._dst, hi._src, 9, ctypes.byref(hi._pos_i), ctypes.byref(hi._pos_j), hi._extent, hi._reach, 8, 8,

@@ -1,6 +1,6 @@
 """``gt4py_amd.horizontal.remap_cells`` on the GPU: bit for bit against the contract's restatement (tests/horizontal_remap_ref.py),
 NaN compared as NaN, over EVERY byte of the destination buffer -- row padding, ghost cells outside the box and the allocation's
-slack keep a NaN-payload sentinel, compared as integers --, with the four layouts of tests/transfer_ref.py on the two sides
+slack keep a NaN-payload sentinel, compared as integers --, with the four layouts of tests/device_layouts.py on the two sides
 independently, for float32 / float64 fields and both methods, at wave and workgroup boundaries along the destination I and J, at
 level counts around the chunk of 8, for coarsening by 2, 3 and a non-integer ratio, refinement by 3, identical grids, one cell over
 everything and destination cells outside the source grid, for 1 to 9 fields per call, with an infinity and a NaN planted, and
@@ -17,52 +17,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import device_layouts as L  # noqa: E402  (the layouts; test infrastructure)
 import horizontal_remap_ref as R  # noqa: E402
-import transfer_ref as L  # noqa: E402  (the layouts; test infrastructure)
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
 METHODS = [R.PCM, R.PLM]
-
-
-class Dev:
-    """An array on the device in one of the four layouts, as a FLAT buffer whose every byte is known: ``values`` in the view, a
-    NaN-payload sentinel everywhere else (``values=None``: everywhere).  One ghost row / column behind the high I / J end of what
-    the product is given (``given``): the array ends there for the product, the buffer does not."""
-
-    def __init__(self, shape, dtype, layout, values=None, align_i=0):
-        import torch
-
-        self.dtype = np.dtype(dtype)
-        isz = self.dtype.itemsize
-        self.lay = L.Layout(shape, layout, isz, align_i)
-        self.image = L.sentinel_image(self.lay.flat.numel(), isz)
-        if values is not None:
-            self.host(self.image)[...] = values
-        self.lay.upload(self.image)
-        self.given = self.lay.view.view({4: torch.float32, 8: torch.float64}[isz])[:-1, :-1]
-
-    def host(self, image):
-        """The view of a host image of the flat buffer, as floats."""
-        return self.lay.host_view(image.view(self.dtype))
-
-    def assert_unchanged(self, what):
-        assert np.array_equal(self.lay.download(), self.image), f"{what} changed"
-
-    def assert_box(self, box, want_box, what):
-        """The box holds ``want_box`` (NaN as NaN), every other byte of the buffer its sentinel.  Returns the box as it is."""
-        got = self.lay.download()
-        want = self.image.copy()
-        self.host(want)[box] = want_box
-        inside = np.zeros(want.shape, dtype=bool)
-        self.lay.host_view(inside)[box] = True
-        both_nan = np.isnan(got.view(self.dtype)) & np.isnan(want.view(self.dtype))
-        ok = (got == want) | (inside & both_nan)
-        if not ok.all():
-            bad = np.flatnonzero(~ok)
-            raise AssertionError(f"{what}: {bad.size} items of the whole buffer differ ({int((~ok & inside).sum())} of them in the box), "
-                                 f"first at flat index {bad[:6].tolist()} (view offset {self.lay.offset}, strides {self.lay.strides}); "
-                                 f"got {got.view(self.dtype)[bad[:6]].tolist()}, want {want.view(self.dtype)[bad[:6]].tolist()}")
-        return np.array(self.host(got)[box])
 
 
 # ---- grids: (source edges, destination edges) of one axis for a destination extent nd ----------------------------------------
@@ -137,8 +96,8 @@ def _call(edges, qs, method, fdtype, dst_layout="ifirst", src_layout="ifirst", w
     for q in qs:
         full = np.random.default_rng(5).uniform(50, 60, s_shape).astype(fdtype)  # ghost cells: finite, far from the fields' values
         full[s_box] = q
-        srcs.append(Dev(s_shape, fdtype, src_layout, full, 1))
-    dsts = [Dev(d_shape, fdtype, dst_layout, None, 1) for _ in qs]
+        srcs.append(L.Dev(s_shape, fdtype, src_layout, full, 1))
+    dsts = [L.Dev(d_shape, fdtype, dst_layout, None, 1) for _ in qs]
     hr = horizontal.HorizontalRemap([d.given for d in dsts], [s.given for s in srcs], src_edges=(xs_i, xs_j), dst_edges=(xd_i, xd_j),
                                     method=method, src_origin=(1, 1, 0), dst_origin=(1, 1, 0))
     assert (hr.src_extent, hr.dst_extent, hr.nk, hr.launches) == (ns, nd, nk, -(-len(qs) // 8))

@@ -11,10 +11,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import edge_values as E  # noqa: E402
+from device_layouts import DOMAINS, LAYOUTS  # noqa: E402
 from oracle import ref_numpy as R  # noqa: E402  (oracle = checker only)
-
-DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2)]
-LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
 
 
 def _eq(got, want, what=""):

@@ -13,34 +13,14 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import gpu_util as G  # noqa: E402
 import level_stats_ref as R  # noqa: E402
+from device_layouts import DOMAINS, LAYOUTS  # noqa: E402
 from gt4py_amd.cartesian.gtscript import PARALLEL, Field, K, computation, interval  # noqa: E402, F401
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
-DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2), (128, 128, 64), (700, 5, 3)]
-LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
+DOMAINS = DOMAINS + [(128, 128, 64), (700, 5, 3)]
 SEVERAL_ROWS_PER_WAVE = [(5, 1030, 3), (3, 771, 2)]
-
-
-def _device(box, layout, halo, align_i=None):
-    """tests/gpu_util.py's DevArray of the box inside `halo` ghost cells in I and J, NaN everywhere outside the box."""
-    import gpu_util as G
-
-    host = np.full((box.shape[0] + 2 * halo, box.shape[1] + 2 * halo, box.shape[2]), np.nan, dtype=box.dtype)
-    host[halo: halo + box.shape[0], halo: halo + box.shape[1]] = box
-    return G.DevArray(host, layout, align_index=(halo if align_i is None else align_i, 0, 0))
-
-
-def _wrap(dev):
-    from gt4py_amd.storage.device_array import DeviceArray
-
-    return DeviceArray(dev.view)
-
-
-def _bits(t):
-    import torch
-
-    return t.view({4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
 def _rows(frozen):
@@ -55,17 +35,13 @@ def _rows(frozen):
     return rows
 
 
-def _data(rng, domain, dtype):
-    return (rng.standard_normal(domain) * 10.0 ** rng.integers(-2, 3, domain)).astype(dtype)
-
-
 @functools.lru_cache(maxsize=None)
 def _case(domain, dtype_name):
     """Data and the restatement's three profiles of a domain (a field, a pair, a pair with an IJ weight): computed once, shared,
     read-only."""
     dtype = np.dtype(dtype_name).type
     rng = np.random.default_rng([*domain, np.dtype(dtype_name).itemsize])
-    a, b = _data(rng, domain, dtype), _data(rng, domain, dtype)
+    a, b = G.data(rng, domain, dtype), G.data(rng, domain, dtype)
     w = rng.uniform(0.5, 2.0, domain[:2] + (1,)).astype(dtype)
     want = [R.profile(a), R.profile(a, b), R.profile(a, w)]
     for x in (a, b, w, *want):
@@ -78,8 +54,8 @@ def _three_entries(domain, dtype, layout, halo):
     from gt4py_amd import diagnostics
 
     a, b, w, _ = _case(domain, np.dtype(dtype).name)
-    devs = [_device(x, layout, halo) for x in (a, b, w)]
-    arrays = [_wrap(d) for d in devs]
+    devs = [G.device(x, layout, halo) for x in (a, b, w)]
+    arrays = [G.wrap(d) for d in devs]
     weight = arrays[2][:, :, 0] if domain[2] > 1 else arrays[2]  # Field[IJ] against Field[IJK]
     frozen = diagnostics.LevelStats([arrays[0]] * 3, others=[None, arrays[1], weight], halo=halo)
     return frozen, devs, (arrays, weight)
@@ -96,14 +72,14 @@ def test_every_row_bit_for_bit_against_the_restatement(dtype, halo):
         want = _case(domain, np.dtype(dtype).name)[3]
         for layout in LAYOUTS:
             frozen, devs, keep = _three_entries(domain, dtype, layout, halo)
-            before = [_bits(d._flat).clone() for d in devs]
+            before = [G.bits(d._flat).clone() for d in devs]
             assert frozen.domain == domain and frozen.launches == 2 and frozen.nk == domain[2]
             assert frozen._workspace_bytes == 3 * domain[2] * R.geometry(*domain[:2])[1] * 64
             got = _rows(frozen)
             for n, what in enumerate(("field", "pair", "weight")):
                 assert R.same_bits(got[n], want[n]), f"{domain} {dtype.__name__} {layout} halo {halo} {what}:\n{got[n]}\n!=\n{want[n]}"
             torch.cuda.synchronize()
-            assert all(torch.equal(_bits(d._flat), x) for d, x in zip(devs, before)), "a field buffer changed"
+            assert all(torch.equal(G.bits(d._flat), x) for d, x in zip(devs, before)), "a field buffer changed"
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -139,11 +115,11 @@ def test_the_bits_of_a_level_depend_on_its_plane_alone(dtype):
     rng = np.random.default_rng(7)
     halo = 2
     for plane in [(65, 63), (300, 37), (5, 1030)]:
-        a, b = _data(rng, plane + (1,), dtype), _data(rng, plane + (1,), dtype)
-        box_a, box_b = _data(rng, plane + (7,), dtype), _data(rng, plane + (7,), dtype)
+        a, b = G.data(rng, plane + (1,), dtype), G.data(rng, plane + (1,), dtype)
+        box_a, box_b = G.data(rng, plane + (7,), dtype), G.data(rng, plane + (7,), dtype)
         box_a[:, :, 3:4], box_b[:, :, 3:4] = a, b
-        fillers = [_wrap(_device(_data(rng, plane + (1,), dtype), "ifirst", halo)) for _ in range(8)]
-        deep_fillers = [_wrap(_device(_data(rng, plane + (7,), dtype), "ifirst", halo)) for _ in range(8)]
+        fillers = [G.wrap(G.device(G.data(rng, plane + (1,), dtype), "ifirst", halo)) for _ in range(8)]
+        deep_fillers = [G.wrap(G.device(G.data(rng, plane + (7,), dtype), "ifirst", halo)) for _ in range(8)]
         seen = {}
 
         def run(tag, fields, others, entry, level=0, **kwargs):
@@ -156,9 +132,9 @@ def test_the_bits_of_a_level_depend_on_its_plane_alone(dtype):
 
         for layout in LAYOUTS:
             for align in (halo, halo + 1):  # the origin column on a 256-byte boundary / one item past it (no 16-byte lanes)
-                da, db = _wrap(_device(a, layout, halo, align)), _wrap(_device(b, layout, halo, align))
+                da, db = G.wrap(G.device(a, layout, halo, align)), G.wrap(G.device(b, layout, halo, align))
                 run((layout, align, "nk = 1"), [da], [db], 0, halo=halo)
-                deep_a, deep_b = _wrap(_device(box_a, layout, halo, align)), _wrap(_device(box_b, layout, halo, align))
+                deep_a, deep_b = G.wrap(G.device(box_a, layout, halo, align)), G.wrap(G.device(box_b, layout, halo, align))
                 run((layout, align, "level 3 of 7"), [deep_a], [deep_b], 0, level=3, halo=halo)
                 flat_a, flat_b = da[:, :, 0], db[:, :, 0]
                 assert flat_a.ndim == 2
@@ -170,7 +146,7 @@ def test_the_bits_of_a_level_depend_on_its_plane_alone(dtype):
                         run((layout, align, position), fields, others, position, halo=halo)
                     run((layout, align, "ninth"), deep_fillers + [deep_a], [None] * 8 + [deep_b], 8, level=3, halo=halo)
         # levels 2 ... 4 of the deep box through origin[2] / domain[2]: profile index 1 is level 3
-        deep_a, deep_b = _wrap(_device(box_a, "ifirst", halo)), _wrap(_device(box_b, "ifirst", halo))
+        deep_a, deep_b = G.wrap(G.device(box_a, "ifirst", halo)), G.wrap(G.device(box_b, "ifirst", halo))
         run("origin[2] = 2", [deep_a], [deep_b], 0, level=1, origin=(halo, halo, 2), domain=plane + (3,))
         assert len(set(seen.values())) == 1, f"{plane} {dtype.__name__}: {len(set(seen.values()))} different results: {sorted(map(str, seen))}"
         assert len(seen) == 8 * 3 + 5 * 4 + 1
@@ -192,9 +168,9 @@ def test_against_field_stats_of_every_plane(dtype):
             if integers:
                 a, b = (rng.integers(-2 ** 19, 2 ** 19, domain, endpoint=True).astype(dtype) for _ in range(2))
             else:
-                a, b = _data(rng, domain, dtype), _data(rng, domain, dtype)
+                a, b = G.data(rng, domain, dtype), G.data(rng, domain, dtype)
                 a[3, 4, 1], b[5, 6, 2] = np.inf, np.nan  # (non-finite counts, NaN extremes of one level)
-            da, db = _wrap(_device(a, "ifirst", halo)), _wrap(_device(b, "ifirst", halo))
+            da, db = G.wrap(G.device(a, "ifirst", halo)), G.wrap(G.device(b, "ifirst", halo))
             single, pair = diagnostics.level_stats(da, da, other=[None, db], halo=halo)
             for k in range(nk):
                 planes = diagnostics.field_stats(da, da, other=[None, db], origin=(halo, halo, k), domain=(ni, nj, 1))
@@ -223,13 +199,13 @@ def test_special_values(dtype):
 
     rng = np.random.default_rng(9)
     domain = (130, 40, 5)
-    a = _data(rng, domain, dtype)
+    a = G.data(rng, domain, dtype)
     a[-1, -1, 3] = np.nan  # one NaN, the last point of level 3
     a[0, 0, 1], a[7, 9, 1] = np.inf, -np.inf  # level 1: both infinities
     a[:, :, 4] = 0.0
     a[::3, :, 4] = -0.0  # level 4: only zeros, of either sign
     a[:, :, 0] = (rng.integers(-7, 8, domain[:2]) * np.finfo(dtype).smallest_subnormal).astype(dtype)  # denormals are numbers
-    dev = _wrap(_device(a, "ifirst", 1))
+    dev = G.wrap(G.device(a, "ifirst", 1))
     p, = diagnostics.level_stats(dev, halo=1)
     want = R.profile(a)
     rows = np.array([getattr(p, name) for name in diagnostics.PROFILE_ROWS], dtype=np.float64)
@@ -246,12 +222,12 @@ def test_special_values(dtype):
     assert (p.min[4], p.max[4], p.sum_abs[4]) == (0, 0, 0) and np.signbit(p.min[4]) and not np.signbit(p.max[4])
     assert p.nonfinite[0] == 0 and p.sum_abs[0] > 0 and p.max[0] == float(a[:, :, 0].max()) and abs(p.max[0]) < np.finfo(dtype).tiny
     a[-1, -1, 3] = 1.0
-    q, = diagnostics.level_stats(_wrap(_device(a, "kfirst", 1)), halo=1)
+    q, = diagnostics.level_stats(G.wrap(G.device(a, "kfirst", 1)), halo=1)
     assert q.first_nonfinite == 1 and not np.isnan(q.min).any() and R.same_bits(q.sum, R.profile(a)[R.SUM])
     # all-(-0) and all-(+0) levels keep their sign in both extremes
     z = np.zeros((9, 5, 2), dtype)
     z[:, :, 1] = -0.0
-    s, = diagnostics.level_stats(_wrap(_device(z, "ifirst", 0)))
+    s, = diagnostics.level_stats(G.wrap(G.device(z, "ifirst", 0)))
     assert np.signbit(s.min).tolist() == [False, True] and np.signbit(s.max).tolist() == [False, True]
 
 
@@ -272,7 +248,7 @@ def test_profile_feeds_a_stencil_in_the_same_stream_without_synchronisation():
     backend, domain = "hip:mi300", (65, 63, 7)
     stencil = gtscript.stencil(backend=backend, definition=anomaly, device_sync=False)
     rng = np.random.default_rng(17)
-    host = _data(rng, domain, np.float64) + 3.0
+    host = G.data(rng, domain, np.float64) + 3.0
     u = gt_storage.from_array(host, backend=backend)
     out = gt_storage.zeros(domain, backend=backend)
     watch = diagnostics.LevelStats([u])

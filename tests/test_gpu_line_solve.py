@@ -13,8 +13,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import device_layouts as L  # noqa: E402  (the layouts; test infrastructure)
 import line_solve_ref as R  # noqa: E402
-import transfer_ref as L  # noqa: E402  (the layouts; test infrastructure)
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
 LANES, TILES, ITEMS = "lanes", "tiles", "items"
@@ -43,59 +43,6 @@ def expected_path(layouts, coef_strides, extent, axis):
     return LANES if any(unit(ax) and extent[ax] > 1 for ax in range(3) if ax != axis) else ITEMS
 
 
-class Dev:
-    """An array on the device in one of the layouts of tests/transfer_ref.py, as a FLAT buffer whose every byte is known:
-    ``values`` in the view, a NaN-payload sentinel everywhere else (``values=None``: everywhere).  The product is given the
-    view without its last row and column: the array ends there for the product, the buffer does not."""
-
-    def __init__(self, shape, dtype, layout, values=None):
-        import torch
-
-        self.dtype = np.dtype(dtype)
-        isz = self.dtype.itemsize
-        self.lay = L.Layout(shape, layout, isz, 1)
-        self.image = L.sentinel_image(self.lay.flat.numel(), isz)
-        if values is not None:
-            self.host(self.image)[...] = values
-        self.lay.upload(self.image)
-        self.given = self.lay.view.view({4: torch.float32, 8: torch.float64}[isz])[:-1, :-1]
-
-    def host(self, image):
-        return self.lay.host_view(image.view(self.dtype))
-
-    def assert_unchanged(self, what):
-        assert np.array_equal(self.lay.download(), self.image), f"{what} changed"
-
-    def assert_box(self, box, want_box, what):
-        """The box holds ``want_box`` (NaN as NaN), every other byte of the buffer what it held.  Returns the box as it is."""
-        got = self.lay.download()
-        want = self.image.copy()
-        self.host(want)[box] = want_box
-        inside = np.zeros(want.shape, dtype=bool)
-        self.lay.host_view(inside)[box] = True
-        both_nan = np.isnan(got.view(self.dtype)) & np.isnan(want.view(self.dtype))
-        ok = (got == want) | (inside & both_nan)
-        if not ok.all():
-            bad = np.flatnonzero(~ok)
-            raise AssertionError(f"{what}: {bad.size} items of the whole buffer differ ({int((~ok & inside).sum())} of them in the box), "
-                                 f"first at flat index {bad[:6].tolist()} (view offset {self.lay.offset}, strides {self.lay.strides}); "
-                                 f"got {got.view(self.dtype)[bad[:6]].tolist()}, want {want.view(self.dtype)[bad[:6]].tolist()}")
-        return np.array(self.host(got)[box])
-
-
-class Line:
-    """A 1-d coefficient on the device."""
-
-    def __init__(self, values):
-        import torch
-
-        self.values = np.ascontiguousarray(values)
-        self.given = torch.from_numpy(self.values).cuda()
-
-    def assert_unchanged(self, what):
-        assert np.array_equal(self.given.cpu().numpy().view(np.uint8), self.values.view(np.uint8)), f"{what} changed"
-
-
 def _coefficients(rng, shape, dtype):
     """Diagonally dominant: |b| >= 2 (|a| + |c|), both signs."""
     a, c = rng.uniform(-1, 1, shape), rng.uniform(-1, 1, shape)
@@ -117,21 +64,21 @@ def _run(extent, axis, periodic, *, dtype=np.float64, layout="ifirst", rhs_layou
     n = extent[axis]
     if line_coefs:
         coefs = _coefficients(rng, (n,), dtype)
-        d_coefs = [Line(v) for v in coefs]
+        d_coefs = [L.Line(v) for v in coefs]
         boxes = coefs
     else:
         coefs = _coefficients(rng, shape, dtype)
         if plant is not None:
             plant(coefs)
-        d_coefs = [Dev(shape, dtype, layout, v) for v in coefs]
+        d_coefs = [L.Dev(shape, dtype, layout, v, 1) for v in coefs]
         boxes = [v[box] for v in coefs]
     ds = [rng.uniform(-1, 1, shape).astype(dtype) * dtype(10.0 ** (f % 3)) for f in range(nfields)]
     rhs_layout = rhs_layout or layout
     if inplace:
-        outs = rhss = [Dev(shape, dtype, layout, d) for d in ds]
+        outs = rhss = [L.Dev(shape, dtype, layout, d, 1) for d in ds]
     else:
-        rhss = [Dev(shape, dtype, rhs_layout, d) for d in ds]
-        outs = [Dev(shape, dtype, layout, None) for _ in ds]
+        rhss = [L.Dev(shape, dtype, rhs_layout, d, 1) for d in ds]
+        outs = [L.Dev(shape, dtype, layout, None, 1) for _ in ds]
     ls = linesolve.LineSolve([o.given for o in outs], [r.given for r in rhss], lower=d_coefs[0].given, diag=d_coefs[1].given,
                              upper=d_coefs[2].given, axis=AXES[axis], periodic=periodic, halo=halo, origin=origin)
     lines = extent[(axis + 1) % 3] * extent[(axis + 2) % 3]

@@ -13,6 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import device_layouts as L  # noqa: E402  (the layouts; test infrastructure)
 import transfer_ref as R  # noqa: E402
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
@@ -26,9 +27,9 @@ def _case(src_layout, dst_layout, itemsize, halo, domain, rng):
     # one more ghost cell than the halo on every I / J side: outside the box, it must stay as it is
     origin = (halo + 1, halo + 1, 0)
     shape = (domain[0] + 2 * halo + 2, domain[1] + 2 * halo + 2, domain[2])
-    src, dst = R.Layout(shape, src_layout, itemsize, origin[0]), R.Layout(shape, dst_layout, itemsize, origin[0])
-    src_image = R.random_image(src.flat.numel(), itemsize, rng)
-    want = R.sentinel_image(dst.flat.numel(), itemsize)
+    src, dst = L.Layout(shape, src_layout, itemsize, origin[0]), L.Layout(shape, dst_layout, itemsize, origin[0])
+    src_image = L.random_image(src.flat.numel(), itemsize, rng)
+    want = L.sentinel_image(dst.flat.numel(), itemsize)
     src.upload(src_image)
     dst.upload(want)
     cp = transfer.FieldCopy(dst.view, src.view, halo=halo, origin=origin, domain=domain)
@@ -49,11 +50,11 @@ def _case(src_layout, dst_layout, itemsize, halo, domain, rng):
     return expected
 
 
-@pytest.mark.parametrize("domain", R.DOMAINS + R.K_LONG)
+@pytest.mark.parametrize("domain", L.DOMAINS + R.K_LONG)
 def test_copy_grid(domain):
     rng = np.random.default_rng(sum(domain))
     taken = {R.ROWS: 0, R.TILES: 0, R.ITEMS: 0}
-    for src_layout, dst_layout, itemsize, halo in itertools.product(R.LAYOUTS, R.LAYOUTS, R.ITEMSIZES, HALOS):
+    for src_layout, dst_layout, itemsize, halo in itertools.product(L.LAYOUTS, L.LAYOUTS, R.ITEMSIZES, HALOS):
         taken[_case(src_layout, dst_layout, itemsize, halo, domain, rng)] += 1
     assert sum(taken.values()) == 16 * 4 * 2
     # the tile path cannot go unexercised behind the item path: of the 16 pairs of layouts 10 differ in their fast axis
@@ -65,7 +66,7 @@ def test_copy_grid(domain):
 
 
 def test_grid_size():
-    assert len(R.DOMAINS + R.K_LONG) * len(R.LAYOUTS) ** 2 * len(R.ITEMSIZES) * len(HALOS) == 9 * 16 * 4 * 2 == 1152
+    assert len(L.DOMAINS + R.K_LONG) * len(L.LAYOUTS) ** 2 * len(R.ITEMSIZES) * len(HALOS) == 9 * 16 * 4 * 2 == 1152
 
 
 def test_nine_pairs_of_mixed_layouts_are_two_launches_and_equal_nine_single_calls():
@@ -83,11 +84,11 @@ def test_nine_pairs_of_mixed_layouts_are_two_launches_and_equal_nine_single_call
         # arrays of different shapes around the one box
         s_shape = (extent[0] + 2 + n % 3, extent[1] + 2 + n % 2, extent[2])
         d_shape = (extent[0] + 2 + (n + 1) % 3, extent[1] + 3, extent[2])
-        src, dst, alone = R.Layout(s_shape, sl, itemsize, origin[0]), R.Layout(d_shape, dl, itemsize, origin[0]), R.Layout(d_shape, dl, itemsize, origin[0])
-        image = R.random_image(src.flat.numel(), itemsize, rng)
+        src, dst, alone = L.Layout(s_shape, sl, itemsize, origin[0]), L.Layout(d_shape, dl, itemsize, origin[0]), L.Layout(d_shape, dl, itemsize, origin[0])
+        image = L.random_image(src.flat.numel(), itemsize, rng)
         src.upload(image)
         for d in (dst, alone):
-            d.upload(R.sentinel_image(d.flat.numel(), itemsize))
+            d.upload(L.sentinel_image(d.flat.numel(), itemsize))
         transfer.copy_fields(alone.view, src.view, halo=halo, origin=origin, domain=domain)
         srcs.append(src), dsts.append(dst), images.append(image), singles.append(alone)
     cp = transfer.FieldCopy([d.view for d in dsts], [s.view for s in srcs], halo=halo, origin=origin, domain=domain)
@@ -97,7 +98,7 @@ def test_nine_pairs_of_mixed_layouts_are_two_launches_and_equal_nine_single_call
     cp()
     for n, (src, dst, alone, image) in enumerate(zip(srcs, dsts, singles, images)):
         got = dst.download()
-        want = R.sentinel_image(dst.flat.numel(), itemsize)
+        want = L.sentinel_image(dst.flat.numel(), itemsize)
         R.copy_box(dst.host_view(want), src.host_view(image), (1, 1, 0), (1, 1, 0), extent)
         assert np.array_equal(got, want), f"pair {n} {pairs[n]}: {int((got != want).sum())} items of the whole buffer differ"
         # (the two buffers may sit differently in memory: compared through their views and their slack separately)
@@ -111,14 +112,14 @@ def test_a_broadcast_source_and_a_strided_side_take_the_item_path():
 
     rng = np.random.default_rng(4)
     plane = torch.from_numpy(rng.uniform(-1, 1, (1, 37, 9))).cuda()
-    dst = R.Layout((21, 37, 9), "ifirst", 8)
-    dst.upload(R.sentinel_image(dst.flat.numel(), 8))
+    dst = L.Layout((21, 37, 9), "ifirst", 8)
+    dst.upload(L.sentinel_image(dst.flat.numel(), 8))
     view = dst.view.view(torch.float64)
     everywhere = plane.expand(21, 37, 9)  # (held: the frozen copy keeps weak references to what the caller passes)
     cp = transfer.FieldCopy(view, everywhere)
     assert cp.paths == [R.ITEMS]
     cp()
-    want = R.sentinel_image(dst.flat.numel(), 8)
+    want = L.sentinel_image(dst.flat.numel(), 8)
     dst.host_view(want.view(np.float64))[...] = plane.cpu().numpy()
     assert np.array_equal(dst.download(), want)
     # every other column of a wider array, on both sides
@@ -145,11 +146,11 @@ def test_conversion_at_ieee_edge_values(layouts):
         assert np.isnan(host).mean() <= 0.01
         shape = host.shape
         isz, osz = host.dtype.itemsize, np.dtype(to).itemsize
-        src, dst = R.Layout(shape, layouts[0], isz), R.Layout(shape, layouts[1], osz)
-        image = R.random_image(src.flat.numel(), isz, np.random.default_rng(1))
+        src, dst = L.Layout(shape, layouts[0], isz), L.Layout(shape, layouts[1], osz)
+        image = L.random_image(src.flat.numel(), isz, np.random.default_rng(1))
         src.host_view(image.view(host.dtype))[...] = host
         src.upload(image)
-        dst.upload(R.sentinel_image(dst.flat.numel(), osz))
+        dst.upload(L.sentinel_image(dst.flat.numel(), osz))
         tf = {4: torch.float32, 8: torch.float64}
         d_view, s_view = dst.view.view(tf[osz]), src.view.view(tf[isz])
         with pytest.raises(TypeError, match="convert=True"):
@@ -161,7 +162,7 @@ def test_conversion_at_ieee_edge_values(layouts):
         with np.errstate(over="ignore", under="ignore"):
             expected = host.astype(to)
         got = dst.host_view(got_flat.view(to))
-        ut = R.NP_UINT[osz]
+        ut = L.NP_UINT[osz]
         nan = np.isnan(expected)
         assert nan.mean() <= 0.01
         differ = ~nan & (np.ascontiguousarray(got).view(ut) != expected.view(ut))
@@ -169,7 +170,7 @@ def test_conversion_at_ieee_edge_values(layouts):
                                   f"{[(float(host[tuple(i)]).hex(), float(got[tuple(i)]).hex(), float(expected[tuple(i)]).hex()) for i in np.argwhere(differ)[:4]]}")
         assert np.isnan(got[nan]).all() and np.array_equal(np.signbit(got[nan]), np.signbit(expected[nan]))
         # and nothing outside the view was written
-        want_flat = R.sentinel_image(dst.flat.numel(), osz)
+        want_flat = L.sentinel_image(dst.flat.numel(), osz)
         dst.host_view(want_flat)[...] = dst.host_view(got_flat)
         assert np.array_equal(got_flat, want_flat)
 
@@ -198,7 +199,7 @@ def test_download_of_a_storage(halo, dtype):
     for a, h in zip(arrays, hosts):
         want = np.ascontiguousarray(h[box]) if dtype is None else h[box].astype(dtype)
         assert a.dtype == want.dtype and a.shape == want.shape and a.flags["C_CONTIGUOUS"]
-        assert np.array_equal(a.view(R.NP_UINT[a.itemsize]), want.view(R.NP_UINT[a.itemsize]))
+        assert np.array_equal(a.view(L.NP_UINT[a.itemsize]), want.view(L.NP_UINT[a.itemsize]))
         pinned = out._host_stage[handle._slot]
         assert pinned.is_pinned() and np.shares_memory(a, pinned.numpy())
     assert handle.done()
@@ -268,7 +269,7 @@ def test_upload_writes_the_box_and_nothing_else():
         assert whole.shape == (37, 22, 9)
         inside = np.zeros(whole.shape, bool)
         inside[1:36, 1:21] = True
-        ut = R.NP_UINT[isz]
+        ut = L.NP_UINT[isz]
         assert np.array_equal(whole[1:36, 1:21].view(ut), kept.astype(dtype).view(ut))
         assert (whole.view(ut)[~inside] == ut(F.SENTINEL_BITS[isz])).all()
         # every other byte: ghost cells outside the box and the row padding keep the sentinel
@@ -313,9 +314,9 @@ def test_one_capture_of_a_frozen_copy_replays_the_same_bits():
 
     rng = np.random.default_rng(12)
     shape = (70, 35, 9)
-    src, dst = R.Layout(shape, "ifirst", 8, 1), R.Layout(shape, "kfirst", 8)
-    first, second = R.random_image(src.flat.numel(), 8, rng), R.random_image(src.flat.numel(), 8, rng)
-    sentinel = R.sentinel_image(dst.flat.numel(), 8)
+    src, dst = L.Layout(shape, "ifirst", 8, 1), L.Layout(shape, "kfirst", 8)
+    first, second = L.random_image(src.flat.numel(), 8, rng), L.random_image(src.flat.numel(), 8, rng)
+    sentinel = L.sentinel_image(dst.flat.numel(), 8)
     cp = transfer.FieldCopy(dst.view, src.view, halo=1)
     assert cp.paths == [R.TILES] and cp.extent == shape
     graph = torch.cuda.CUDAGraph()
@@ -339,7 +340,7 @@ def test_the_c_entry_counts_what_it_enqueued():
 
     from gt4py_amd import _lib, transfer
 
-    src, dst = R.Layout((33, 9, 4), "jfirst", 2), R.Layout((33, 9, 4), "ifirst", 2)
+    src, dst = L.Layout((33, 9, 4), "jfirst", 2), L.Layout((33, 9, 4), "ifirst", 2)
     cp = transfer.FieldCopy(dst.view, src.view)
     launches, paths = ctypes.c_int(-1), (ctypes.c_int * 1)(-1)
     rc = _lib.load().gt4mi_field_copy(cp._dst, cp._src, 1, cp._extent3, 2, 2, 0, torch.cuda.current_stream().cuda_stream, paths,

@@ -1,6 +1,6 @@
 """``gt4py_amd.vertical`` on the GPU: bit for bit against the contract's restatement (tests/vertical_remap_ref.py), NaN compared
 as NaN, over EVERY byte of the destination buffer -- row padding, ghost cells outside the box and the allocation's slack keep a
-NaN-payload sentinel, compared as integers --, in the four layouts of tests/transfer_ref.py, for float32 / float64 fields against
+NaN-payload sentinel, compared as integers --, in the four layouts of tests/device_layouts.py, for float32 / float64 fields against
 float32 / float64 edges, at wave and workgroup boundaries along I, for edge sets that make the lanes of a wave diverge, tie,
 leave the source range or degenerate, for 1 to 9 fields per call, and handed over to a stencil in stream order.
 
@@ -13,66 +13,12 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-import transfer_ref as L  # noqa: E402  (the layouts; test infrastructure)
+import device_layouts as L  # noqa: E402  (the layouts; test infrastructure)
 import vertical_remap_ref as V  # noqa: E402
 from oracle import ref_numpy as ORACLE  # noqa: E402  (oracle = checker only)
 
 METHODS = [V.PCM, V.PLM]
 LEVELS = [(1, 1), (1, 5), (5, 1), (2, 3), (17, 9), (9, 17)]
-
-
-class Dev:
-    """An array on the device in one of the four layouts, as a FLAT buffer whose every byte is known: ``values`` in the view, a
-    NaN-payload sentinel everywhere else (``values=None``: everywhere).  One ghost row / column behind the high I / J end of what
-    the product is given (``given``): the array ends there for the product, the buffer does not."""
-
-    def __init__(self, shape, dtype, layout, values=None, align_i=0):
-        import torch
-
-        self.dtype = np.dtype(dtype)
-        isz = self.dtype.itemsize
-        self.lay = L.Layout(shape, layout, isz, align_i)
-        self.image = L.sentinel_image(self.lay.flat.numel(), isz)
-        if values is not None:
-            self.host(self.image)[...] = values
-        self.lay.upload(self.image)
-        self.given = self.lay.view.view({4: torch.float32, 8: torch.float64}[isz])[:-1, :-1]
-
-    def host(self, image):
-        """The view of a host image of the flat buffer, as floats."""
-        return self.lay.host_view(image.view(self.dtype))
-
-    def assert_unchanged(self, what):
-        assert np.array_equal(self.lay.download(), self.image), f"{what} changed"
-
-    def assert_box(self, box, want_box, what):
-        """The box holds ``want_box`` (NaN as NaN), every other byte of the buffer its sentinel.  Returns the box as it is."""
-        got = self.lay.download()
-        want = self.image.copy()
-        self.host(want)[box] = want_box
-        inside = np.zeros(want.shape, dtype=bool)
-        self.lay.host_view(inside)[box] = True
-        both_nan = np.isnan(got.view(self.dtype)) & np.isnan(want.view(self.dtype))
-        ok = (got == want) | (inside & both_nan)
-        if not ok.all():
-            bad = np.flatnonzero(~ok)
-            raise AssertionError(f"{what}: {bad.size} items of the whole buffer differ ({int((~ok & inside).sum())} of them in the box), "
-                                 f"first at flat index {bad[:6].tolist()} (view offset {self.lay.offset}, strides {self.lay.strides}); "
-                                 f"got {got.view(self.dtype)[bad[:6]].tolist()}, want {want.view(self.dtype)[bad[:6]].tolist()}")
-        return np.array(self.host(got)[box])
-
-
-class Column:
-    """A ``Field[K]`` of edges on the device."""
-
-    def __init__(self, values, dtype):
-        import torch
-
-        self.values = np.ascontiguousarray(values, dtype=dtype)
-        self.given = torch.from_numpy(self.values).cuda()
-
-    def assert_unchanged(self, what):
-        assert np.array_equal(self.given.cpu().numpy().view(np.uint8), self.values.view(np.uint8)), f"{what} changed"
 
 
 # ---- edge sets: float64 arrays that hold values of the edge dtype, so that the restatement sees what the device sees ------------
@@ -164,10 +110,10 @@ def _run(ni, nj, ns, nd, method, *, fdtype=np.float64, edtype=np.float64, layout
     else:
         zs, zd = edges
     qs = _fields(rng_q, shape_ij, ns, nfields, fdtype)
-    d_zs = Column(zs[0, 0], edtype) if shared_src else Dev(shape_ij + (ns + 1,), edtype, layout, zs, origin[0])
-    d_zd = Column(zd[0, 0], edtype) if shared_dst else Dev(shape_ij + (nd + 1,), edtype, layout, zd, origin[0])
-    srcs = [Dev(shape_ij + (ns,), fdtype, layout, q, origin[0]) for q in qs]
-    dsts = [Dev(shape_ij + (nd,), fdtype, layout, None, origin[0]) for _ in qs]
+    d_zs = L.Line(zs[0, 0], edtype) if shared_src else L.Dev(shape_ij + (ns + 1,), edtype, layout, zs, origin[0])
+    d_zd = L.Line(zd[0, 0], edtype) if shared_dst else L.Dev(shape_ij + (nd + 1,), edtype, layout, zd, origin[0])
+    srcs = [L.Dev(shape_ij + (ns,), fdtype, layout, q, origin[0]) for q in qs]
+    dsts = [L.Dev(shape_ij + (nd,), fdtype, layout, None, origin[0]) for _ in qs]
     vr = vertical.VerticalRemap([d.given for d in dsts], [s.given for s in srcs], src_edges=d_zs.given, dst_edges=d_zd.given,
                                 method=method, halo=halo, origin=origin)
     assert (vr.ns, vr.nd, vr.extent, vr.launches) == (ns, nd, ext, -(-nfields // 8))
@@ -260,11 +206,11 @@ def test_an_entry_does_not_depend_on_its_position_or_on_the_number_of_entries():
         rng = np.random.default_rng(66)
         shape_ij = (ni + 2, nj + 2)
         zs, zd = edges
-        d_zs, d_zd = Dev(shape_ij + (ns + 1,), np.float64, "ifirst", zs, 1), Dev(shape_ij + (nd + 1,), np.float64, "ifirst", zd, 1)
+        d_zs, d_zd = L.Dev(shape_ij + (ns + 1,), np.float64, "ifirst", zs, 1), L.Dev(shape_ij + (nd + 1,), np.float64, "ifirst", zd, 1)
         fillers = _fields(rng, shape_ij, ns, 2, np.float32)
         for position, fields in ((0, [qs[8]]), (2, fillers + [qs[8]])):
-            srcs = [Dev(shape_ij + (ns,), np.float32, "ifirst", q, 1) for q in fields]
-            dsts = [Dev(shape_ij + (nd,), np.float32, "ifirst", None, 1) for _ in fields]
+            srcs = [L.Dev(shape_ij + (ns,), np.float32, "ifirst", q, 1) for q in fields]
+            dsts = [L.Dev(shape_ij + (nd,), np.float32, "ifirst", None, 1) for _ in fields]
             vertical.remap_levels([d.given for d in dsts], [s.given for s in srcs], src_edges=d_zs.given, dst_edges=d_zd.given, method=method,
                                   origin=(1, 1, 0))
             got = dsts[position].assert_box((slice(1, 1 + ni), slice(1, 1 + nj)), nine[8], f"{method}: field 8 at position {position}")
@@ -282,13 +228,13 @@ def test_identity_on_the_device_returns_the_source_bit_for_bit():
     box = (slice(1, 1 + ni), slice(1, 1 + nj))
     for fdtype, edtype in ((np.float64, np.float32), (np.float32, np.float64)):
         zs = _source_edges(rng, shape_ij, ns, edtype)
-        d_zs = Dev(shape_ij + (ns + 1,), edtype, "ifirst", zs, 1)
+        d_zs = L.Dev(shape_ij + (ns + 1,), edtype, "ifirst", zs, 1)
         for method in METHODS:
             qs = _fields(rng, shape_ij, ns, 3, fdtype)
             if method == V.PCM:
                 qs[0][rng.uniform(size=qs[0].shape) < 0.1] = -0.0
-            srcs = [Dev(shape_ij + (ns,), fdtype, "ifirst", q, 1) for q in qs]
-            dsts = [Dev(shape_ij + (ns,), fdtype, "jfirst", None) for _ in qs]
+            srcs = [L.Dev(shape_ij + (ns,), fdtype, "ifirst", q, 1) for q in qs]
+            dsts = [L.Dev(shape_ij + (ns,), fdtype, "jfirst", None) for _ in qs]
             vertical.remap_levels([d.given for d in dsts], [s.given for s in srcs], src_edges=d_zs.given, dst_edges=d_zs.given, method=method,
                                   origin=(1, 1, 0))
             for n, (d, q) in enumerate(zip(dsts, qs)):
@@ -337,9 +283,9 @@ def test_the_c_entry_counts_what_it_enqueued():
     shape_ij = (9, 4)
     rng = np.random.default_rng(9)
     zs = _source_edges(rng, shape_ij, 5, np.float64)
-    d_zs = Dev(shape_ij + (6,), np.float64, "ifirst", zs)
-    srcs = [Dev(shape_ij + (5,), np.float64, "ifirst", q) for q in _fields(rng, shape_ij, 5, 9, np.float64)]
-    dsts = [Dev(shape_ij + (5,), np.float64, "ifirst", None) for _ in srcs]
+    d_zs = L.Dev(shape_ij + (6,), np.float64, "ifirst", zs)
+    srcs = [L.Dev(shape_ij + (5,), np.float64, "ifirst", q) for q in _fields(rng, shape_ij, 5, 9, np.float64)]
+    dsts = [L.Dev(shape_ij + (5,), np.float64, "ifirst", None) for _ in srcs]
     vr = vertical.VerticalRemap([d.given for d in dsts], [s.given for s in srcs], src_edges=d_zs.given, dst_edges=d_zs.given)
     launches = ctypes.c_int(-1)
     rc = _lib.load().gt4mi_vertical_remap(vr._dst, vr._src, 9, ctypes.byref(vr._src_edges), ctypes.byref(vr._dst_edges), vr._extent2, 5, 5, 8, 8,

@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import device_layouts as L
 import transfer_ref as R
 from gt4py_amd import _lib, transfer
 
@@ -306,6 +307,34 @@ def test_a_frozen_copy_refuses_to_run_after_an_array_died(monkeypatch):
     gc.collect()
     with pytest.raises(RuntimeError, match="no longer exists"):
         cp()
+
+
+# ---- the layouts every GPU test of a utility entry puts its buffers in -------------------------------------------------------------
+def test_the_geometry_of_the_four_layouts():
+    """tests/device_layouts.py's ``geometry``: every item of the view inside the flat buffer and at an address of its own, the
+    column ``align_i`` of an "ifirst" row on a 256-byte address, an "ifirst_unaligned" view on an odd item address with an odd
+    pitch -- wherever the allocation starts."""
+    base = 0x7F00_0000_0000  # (a multiple of 256 bytes, as allocations are; the sweep below moves off it)
+    cases = 0
+    for layout in L.LAYOUTS:
+        for itemsize in (1, 2, 4, 8):
+            for align_i in (0, 1, 3):
+                for shape in ((1, 1, 1), (3, 5, 2), (65, 63, 7)):
+                    numel, strides, offset_of = L.geometry(shape, layout, itemsize, align_i)
+                    index = sum(np.arange(n).reshape([-1 if a == ax else 1 for a in range(3)]) * strides[ax] for ax, n in enumerate(shape))
+                    rows = index[0]  # (the first item of every row)
+                    for k in (0, 1, 2, 7, 31, 100, 255):  # ptr // itemsize of both parities, 7 residues modulo 256 bytes
+                        ptr = base + k * itemsize
+                        offset = offset_of(ptr)
+                        what = (layout, itemsize, align_i, shape, k)
+                        assert 0 <= offset and offset + int(index.max()) < numel, what
+                        assert np.unique(index).size == index.size, what
+                        if layout == "ifirst":
+                            assert ((ptr + (offset + align_i + rows) * itemsize) % 256 == 0).all(), what
+                        if layout == "ifirst_unaligned":
+                            assert (ptr // itemsize + offset) % 2 == 1 and strides[1] % 2 == 1, what
+                        cases += 1
+    assert cases == 4 * 4 * 3 * 3 * 7
 
 
 # ---- numpy's own two conversions on the values the GPU test plants ----------------------------------------------------------

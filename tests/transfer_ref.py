@@ -1,77 +1,17 @@
 """The field copy's contract restated with numpy slicing on host images of the FLAT buffers (``gt4mi_field_copy`` in
-include/gt4py_amd.h; gt4py_amd/transfer.py), the four layouts of tests/gpu_util.py for items of 1, 2, 4 and 8 bytes, and the rule
-that names the path a pair takes.  Test infrastructure; imports no product code and (at import) no torch."""
+include/gt4py_amd.h; gt4py_amd/transfer.py), the rule that names the path a pair takes, and the inputs of the conversions.  The
+buffers and their four layouts are tests/device_layouts.py's.  Test infrastructure; imports no product code and (at import) no
+torch."""
 
 from __future__ import annotations
 
 import numpy as np
 
-LAYOUTS = ["ifirst", "ifirst_unaligned", "kfirst", "jfirst"]
+from device_layouts import NP_UINT
+
 ITEMSIZES = [1, 2, 4, 8]
-DOMAINS = [(1, 1, 1), (3, 5, 2), (17, 33, 5), (64, 64, 8), (65, 63, 7), (130, 40, 3), (300, 37, 2)]  # test_gpu_kernels.py's
-K_LONG = [(66, 3, 65), (7, 2, 200)]  # these cross a tile edge along K; the shared list never does
-#: 2-byte: float16's NaN with a payload; 4, 8: tests/fullsize_util.py's NaNs with a payload
-SENTINEL = {1: 0xA5, 2: 0x7DAD, 4: 0x7FA0_BEEF, 8: 0x7FF4_DEAD_BEEF_0001}
-NP_INT = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}  # (what torch has)
-NP_UINT = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+K_LONG = [(66, 3, 65), (7, 2, 200)]  # these cross a tile edge along K; device_layouts.DOMAINS never does
 ROWS, TILES, ITEMS = 0, 1, 2
-
-
-def geometry(shape, layout: str, itemsize: int, align_i: int):
-    """(items of the flat buffer, strides in items, offset(address of the flat buffer) in items) of a layout."""
-    ni, nj, nk = shape
-    if layout == "ifirst":  # rows padded to 256 bytes, the column `align_i` on a 256-byte boundary
-        items = 256 // itemsize
-        pitch = -(-ni // items) * items
-        lead = (items - align_i % items) % items
-        return pitch * nj * nk + 2 * items, (1, pitch, pitch * nj), lambda ptr: (-(ptr // itemsize) % items + lead) % items
-    if layout == "ifirst_unaligned":  # an odd pitch, the first item on an odd item address
-        pitch = ni + 3 if (ni + 3) % 2 else ni + 4
-        return pitch * nj * nk + 8, (1, pitch, pitch * nj), lambda ptr: 1 if (ptr // itemsize) % 2 == 0 else 2
-    if layout == "kfirst":  # numpy's C order
-        return ni * nj * nk, (nj * nk, nk, 1), lambda ptr: 0
-    if layout == "jfirst":
-        return ni * nj * nk, (nj, 1, ni * nj), lambda ptr: 0
-    raise ValueError(layout)
-
-
-def host_view(host_flat: np.ndarray, shape, strides, offset: int) -> np.ndarray:
-    isz = host_flat.itemsize
-    return np.lib.stride_tricks.as_strided(host_flat[offset:], shape, tuple(s * isz for s in strides))
-
-
-class Layout:
-    """A device buffer of integers in one of the four layouts, kept as a FLAT tensor so that every byte of it can be compared."""
-
-    def __init__(self, shape, layout: str, itemsize: int, align_i: int = 0):
-        import torch
-
-        tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[itemsize]
-        numel, self.strides, offset = geometry(shape, layout, itemsize, align_i)
-        self.flat = torch.empty(numel, dtype=tdt, device="cuda")
-        self.offset = offset(self.flat.data_ptr())
-        self.shape, self.itemsize = tuple(shape), itemsize
-        self.view = torch.as_strided(self.flat, self.shape, self.strides, self.offset)
-
-    def host_view(self, host_flat):
-        return host_view(host_flat, self.shape, self.strides, self.offset)
-
-    def upload(self, host_flat):
-        import torch
-
-        self.flat.copy_(torch.from_numpy(host_flat))
-
-    def download(self):
-        return self.flat.cpu().numpy()
-
-
-def sentinel_image(numel: int, itemsize: int) -> np.ndarray:
-    return np.full(numel, SENTINEL[itemsize], dtype=NP_UINT[itemsize]).view(NP_INT[itemsize])
-
-
-def random_image(numel: int, itemsize: int, rng) -> np.ndarray:
-    info = np.iinfo(NP_INT[itemsize])
-    return rng.integers(info.min, info.max, size=numel, dtype=NP_INT[itemsize], endpoint=True)
 
 
 def box_slices(start, extent):
@@ -135,7 +75,7 @@ def conversion_inputs(shape=(65, 63, 7)):
         values = np.concatenate([np.asarray(p, dtype=dt) for p in planted])
         where = rng.choice(n, size=(values.size, 4), replace=False)  # every value at four points
         a[where] = values[:, None]
-        ut = {4: np.uint32, 8: np.uint64}[np.dtype(dt).itemsize]
+        ut = NP_UINT[np.dtype(dt).itemsize]
         quiet = {4: [0x7FC0_0000, 0xFFC0_0000, 0x7FC1_2345, 0xFFC5_4321],
                  8: [0x7FF8_0000_0000_0000, 0xFFF8_0000_0000_0000, 0x7FF8_0000_0BAD_F00D, 0xFFF8_0000_DEAD_BEEF]}[np.dtype(dt).itemsize]
         free = np.setdiff1d(np.arange(n), where.ravel())
