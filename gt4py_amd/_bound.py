@@ -1,5 +1,5 @@
 """What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
-``vertical.VerticalRemap``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``linesolve.LineSolve``) share on the Python side: turning a refusal of the library into an
+``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``linesolve.LineSolve``) share on the Python side: turning a refusal of the library into an
 exception, normalising halo / origin / domain / field lists, and binding a checked call to the caller's objects.  A new
 utility states what differs (its name in the messages, its extra fields) and takes the rest from here."""
 

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_level_stats",
     "gt4mi_field_copy",
     "gt4mi_vertical_remap",
+    "gt4mi_vertical_interp",
     "gt4mi_horizontal_interp",
     "gt4mi_overlap_table",
     "gt4mi_horizontal_remap",
@@ -113,6 +114,10 @@ COPY_PATH_ROWS, COPY_PATH_TILES, COPY_PATH_ITEMS = 0, 1, 2
 COPY_CONVERT, COPY_DRY_RUN = 1, 256
 # gt4mi_vertical_remap: methods, flags
 REMAP_PCM, REMAP_PLM, REMAP_DRY_RUN = 0, 1, 256
+# gt4mi_vertical_interp: methods, what a target outside the source range gets, flags
+VINTERP_NEAREST, VINTERP_LINEAR, VINTERP_CUBIC, VINTERP_CUBIC_MONOTONE = 0, 1, 2, 3
+VINTERP_OUTSIDE_CLAMP, VINTERP_OUTSIDE_LINEAR, VINTERP_OUTSIDE_FILL = 0, 1, 2
+VINTERP_DRY_RUN = 256
 # gt4mi_horizontal_interp: methods, flags
 INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC, INTERP_CUBIC_MONOTONE = 0, 1, 2, 3
 INTERP_RELATIVE, INTERP_DRY_RUN = 1, 256
@@ -238,6 +243,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_field_copy.argtypes = [FP, FP, I, DOM, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_vertical_remap.restype = I
     lib.gt4mi_vertical_remap.argtypes = [FP, FP, I, FP, FP, DOM, ctypes.c_int64, ctypes.c_int64, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_vertical_interp.restype = I
+    lib.gt4mi_vertical_interp.argtypes = [FP, FP, I, FP, FP, DOM, ctypes.c_int64, ctypes.c_int64, I, I, I, I, ctypes.c_double, I, P,
+                                          ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_horizontal_interp.restype = I
     lib.gt4mi_horizontal_interp.argtypes = [FP, FP, I, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_overlap_table.restype = I

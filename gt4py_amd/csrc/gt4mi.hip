@@ -15,6 +15,7 @@
 #include "level_stats.hip.h"
 #include "field_copy.hip.h"
 #include "vertical_remap.hip.h"
+#include "vertical_interp.hip.h"
 #include "horizontal_interp.hip.h"
 #include "horizontal_remap.hip.h"
 #include "line_solve.hip.h"
@@ -226,6 +227,13 @@ int gt4mi_vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfi
                          int edge_elem_size, int method, int flags, void* stream, int* launches) {
     return gt4mi::vertical_remap(dst, src, nfields, src_edges, dst_edges, extent_ij, ns, nd, elem_size, edge_elem_size, method, flags,
                                  static_cast<hipStream_t>(stream), launches);
+}
+
+int gt4mi_vertical_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_coord,
+                          const gt4mi_field* dst_coord, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
+                          int coord_elem_size, int method, int outside, double fill_value, int flags, void* stream, int* launches) {
+    return gt4mi::vertical_interp(dst, src, nfields, src_coord, dst_coord, extent_ij, ns, nd, elem_size, coord_elem_size, method, outside,
+                                  fill_value, flags, static_cast<hipStream_t>(stream), launches);
 }
 
 int gt4mi_horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* pos_i,

@@ -318,6 +318,68 @@ int gt4mi_vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfi
                          const gt4mi_field* dst_edges, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
                          int edge_elem_size, int method, int flags, void* stream, int* launches);
 
+/* ---- vertical interpolation to run-time levels (NEW entry, additive: the ABI version stays 8; no reference counterpart -- gt4py leaves
+ * output on pressure, height or isentropic levels and the vertical half of a semi-Lagrangian step to user stencils: a `while` loop, a
+ * carried run-time K index and reads at a run-time K index, one field per call, the search and the weights repeated for every field)
+ * Writes to dst[n], at each of the `nd` target levels of every column (i, j) of the box, the POINT value of src[n] at the coordinate
+ * that dst_coord holds for that level, src[n] given at the `ns` source levels whose coordinates src_coord holds, for `nfields` pairs
+ * that share ONE pair of coordinate fields, in ONE kernel launch per 8 pairs, on `stream`, without synchronisation or allocation.  The
+ * box is [origin, origin + extent_ij) in I and J of every field; along K a src and src_coord hold `ns` levels from their origin, a dst
+ * and dst_coord `nd`.  `elem_size` (fields) and `coord_elem_size` (coordinate fields) are 4 (float32) or 8 (float64) and need not
+ * match.  A coordinate field may have byte stride 0 along I and / or J: a Field[K] of fixed levels broadcasts without a copy and is
+ * exempt from the shape check on that axis.  A src stride of 0 broadcasts too; a dst stride of 0 on an extent above 1 is
+ * GT4MI_ERR_INVALID_ARGUMENT.  Source coordinates are meant to increase strictly with k (negate a coordinate that decreases); target
+ * coordinates may come in ANY order (departure heights are not monotone).  Interpolation that is linear in ln p takes ln p as the
+ * coordinate: the kernel computes no logarithm.
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/vertical_interp.hip.h states it again, tests/vertical_interp_ref.py restates it in plain
+ * Python and in numpy).  All of it is float64, one IEEE rounding per operation, no FMA; float32 items and coordinates are widened
+ * exactly on load and the result is rounded once on store.  Per column: coordinates z[0..ns-1], targets x[0..nd-1], values q[0..ns-1]
+ * of each field.  A bracket index k starts at 0 and is carried from one target of the column to the next, in the order m = 0, 1, ...,
+ * nd-1.  For a target x:
+ *   1. hunt:    while k < ns-2 and z[k+1] <= x: k += 1;  then  while k > 0 and z[k] > x: k -= 1.  k changes nowhere else.
+ *   2. outside: below = x < z[0], above = x > z[ns-1].  With `outside` =
+ *        GT4MI_VINTERP_OUTSIDE_FILL    store fill_value -- the double rounded once to the item type, a NaN as the canonical quiet NaN
+ *                                      (0x7FC00000 / 0x7FF8000000000000) -- and go to the next target
+ *        GT4MI_VINTERP_OUTSIDE_CLAMP   x = z[0] (below) or x = z[ns-1] (above) before step 3: the end level's value
+ *        GT4MI_VINTERP_OUTSIDE_LINEAR  x stays, and step 3 uses the linear formula whatever the method: the end interval's line,
+ *                                      extended; GT4MI_VINTERP_NEAREST moves item 0 (below) or item ns-1 (above)
+ *   3. inside, with h = z[k+1] - z[k] and t = (x - z[k]) / h (one IEEE division):
+ *        GT4MI_VINTERP_NEAREST         the ITEM q[k+1] if t >= 0.5, else q[k]: the bit pattern is moved (a NaN payload survives); if x is
+ *                                      NaN the canonical quiet NaN is stored
+ *        GT4MI_VINTERP_LINEAR          out = (1.0 - t) * q[k] + t * q[k+1], both products rounded before the addition; a weight of zero
+ *                                      still multiplies (0 * inf = NaN on a source level next to an infinity)
+ *        GT4MI_VINTERP_CUBIC           if k < 1 or k > ns-3 (the end intervals, and every interval when ns < 4) the linear formula;
+ *                                      otherwise Lagrange on the four nodes z0..z3 = z[k-1..k+2] with q0..q3 = q[k-1..k+2]:
+ *                                      w_a = (product of (x - z_b) for b != a, left to right in b) / (product of (z_a - z_b) for b != a,
+ *                                      left to right in b), one division per weight, e.g. w1 = (((x - z0) * (x - z2)) * (x - z3)) /
+ *                                      (((z1 - z0) * (z1 - z2)) * (z1 - z3));  out = ((w0*q0 + w1*q1) + w2*q2) + w3*q3
+ *        GT4MI_VINTERP_CUBIC_MONOTONE  the cubic out, then -- only where the cubic formula was used -- out = mn if out < mn else (mx if
+ *                                      out > mx else out), mn = min(q[k], q[k+1]), mx = max(q[k], q[k+1]), min(a, b) = b if b < a else
+ *                                      a, max(a, b) = b if b > a else a; a NaN out stays NaN
+ *   4. the bracket, t and the weights of a target are computed ONCE for all fields of the call.
+ * Path independence: for strictly increasing z and a non-NaN x, step 1 ends at the largest k <= ns-2 with z[k] <= x, or at 0 when there
+ * is none, wherever it started; a target's bits therefore depend on neither the other targets of the column nor their order, and not
+ * on layout, strides, alignment, position in the call, number of fields in the call, Field[K] versus an IJK coordinate field with the
+ * same items, or device.  The loops end whatever the data holds: the first only increments k below ns-2, the second only decrements it
+ * above 0, so a target costs at most ns-2 steps each way and the target loop counts to nd; a NaN x leaves k where it was and yields NaN
+ * through the arithmetic; NaN, repeated or non-monotone z change which comparisons hold (and give that column whatever IEEE arithmetic
+ * gives), never the bounds, and affect no other column.  Every K index of a load is k-1 ... k+2 within 0 ... ns-1 by those integers, 0
+ * or ns-1; every K index of a store is m < nd: no address depends on the data.
+ * Refusals: null pointers, nfields < 1, ns < 2 (one level has nothing to interpolate between), nd < 1, an extent out of range, an
+ * unknown method, outside value or flag (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a misaligned or wrongly strided
+ * field (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS); a dst stride of 0 on an extent above 1
+ * (GT4MI_ERR_INVALID_ARGUMENT: only a src or a coordinate field may be broadcast); the bytes of a dst box (first to last item) meeting
+ * those of any src box, of a coordinate field or of another dst box (GT4MI_ERR_UNSUPPORTED, the rule of gt4mi_field_copy).  No byte
+ * outside the dst boxes changes.  An extent with a zero entry is GT4MI_OK, nothing enqueued.  Every check runs before the first launch;
+ * a refused call enqueues nothing.  With GT4MI_VINTERP_DRY_RUN the checks run, *launches is set and no device is touched.  *launches
+ * (may be NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_VINTERP_NEAREST = 0, GT4MI_VINTERP_LINEAR = 1, GT4MI_VINTERP_CUBIC = 2, GT4MI_VINTERP_CUBIC_MONOTONE = 3 };
+enum { GT4MI_VINTERP_OUTSIDE_CLAMP = 0, GT4MI_VINTERP_OUTSIDE_LINEAR = 1, GT4MI_VINTERP_OUTSIDE_FILL = 2 };
+enum { GT4MI_VINTERP_DRY_RUN = 256 };
+int gt4mi_vertical_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_coord,
+                          const gt4mi_field* dst_coord, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
+                          int coord_elem_size, int method, int outside, double fill_value, int flags, void* stream, int* launches);
+
 /* ---- horizontal interpolation at run-time positions (NEW entry, additive: the ABI version stays 8; no reference counterpart -- GTScript
  * takes compile-time horizontal offsets only, and gt4py leaves a gather at data-dependent I / J positions (semi-Lagrangian departure
  * points, sampling on a rotated, shifted or nested grid) to fancy indexing on its numpy / cupy storages) --------------------------------
