@@ -109,21 +109,25 @@ GT_DEV double gt_max(double a, double b) { return (a != a || b != b) ? a + b : (
 GT_DEV float gt_max(float a, float b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
 template <class T> GT_DEV T gt_min(T a, T b) { return a < b ? a : b; }
 template <class T> GT_DEV T gt_max(T a, T b) { return a > b ? a : b; }
-// numpy.remainder: result takes the sign of the divisor (npy_divmod)
+// numpy.remainder: result takes the sign of the divisor (npy_divmod).  fmod is the device library's, which is exact: the
+// compiler's own lowering of __builtin_fmod (frem) is a - trunc(a / b) * b with a rounded quotient, off by a whole b
+// now and then (found by the typed fuzzer)
+extern "C" __device__ double __ocml_fmod_f64(double, double);
+extern "C" __device__ float __ocml_fmod_f32(float, float);
 GT_DEV double gt_mod(double a, double b) {
-    double m = __builtin_fmod(a, b);
+    double m = __ocml_fmod_f64(a, b);
     if (b == 0.0) return m;
     if (m != 0.0) { if ((b < 0.0) != (m < 0.0)) m += b; } else { m = __builtin_copysign(0.0, b); }
     return m;
 }
 GT_DEV float gt_mod(float a, float b) {
-    float m = __builtin_fmodf(a, b);
+    float m = __ocml_fmod_f32(a, b);
     if (b == 0.0f) return m;
     if (m != 0.0f) { if ((b < 0.0f) != (m < 0.0f)) m += b; } else { m = __builtin_copysignf(0.0f, b); }
     return m;
 }
 template <class T> GT_DEV T gt_mod(T a, T b) {
-    if (b == 0) return 0;
+    if (b == 0 || b == -1) return 0;  // (min % -1 overflows in C; numpy gives 0)
     T m = a % b;
     return (m != 0 && ((m < 0) != (b < 0))) ? m + b : m;
 }
@@ -136,16 +140,47 @@ extern "C" __device__ double __ocml_erfc_f64(double);
 extern "C" __device__ float __ocml_erfc_f32(float);
 extern "C" __device__ double __ocml_tgamma_f64(double);
 extern "C" __device__ float __ocml_tgamma_f32(float);
-GT_DEV double gt_pow(double a, double b) { return __ocml_pow_f64(a, b); }
+// Whole exponents 1..16 of a finite, non-zero base: repeated multiplication in double-double (error some 2^-100 of the
+// value), so that a power that is representable comes out exact, as the host's pow gives it; the device library's pow is a
+// unit in the last place off there (0.5 ** 4 = 0x1.fffffffffffffp-5; found by the typed fuzzer).  Results near the ends of
+// the exponent range, and every other argument, are the device library's.
+GT_DEV double gt_pow(double a, double b) {
+    if (b >= 1.0 && b <= 16.0 && b == __builtin_trunc(b) && (a - a) == 0.0 && a != 0.0) {
+        double hi = 1.0, lo = 0.0;
+        for (int n = (int)b; n > 0; --n) {
+            const double p = hi * a;
+            const double e = __builtin_fma(lo, a, __builtin_fma(hi, a, -p));
+            hi = p + e;
+            lo = e - (hi - p);
+        }
+        const double m = __builtin_fabs(hi);
+        if (m > 0x1p-900 && m < 0x1p1000) return hi;
+    }
+    return __ocml_pow_f64(a, b);
+}
 GT_DEV float gt_pow(float a, float b) { return __ocml_pow_f32(a, b); }
 template <class T> GT_DEV T gt_pow(T a, T b) {
     T r = 1;
     for (T n = 0; n < b; ++n) r *= a;
     return r;
 }
+// int32 / int64 wrap around like numpy's: the arithmetic is done in the unsigned type of the same width (signed overflow is
+// undefined in C, and the compiler uses that: it widened an int32 `abs(a - b)` stored to an int64 field)
+GT_DEV int gt_pow(int a, int b) {
+    unsigned r = 1u;
+    for (int n = 0; n < b; ++n) r *= (unsigned)a;
+    return (int)r;
+}
+GT_DEV long long gt_pow(long long a, long long b) {
+    unsigned long long r = 1ull;
+    for (long long n = 0; n < b; ++n) r *= (unsigned long long)a;
+    return (long long)r;
+}
 GT_DEV double gt_abs(double a) { return __builtin_fabs(a); }
 GT_DEV float gt_abs(float a) { return __builtin_fabsf(a); }
 template <class T> GT_DEV T gt_abs(T a) { return a < 0 ? -a : a; }
+GT_DEV int gt_abs(int a) { return a < 0 ? (int)(0u - (unsigned)a) : a; }
+GT_DEV long long gt_abs(long long a) { return a < 0 ? (long long)(0ull - (unsigned long long)a) : a; }
 #define GT_MATH1(name, fd, ff) \
     GT_DEV double gt_##name(double a) { return fd(a); } \
     GT_DEV float gt_##name(float a) { return ff(a); }
@@ -250,6 +285,9 @@ template <class T> GT_DEV bool gt_isinf(T a) { return a == a && (a - a) != (a - 
 template <class T> GT_DEV bool gt_isfinite(T a) { return (a - a) == (a - a); }
 """
 
+# int32 / int64 `+ - *` and negation are emitted in the unsigned type of the same width, so that they wrap like numpy's
+# (int8 / int16 operands are promoted to int by C and cannot overflow it); float programs are emitted as before
+_WRAPPING = {"int": "unsigned int", "long long": "unsigned long long"}
 _EXACT_CALLS = {"abs", "min", "max", "mod", "sqrt", "floor", "ceil", "trunc", "isfinite", "isinf", "isnan", "round",
                 "round_away_from_zero"}
 
@@ -426,9 +464,13 @@ class _Emitter:
         if isinstance(e, ir.UnaryOp):
             if e.op == "not":
                 return f"(!({rec(e.expr)}))"
+            if e.op == "-" and ct in _WRAPPING:
+                return f"(({ct})(-({_WRAPPING[ct]})({rec(e.expr)})))"
             return f"(({ct})({e.op}({rec(e.expr)})))"
         if isinstance(e, ir.BinaryOp):
             left, right = rec(e.left), rec(e.right)
+            if e.op in ("+", "-", "*") and ct in _WRAPPING:
+                return f"(({ct})(({_WRAPPING[ct]})({left}) {e.op} ({_WRAPPING[ct]})({right})))"
             if e.op in ("+", "-", "*", "/"):
                 return f"(({ct})(({left}) {e.op} ({right})))"
             if e.op == "%":
@@ -771,7 +813,8 @@ class _Emitter:
         L = self.lines
         stage_fwd = {n: d for (s_i, n), d in self.plan.forwarded.items() if s_i == si}
         for n in stage_fwd:  # r_<n>: the level behind the sweep, alive across the stage's nests
-            L.append(f"    {_CTYPE[self.decl_dtype[n].name]} r_{_c_ident(n)} = {_CTYPE[self.decl_dtype[n].name]}();")
+            ct = _CTYPE[self.decl_dtype[n].name]  # `signed char()` / `long long()` are not expressions: two-word names get a cast
+            L.append(f"    {ct} r_{_c_ident(n)} = {f'({ct})0' if ' ' in ct else f'{ct}()'};")
         if self.tc is not None:
             cache, n_reg, n_lds, threads = self.tc
             L.append(f"    const unsigned tc_tid = threadIdx.y * {threads // max(1, TUNING['block_column'][1])} + threadIdx.x;")

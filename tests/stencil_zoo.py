@@ -474,3 +474,38 @@ def make_inputs(stencil_object, domain, seed=1337):
         arrays[name] = data
         origins[name] = tuple(origin)
     return arrays, origins
+
+
+def make_typed_inputs(stencil_object, domain, seed=1337):
+    """Arrays sized domain + boundary for every field of a built stencil -> (arrays, origins), like ``stencil_zoo.make_inputs``:
+    finite floats (a quarter of them small multiples of 0.5, so that comparisons with integers hit equality), integers in +-50
+    with about 3 % of the items from {min, min + 1, -1, 0, 1, max} of the field's dtype, random bools."""
+    rng = np.random.default_rng(seed + 77003)
+    arrays, origins = {}, {}
+    for name, info in stencil_object.field_info.items():
+        if info is None:
+            continue
+        shape, origin = [], []
+        for axis, d in zip("IJK", domain):
+            if axis not in info.axes:
+                continue
+            lo, hi = (max(0, int(b)) for b in info.boundary["IJK".index(axis)])
+            shape.append(int(d) + lo + hi)
+            origin.append(lo)
+        shape += [int(n) for n in info.data_dims]
+        origin += [0] * len(info.data_dims)
+        dt = np.dtype(info.dtype)
+        if dt.kind == "f":
+            data = rng.uniform(-3.0, 3.0, shape)
+            exact = rng.integers(-6, 7, shape) * 0.5
+            data = np.where(rng.random(shape) < 0.25, exact, data).astype(dt)
+        elif dt.kind == "i":
+            data = rng.integers(-50, 51, shape).astype(dt)
+            lim = np.iinfo(dt)
+            edge = np.array([lim.min, lim.min + 1, -1, 0, 1, lim.max], dtype=dt)
+            data = np.where(rng.random(shape) < 0.03, edge[rng.integers(0, len(edge), shape)], data).astype(dt)
+        else:
+            data = rng.integers(0, 2, shape).astype(dt)
+        arrays[name] = data
+        origins[name] = tuple(origin)
+    return arrays, origins
