@@ -1,10 +1,20 @@
 """What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
 ``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``linesolve.LineSolve``) share on the Python side: turning a refusal of the library into an
-exception, normalising halo / origin / domain / field lists, and binding a checked call to the caller's objects.  A new
-utility states what differs (its name in the messages, its extra fields) and takes the rest from here."""
+exception, normalising halo / origin / domain / field lists, the native field tables, the dry run, and binding a checked call to
+the caller's objects.
+
+A new utility is a subclass of :class:`Bound` that states ``_entry`` (the C entry's name), ``_dry_run_bit`` (the entry's
+``*_DRY_RUN`` flag) and ``_arguments()``: the entry's argument list, written ONCE, with :data:`FLAGS` and :data:`STREAM` where the
+flags and the stream go and an :class:`Out` where the entry takes an out-pointer (``launches``, ``workspace_needed``, ``path``,
+``paths``).  Its constructor checks what only Python can say (names, dtypes, dimensions, the messages in its own words), builds
+the descriptors (:func:`field_table`, :func:`_common_domain`), sets ``_flags`` where the object has flags of its own, calls
+:meth:`Bound._dry_run` -- every check of the library on exactly that list, nothing enqueued, the out values returned -- and
+:meth:`Bound._bind` last.  ``__call__`` is the base's: the same list with the object's flags, the stream that is current then and
+null out-pointers."""
 
 from __future__ import annotations
 
+import ctypes
 import weakref
 from typing import NoReturn, Sequence, Tuple
 
@@ -79,6 +89,25 @@ def _box_of(first: DeviceArray, halo4, origin, domain, least: int):
     return origin, _triple(domain, "domain", 1)
 
 
+def _common_domain(arrays, halo4, origin, listed, axes: int = 3, least_k: int = 0) -> Tuple[int, ...]:
+    """The common compute domain along the first ``axes`` axes: what every one of ``arrays`` has left behind ``origin`` and (in I and
+    J) in front of its high ghost cells, over the axes it has.  ``listed``: the arrays whose shapes the refusal names; ``least_k``:
+    the fewest levels (where ``axes`` is 3)."""
+    high = (halo4[1], halo4[3], 0)
+    domain = tuple(min(a.shape[x] - origin[x] - high[x] for a in arrays if a.ndim > x) for x in range(axes))
+    if min(domain) < 0 or (axes == 3 and domain[2] < least_k):
+        raise ValueError(f"halo {halo4} and origin {origin} leave no domain in fields of shapes {[a.shape for a in listed]}")
+    return domain
+
+
+def field_table(arrays, start):
+    """The native ``_lib.Field`` table of ``arrays`` (IJK, or IJ: one level), every box starting at ``start``."""
+    table = (_lib.Field * len(arrays))()
+    for n, a in enumerate(arrays):
+        table[n] = _lib.Field.make(a.ptr, _shape3(a), tuple(a.strides) + (0,) * (3 - a.ndim), start)
+    return table
+
+
 def _pair_lists(who: str, dst, src, halo, method=None, methods=None, shared=(), roles=("destination(s)", "source(s)")):
     """The opening of a call on (dst, src) pairs, in the order the checks have always had: two lists of equal length, a known
     ``method`` (where there are ``methods``), DeviceArrays of everything (``shared``: fields every pair reads), the halo.
@@ -129,13 +158,62 @@ def refuse_host_arrays(who: str, arrays) -> None:
             raise TypeError(f"{who} works on device fields; a host array was passed")
 
 
+#: the slots of an argument list that the dry run and the call fill differently
+FLAGS, STREAM = object(), object()
+
+
+class Out:
+    """An out-pointer slot of an argument list: a ``ctype`` the entry writes one of, or an array type it fills."""
+
+    def __init__(self, ctype):
+        self.ctype = ctype
+
+
+def dry_run(entry: str, dry_run_bit: int, flags: int, arguments) -> list:
+    """Entry ``entry`` on ``arguments`` with ``dry_run_bit`` set in the flags, a null stream and real out-pointers: every check of
+    the library, nothing enqueued.  A refusal becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the library's
+    message.  Returns what the entry left behind the out-pointers, in their order (an array as a list)."""
+    outs = []
+
+    def slot(a):
+        if a is FLAGS:
+            return flags | dry_run_bit
+        if a is STREAM:
+            return None
+        if isinstance(a, Out):
+            outs.append(a.ctype())
+            return outs[-1] if isinstance(outs[-1], ctypes.Array) else ctypes.byref(outs[-1])
+        return a
+
+    rc = getattr(_lib.load(), entry)(*[slot(a) for a in arguments])
+    if rc != _lib.OK:
+        raise_refusal(entry, rc)
+    return [list(o) if isinstance(o, ctypes.Array) else o.value for o in outs]
+
+
 class Bound:
-    """Base of the frozen calls: a constructor checks its arguments through the library's dry run, builds the native
-    descriptors and calls :meth:`_bind` last; ``__call__`` is :meth:`_check_alive` and the one ctypes call."""
+    """Base of the frozen calls: a constructor builds the native descriptors, checks them through the library's dry run
+    (:meth:`_dry_run`) and calls :meth:`_bind` last; ``__call__`` is :meth:`_check_alive` and the one ctypes call, both on the
+    argument list that :meth:`_arguments` states."""
+
+    _entry = ""        # the C entry
+    _dry_run_bit = 0   # its *_DRY_RUN flag
+    _flags = 0         # the flags of the object's own calls
+
+    def _arguments(self) -> tuple:
+        """The entry's arguments in order, :data:`FLAGS`, :data:`STREAM` and :class:`Out` where those go."""
+        raise NotImplementedError
+
+    def _dry_run(self) -> list:
+        return dry_run(self._entry, self._dry_run_bit, self._flags, self._arguments())
 
     def _bind(self, who: str, arrays, objects) -> None:
         """``who``: the public function's name; ``arrays``: the DeviceArrays of the call; ``objects``: what the caller passed."""
         refuse_host_arrays(who, arrays)  # (last: none of the checks before needs a device)
+        # the call's arguments, built once: all but the stream, which is the one current at the call
+        arguments = [self._flags if a is FLAGS else None if isinstance(a, Out) else a for a in self._arguments()]
+        at = next(n for n, a in enumerate(arguments) if a is STREAM)
+        self._before, self._after = tuple(arguments[:at]), tuple(arguments[at + 1:])
         # what must stay alive is what the CALLER holds: for a torch tensor or another exporter `as_device_array` made a wrapper
         # that dies with the constructor, so the weak reference goes to the object that was passed; one that cannot be weakly
         # referenced is held instead
@@ -148,7 +226,13 @@ class Bound:
         import torch
 
         self._current_stream = torch.cuda.current_stream
-        self._lib = _lib.load()
+        self._native = getattr(_lib.load(), self._entry)
+
+    def __call__(self) -> None:
+        self._check_alive()
+        rc = self._native(*self._before, self._current_stream().cuda_stream, *self._after)
+        if rc != _lib.OK:
+            _lib.check(self._entry, rc)
 
     def _check_alive(self) -> None:
         for r in self._refs:  # (a plain loop: this runs in front of every call)

@@ -25,7 +25,7 @@ from typing import Any, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._bound import Bound, _box_of, _halo4, _shape3, raise_refusal
+from ._bound import FLAGS, STREAM, Bound, Out, _box_of, _halo4, field_table
 from .storage.device_array import DeviceArray, as_device_array
 
 I_LO, I_HI, J_LO, J_HI = _lib.HALO_I_LO, _lib.HALO_I_HI, _lib.HALO_J_LO, _lib.HALO_J_HI
@@ -60,23 +60,18 @@ def _mode_pair(mode) -> Tuple[int, int]:
     return MODES[pair[0]], MODES[pair[1]]
 
 
-def _native(fields, nfields: int, domain, halo4, modes, sides: int, value, itemsize: int, stream: Optional[int]) -> int:
-    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for an item size no kernel moves)
-    with the library's message.  Returns the number of kernels enqueued."""
-    launches = ctypes.c_int(0)
-    rc = _lib.load().gt4mi_halo_fill(fields, nfields, domain, halo4, modes[0], modes[1], sides, value, itemsize, stream,
-                                     ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_halo_fill", rc)
-    return launches.value
-
-
 class HaloFill(Bound):
     """The frozen form of :func:`fill_halo` (what ``FrozenStencil`` is for stencils): arguments are checked and the native
     descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is current THEN.
 
     The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it refuses to run once one of
     them has died.  (An exporter that cannot be weakly referenced is held instead, so its memory stays valid.)"""
+
+    _entry, _dry_run_bit = "gt4mi_halo_fill", _lib.HALO_DRY_RUN
+
+    def _arguments(self) -> tuple:  # (the sides are the entry's flags)
+        return (self._fields, self._n, self._domain3, self._halo4, self._modes[0], self._modes[1], FLAGS, self._value, self._itemsize,
+                STREAM, Out(ctypes.c_int))
 
     def __init__(self, fields: Sequence[Any], *, halo, mode, origin: Optional[Sequence[int]] = None,
                  domain: Optional[Sequence[int]] = None, value=0, sides: int = ALL):
@@ -90,7 +85,7 @@ class HaloFill(Bound):
             raise TypeError(f"sides must be a bit mask of I_LO, I_HI, J_LO, J_HI, not {type(sides).__name__}")
         if int(sides) & ~ALL:
             raise ValueError(f"sides must be a bit mask of I_LO, I_HI, J_LO, J_HI (0..{ALL}), not {int(sides)}")
-        self._sides = int(sides)
+        self._sides = self._flags = int(sides)
         first = arrays[0]
         for a in arrays:
             if a.ndim not in (2, 3):
@@ -110,22 +105,12 @@ class HaloFill(Bound):
             raise TypeError("value must be a scalar")
         self._value = ctypes.create_string_buffer(item.tobytes(), 8)
         self._n = len(arrays)
-        self._fields = (_lib.Field * self._n)()
-        for n, a in enumerate(arrays):
-            self._fields[n] = _lib.Field.make(a.ptr, _shape3(a), tuple(a.strides) + (0,) * (3 - a.ndim), origin)
+        self._fields = field_table(arrays, origin)
         self._domain3 = _lib.domain3(domain)
         self._halo4 = (ctypes.c_int64 * 4)(*self._halo)
         # every check of the library, nothing enqueued; also: how many kernels a call makes
-        self.launches = _native(self._fields, self._n, self._domain3, self._halo4, self._modes, self._sides | _lib.HALO_DRY_RUN,
-                                self._value, self._itemsize, None)
+        self.launches, = self._dry_run()
         self._bind("fill_halo", arrays, fields)
-
-    def __call__(self) -> None:
-        self._check_alive()
-        rc = self._lib.gt4mi_halo_fill(self._fields, self._n, self._domain3, self._halo4, self._modes[0], self._modes[1],
-                                       self._sides, self._value, self._itemsize, self._current_stream().cuda_stream, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_halo_fill", rc)
 
 
 def fill_halo(*fields, halo, mode, origin: Optional[Sequence[int]] = None, domain: Optional[Sequence[int]] = None, value=0,

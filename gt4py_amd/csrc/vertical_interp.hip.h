@@ -45,31 +45,26 @@
 // another dst box.
 #pragma once
 
+#include "column_entry.hip.h"
 #include "common.hip.h"
-#include "field_args.hip.h"
 #include "horizontal_interp.hip.h"  // InterpBits, interp_min, interp_max
 
 namespace gt4mi {
 
-constexpr int VINTERP_TILE_I = 64, VINTERP_TILE_J = 4;
-
-struct VInterpArgs {
-    PairEntry e[PAIR_MAX_FIELDS];
-    SharedField zs, zd;  // level 0 of the box's first column; stride 0 along I / J broadcasts
-    double fill;         // what GT4MI_VINTERP_FILL stores (rounded once to the item type in the kernel)
-    int ni, nj, ns, nd, nf, outside;
-    unsigned tiles_i;
+struct VInterpArgs : ColumnArgs {  // (zs / zd: the coordinates)
+    double fill;  // what GT4MI_VINTERP_FILL stores (rounded once to the item type in the kernel)
+    int outside;
 };
 
 // T: item type of the fields, E: of the coordinates, METHOD: GT4MI_VINTERP_*, NF: entries the kernel has registers for (a.nf <= NF)
 template <typename T, typename E, int METHOD, int NF>
-__global__ void __launch_bounds__(VINTERP_TILE_I * VINTERP_TILE_J)
+__global__ void __launch_bounds__(COLUMN_TILE_I * COLUMN_TILE_J)
 vertical_interp_kernel(const VInterpArgs a) {
     using U = typename InterpBits<T>::type;
     constexpr bool NEAREST = METHOD == GT4MI_VINTERP_NEAREST;
     constexpr bool CUBIC = METHOD == GT4MI_VINTERP_CUBIC || METHOD == GT4MI_VINTERP_CUBIC_MONOTONE;
     const unsigned tj = blockIdx.x / a.tiles_i, ti = blockIdx.x - tj * a.tiles_i;
-    const int64_t i = (int64_t)ti * VINTERP_TILE_I + (threadIdx.x & 63u), j = (int64_t)tj * VINTERP_TILE_J + (threadIdx.x >> 6);
+    const int64_t i = (int64_t)ti * COLUMN_TILE_I + (threadIdx.x & 63u), j = (int64_t)tj * COLUMN_TILE_J + (threadIdx.x >> 6);
     if (i >= a.ni || j >= a.nj) return;
     const int ns = a.ns, nd = a.nd, nf = a.nf, outside = a.outside;
     const E* const zs = reinterpret_cast<const E*>(a.zs.p) + i * a.zs.s[0] + j * a.zs.s[1];
@@ -171,14 +166,15 @@ vertical_interp_kernel(const VInterpArgs a) {
     }
 }
 
-const BoxChecks VINTERP_CHECKS = {"vertical_interp", "extent", "only a src or a coordinate field may be broadcast", false, false};
-constexpr int VINTERP_COORD_FREE_AXES = 3;  // a Field[K] of levels: stride 0 along I / J, one item for every i / j, no shape to check
+const ColumnEntry VINTERP_ENTRY = {"vertical_interp", {"src_coord", "dst_coord"}, "coordinate", 0, 2,
+                                   "at least two source levels and one target level are needed", GT4MI_VINTERP_DRY_RUN,
+                                   {"vertical_interp", "extent", "only a src or a coordinate field may be broadcast", false, false}};
 
 template <typename T, typename E, int METHOD>
 inline void vinterp_launch(const VInterpArgs& a, int64_t blocks, hipStream_t stream) {
     with_pair_entries(a.nf, [&](auto nf) {
         hipLaunchKernelGGL((vertical_interp_kernel<T, E, METHOD, decltype(nf)::value>), dim3((unsigned)blocks),
-                           dim3(VINTERP_TILE_I * VINTERP_TILE_J), 0, stream, a);
+                           dim3(COLUMN_TILE_I * COLUMN_TILE_J), 0, stream, a);
     });
 }
 
@@ -186,47 +182,18 @@ inline void vinterp_launch(const VInterpArgs& a, int64_t blocks, hipStream_t str
 inline int vertical_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_coord,
                            const gt4mi_field* dst_coord, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
                            int coord_elem_size, int method, int outside, double fill_value, int flags, hipStream_t stream, int* launches) {
-    if (launches) *launches = 0;
-    if (dst == nullptr || src == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: %s is null", dst == nullptr ? "dst" : "src");
-    if (src_coord == nullptr || dst_coord == nullptr)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: %s is null", src_coord == nullptr ? "src_coord" : "dst_coord");
-    if (extent_ij == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: extent_ij is null");
-    if (nfields < 1) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: nfields = %d, at least one pair is needed", nfields);
-    if (ns < 2 || nd < 1 || ns >= INT32_MAX - 2 || nd >= INT32_MAX - 2)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT,
-                    "vertical_interp: ns = %lld source and nd = %lld target levels, at least two source levels and one target level are needed",
-                    (long long)ns, (long long)nd);
-    for (int ax = 0; ax < 2; ++ax)
-        if (extent_ij[ax] < 0 || extent_ij[ax] > INT32_MAX)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: invalid extent %lld along axis %d", (long long)extent_ij[ax], ax);
-    if (flags & ~GT4MI_VINTERP_DRY_RUN) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: unknown bits in flags 0x%x", (unsigned)flags);
+    if (int rc = column_call(VINTERP_ENTRY, dst, src, nfields, src_coord, dst_coord, extent_ij, ns, nd, flags, launches)) return rc;
     if (method < GT4MI_VINTERP_NEAREST || method > GT4MI_VINTERP_CUBIC_MONOTONE)
         return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: unknown method %d", method);
     if (outside < GT4MI_VINTERP_OUTSIDE_CLAMP || outside > GT4MI_VINTERP_OUTSIDE_FILL)
         return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_interp: unknown outside value %d", outside);
-    if (elem_size != 4 && elem_size != 8)
-        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_interp: field item size %d is not supported (float32 or float64)", elem_size);
-    if (coord_elem_size != 4 && coord_elem_size != 8)
-        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_interp: coordinate item size %d is not supported (float32 or float64)", coord_elem_size);
-    const int64_t d_ext[3] = {extent_ij[0], extent_ij[1], nd}, s_ext[3] = {extent_ij[0], extent_ij[1], ns};
-    for (int n = 0; n < nfields; ++n) {
-        if (int rc = check_box_field(VINTERP_CHECKS, "dst", n, dst[n], d_ext, elem_size, true)) return rc;
-        if (int rc = check_box_field(VINTERP_CHECKS, "src", n, src[n], s_ext, elem_size, false)) return rc;
-    }
-    if (int rc = check_box_field(VINTERP_CHECKS, "src_coord", 0, *src_coord, s_ext, coord_elem_size, false, VINTERP_COORD_FREE_AXES)) return rc;
-    if (int rc = check_box_field(VINTERP_CHECKS, "dst_coord", 0, *dst_coord, d_ext, coord_elem_size, false, VINTERP_COORD_FREE_AXES)) return rc;
-    if (extent_ij[0] == 0 || extent_ij[1] == 0) return GT4MI_OK;
-    const NamedSpan coords[2] = {{"src_coord", box_span(*src_coord, s_ext, coord_elem_size)}, {"dst_coord", box_span(*dst_coord, d_ext, coord_elem_size)}};
-    if (int rc = check_pairs_disjoint("vertical_interp", dst, src, nfields, d_ext, s_ext, elem_size, elem_size, nullptr, coords, 2)) return rc;
-    const int64_t tiles_i = cdiv(extent_ij[0], VINTERP_TILE_I), blocks = tiles_i * cdiv(extent_ij[1], VINTERP_TILE_J);
-    if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_interp: too many columns for one launch");
-    if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
-    if (flags & GT4MI_VINTERP_DRY_RUN) return GT4MI_OK;
     VInterpArgs a{};
-    a.zs = shared_field(*src_coord, coord_elem_size), a.zd = shared_field(*dst_coord, coord_elem_size);
-    a.fill = fill_value;
-    a.ni = (int)extent_ij[0], a.nj = (int)extent_ij[1], a.ns = (int)ns, a.nd = (int)nd, a.outside = outside;
-    a.tiles_i = (unsigned)tiles_i;
+    int64_t blocks = 0;
+    if (int rc = column_fields(VINTERP_ENTRY, a, &blocks, dst, src, nfields, src_coord, dst_coord, extent_ij, ns, nd, elem_size,
+                               coord_elem_size, flags, launches))
+        return rc;
+    if (blocks == 0) return GT4MI_OK;  // an empty extent or a dry run
+    a.fill = fill_value, a.outside = outside;
     int next = 0;
     while (next_pair_batch(a, dst, src, &next, nfields, elem_size)) {
         with_item_type(elem_size, [&](auto t) {

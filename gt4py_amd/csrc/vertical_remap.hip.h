@@ -34,19 +34,12 @@
 // which a dst box meets a src box, an edge field or another dst box.
 #pragma once
 
+#include "column_entry.hip.h"
 #include "common.hip.h"
-#include "field_args.hip.h"
 
 namespace gt4mi {
 
-constexpr int REMAP_TILE_I = 64, REMAP_TILE_J = 4;
-
-struct RemapArgs {
-    PairEntry e[PAIR_MAX_FIELDS];
-    SharedField zs, zd;  // edge 0 of the box's first column; stride 0 along I / J broadcasts
-    int ni, nj, ns, nd, nf;
-    unsigned tiles_i;
-};
+struct RemapArgs : ColumnArgs {};  // (zs / zd: the edges)
 
 // the limited centred slope across a cell of thickness hc, den = 0.5 h[k-1] + h[k] + 0.5 h[k+1] (horizontal_remap.hip.h reads den
 // from its overlap table)
@@ -67,11 +60,11 @@ __device__ __forceinline__ double remap_slope(double qm, double qc, double qp, d
 
 // T: item type of the fields, E: of the edges, METHOD: GT4MI_REMAP_*, NF: entries the kernel has registers for (a.nf <= NF)
 template <typename T, typename E, int METHOD, int NF>
-__global__ void __launch_bounds__(REMAP_TILE_I * REMAP_TILE_J)
+__global__ void __launch_bounds__(COLUMN_TILE_I * COLUMN_TILE_J)
 vertical_remap_kernel(const RemapArgs a) {
     constexpr bool PLM = METHOD == GT4MI_REMAP_PLM;
     const unsigned tj = blockIdx.x / a.tiles_i, ti = blockIdx.x - tj * a.tiles_i;
-    const int64_t i = (int64_t)ti * REMAP_TILE_I + (threadIdx.x & 63u), j = (int64_t)tj * REMAP_TILE_J + (threadIdx.x >> 6);
+    const int64_t i = (int64_t)ti * COLUMN_TILE_I + (threadIdx.x & 63u), j = (int64_t)tj * COLUMN_TILE_J + (threadIdx.x >> 6);
     if (i >= a.ni || j >= a.nj) return;
     const int ns = a.ns, nd = a.nd, nf = a.nf;
     const E* const zs = reinterpret_cast<const E*>(a.zs.p) + i * a.zs.s[0] + j * a.zs.s[1];
@@ -146,14 +139,14 @@ vertical_remap_kernel(const RemapArgs a) {
     }
 }
 
-const BoxChecks REMAP_CHECKS = {"vertical_remap", "extent", "only a src or an edge field may be broadcast", false, false};
-constexpr int REMAP_EDGE_FREE_AXES = 3;  // a Field[K] of edges: stride 0 along I / J, one item for every i / j, no shape to check
+const ColumnEntry REMAP_ENTRY = {"vertical_remap", {"src_edges", "dst_edges"}, "edge", 1, 1, "at least one each is needed", GT4MI_REMAP_DRY_RUN,
+                                 {"vertical_remap", "extent", "only a src or an edge field may be broadcast", false, false}};
 
 template <typename T, typename E, int METHOD>
 inline void remap_launch(const RemapArgs& a, int64_t blocks, hipStream_t stream) {
     with_pair_entries(a.nf, [&](auto nf) {
         hipLaunchKernelGGL((vertical_remap_kernel<T, E, METHOD, decltype(nf)::value>), dim3((unsigned)blocks),
-                           dim3(REMAP_TILE_I * REMAP_TILE_J), 0, stream, a);
+                           dim3(COLUMN_TILE_I * COLUMN_TILE_J), 0, stream, a);
     });
 }
 
@@ -161,44 +154,15 @@ inline void remap_launch(const RemapArgs& a, int64_t blocks, hipStream_t stream)
 inline int vertical_remap(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* src_edges,
                           const gt4mi_field* dst_edges, const int64_t extent_ij[2], int64_t ns, int64_t nd, int elem_size,
                           int edge_elem_size, int method, int flags, hipStream_t stream, int* launches) {
-    if (launches) *launches = 0;
-    if (dst == nullptr || src == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: %s is null", dst == nullptr ? "dst" : "src");
-    if (src_edges == nullptr || dst_edges == nullptr)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: %s is null", src_edges == nullptr ? "src_edges" : "dst_edges");
-    if (extent_ij == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: extent_ij is null");
-    if (nfields < 1) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: nfields = %d, at least one pair is needed", nfields);
-    if (ns < 1 || nd < 1 || ns >= INT32_MAX - 2 || nd >= INT32_MAX - 2)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: ns = %lld source and nd = %lld target levels, at least one each is needed",
-                    (long long)ns, (long long)nd);
-    for (int ax = 0; ax < 2; ++ax)
-        if (extent_ij[ax] < 0 || extent_ij[ax] > INT32_MAX)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: invalid extent %lld along axis %d", (long long)extent_ij[ax], ax);
-    if (flags & ~GT4MI_REMAP_DRY_RUN) return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: unknown bits in flags 0x%x", (unsigned)flags);
+    if (int rc = column_call(REMAP_ENTRY, dst, src, nfields, src_edges, dst_edges, extent_ij, ns, nd, flags, launches)) return rc;
     if (method != GT4MI_REMAP_PCM && method != GT4MI_REMAP_PLM)
         return fail(GT4MI_ERR_INVALID_ARGUMENT, "vertical_remap: unknown method %d", method);
-    if (elem_size != 4 && elem_size != 8)
-        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: field item size %d is not supported (float32 or float64)", elem_size);
-    if (edge_elem_size != 4 && edge_elem_size != 8)
-        return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: edge item size %d is not supported (float32 or float64)", edge_elem_size);
-    const int64_t d_ext[3] = {extent_ij[0], extent_ij[1], nd}, s_ext[3] = {extent_ij[0], extent_ij[1], ns};
-    const int64_t de_ext[3] = {extent_ij[0], extent_ij[1], nd + 1}, se_ext[3] = {extent_ij[0], extent_ij[1], ns + 1};
-    for (int n = 0; n < nfields; ++n) {
-        if (int rc = check_box_field(REMAP_CHECKS, "dst", n, dst[n], d_ext, elem_size, true)) return rc;
-        if (int rc = check_box_field(REMAP_CHECKS, "src", n, src[n], s_ext, elem_size, false)) return rc;
-    }
-    if (int rc = check_box_field(REMAP_CHECKS, "src_edges", 0, *src_edges, se_ext, edge_elem_size, false, REMAP_EDGE_FREE_AXES)) return rc;
-    if (int rc = check_box_field(REMAP_CHECKS, "dst_edges", 0, *dst_edges, de_ext, edge_elem_size, false, REMAP_EDGE_FREE_AXES)) return rc;
-    if (extent_ij[0] == 0 || extent_ij[1] == 0) return GT4MI_OK;
-    const NamedSpan edges[2] = {{"src_edges", box_span(*src_edges, se_ext, edge_elem_size)}, {"dst_edges", box_span(*dst_edges, de_ext, edge_elem_size)}};
-    if (int rc = check_pairs_disjoint("vertical_remap", dst, src, nfields, d_ext, s_ext, elem_size, elem_size, nullptr, edges, 2)) return rc;
-    const int64_t tiles_i = cdiv(extent_ij[0], REMAP_TILE_I), blocks = tiles_i * cdiv(extent_ij[1], REMAP_TILE_J);
-    if (blocks > INT32_MAX) return fail(GT4MI_ERR_UNSUPPORTED, "vertical_remap: too many columns for one launch");
-    if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
-    if (flags & GT4MI_REMAP_DRY_RUN) return GT4MI_OK;
     RemapArgs a{};
-    a.zs = shared_field(*src_edges, edge_elem_size), a.zd = shared_field(*dst_edges, edge_elem_size);
-    a.ni = (int)extent_ij[0], a.nj = (int)extent_ij[1], a.ns = (int)ns, a.nd = (int)nd;
-    a.tiles_i = (unsigned)tiles_i;
+    int64_t blocks = 0;
+    if (int rc = column_fields(REMAP_ENTRY, a, &blocks, dst, src, nfields, src_edges, dst_edges, extent_ij, ns, nd, elem_size, edge_elem_size,
+                               flags, launches))
+        return rc;
+    if (blocks == 0) return GT4MI_OK;  // an empty extent or a dry run
     int next = 0;
     while (next_pair_batch(a, dst, src, &next, nfields, elem_size)) {
         with_item_type(elem_size, [&](auto t) {

@@ -39,7 +39,7 @@ from typing import Any, List, NamedTuple, Optional, Sequence, Union
 import numpy as np
 
 from . import _lib
-from ._bound import FLOATS, Bound, _box_of, _halo4, _shape3, raise_refusal
+from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _box_of, _halo4, _shape3, refuse_host_arrays
 from .storage.device_array import DeviceArray, as_device_array
 
 
@@ -122,26 +122,19 @@ def merge(stats: Sequence[Stats]) -> Stats:
     return out
 
 
-def _native(fields, others, n: int, domain, itemsize: int, workspace, workspace_bytes: int, result, flags: int, stream,
-            entry: str = "gt4mi_field_stats"):
-    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
-    library's message.  Returns (workspace bytes needed, kernels enqueued)."""
-    needed, launches = ctypes.c_int64(0), ctypes.c_int(0)
-    rc = getattr(_lib.load(), entry)(fields, others, n, domain, itemsize, workspace, workspace_bytes, result, flags, stream,
-                                     ctypes.byref(needed), ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal(entry, rc)
-    return needed.value, launches.value
-
-
 class _StatsCall(Bound):
     """What :class:`FieldStats` and :class:`LevelStats` share: everything but the entry, the public function's name in the
     messages and the shape of a result block."""
 
-    _who = _entry = ""
+    _who = ""
+    _dry_run_bit = _lib.STATS_DRY_RUN
 
     def _result_block(self) -> tuple:
         raise NotImplementedError
+
+    def _arguments(self) -> tuple:  # (no workspace and no result until the first dry run has said how large they are)
+        return (self._fields, self._others, self._n, self._domain3, self._itemsize, self._workspace_ptr, self._workspace_bytes,
+                self._result_ptr, FLAGS, STREAM, Out(ctypes.c_int64), Out(ctypes.c_int))
 
     def __init__(self, fields: Sequence[Any], *, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
                  domain: Optional[Sequence[int]] = None, halo=0):
@@ -183,18 +176,24 @@ class _StatsCall(Bound):
                 self._others[n] = describe(o, True)
         self._domain3 = _lib.domain3(domain)
         # every check of the library, nothing enqueued; also: the workspace the call needs and how many kernels it makes
-        needed, self.launches = _native(self._fields, self._others, self._n, self._domain3, self._itemsize, None, 0, None,
-                                        _lib.STATS_DRY_RUN, None, self._entry)
-        self._bind(who, every, fields + [o for o in others if o is not None])
+        self._workspace_ptr, self._workspace_bytes, self._result_ptr = None, 0, None
+        needed, self.launches = self._dry_run()
+        refuse_host_arrays(who, every)  # (nothing is allocated for a call that cannot be bound)
         import torch
 
         self._workspace = torch.empty(needed // 8, dtype=torch.float64, device=first.tensor.device)
         self.result = DeviceArray(torch.zeros((self._n,) + self._result_block(), dtype=torch.float64, device=first.tensor.device))
-        self._workspace_bytes = needed
-        # the buffers against the fields (overlap, alignment): the dry run once more, now with them
-        _native(self._fields, self._others, self._n, self._domain3, self._itemsize, self._workspace.data_ptr(), needed,
-                self.result.ptr, _lib.STATS_DRY_RUN, None, self._entry)
+        self._workspace_ptr, self._workspace_bytes, self._result_ptr = self._workspace.data_ptr(), needed, self.result.ptr
+        self._dry_run()  # the buffers against the fields (overlap, alignment): the dry run once more, now with them
+        self._bind(who, every, fields + [o for o in others if o is not None])
         self._stream = None
+
+    def __call__(self) -> None:
+        self._check_alive()
+        self._stream = self._current_stream()  # (kept for get())
+        rc = self._native(*self._before, self._stream.cuda_stream, *self._after)
+        if rc != _lib.OK:
+            _lib.check(self._entry, rc)
 
 
 class FieldStats(_StatsCall):
@@ -212,15 +211,6 @@ class FieldStats(_StatsCall):
 
     def _result_block(self) -> tuple:
         return (_lib.STATS_SLOTS,)
-
-    def __call__(self) -> None:
-        self._check_alive()
-        self._stream = self._current_stream()
-        rc = self._lib.gt4mi_field_stats(self._fields, self._others, self._n, self._domain3, self._itemsize,
-                                         self._workspace.data_ptr(), self._workspace_bytes, self.result.ptr, 0,
-                                         self._stream.cuda_stream, None, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_field_stats", rc)
 
     def get(self) -> List[Stats]:
         """Synchronise the stream of the last call and return its results (``RuntimeError`` before the first call)."""
@@ -378,15 +368,6 @@ class LevelStats(_StatsCall):
     @property
     def nk(self) -> int:
         return self.domain[2]
-
-    def __call__(self) -> None:
-        self._check_alive()
-        self._stream = self._current_stream()
-        rc = self._lib.gt4mi_level_stats(self._fields, self._others, self._n, self._domain3, self._itemsize,
-                                         self._workspace.data_ptr(), self._workspace_bytes, self.result.ptr, 0,
-                                         self._stream.cuda_stream, None, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_level_stats", rc)
 
     def profile(self, name: str, entry: int = 0) -> DeviceArray:
         """The contiguous ``(nk,)`` device view of one row of ``result``: ``name`` is a field of :class:`Stats` or ``"mean"``.

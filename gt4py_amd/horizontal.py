@@ -53,22 +53,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._bound import FLOATS, Bound, _float_pairs, _origin3, _pair_lists, _triple, raise_refusal
+from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _common_domain, _float_pairs, _origin3, _pair_lists, _triple, field_table, raise_refusal
 from .storage.device_array import DeviceArray
 
 METHODS = {"nearest": _lib.INTERP_NEAREST, "linear": _lib.INTERP_LINEAR, "cubic": _lib.INTERP_CUBIC,
            "cubic_monotone": _lib.INTERP_CUBIC_MONOTONE}
-
-
-def _native(dst, src, n: int, pos_i, pos_j, extent, reach, size: int, pos_size: int, method: int, flags: int, stream: Optional[int]) -> int:
-    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
-    library's message.  Returns the kernels enqueued."""
-    launches = ctypes.c_int(0)
-    rc = _lib.load().gt4mi_horizontal_interp(dst, src, n, ctypes.byref(pos_i), ctypes.byref(pos_j), extent, reach, size, pos_size, method,
-                                             flags, stream, ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_horizontal_interp", rc)
-    return launches.value
 
 
 def _position_field(a: DeviceArray, origin) -> "_lib.Field":
@@ -86,42 +75,30 @@ class HorizontalInterp(Bound):
     a call enqueues.  The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it refuses to
     run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
 
+    _entry, _dry_run_bit = "gt4mi_horizontal_interp", _lib.INTERP_DRY_RUN
+
+    def _arguments(self) -> tuple:
+        return (self._dst, self._src, self._n, ctypes.byref(self._pos_i), ctypes.byref(self._pos_j), self._extent, self._reach, self._size,
+                self._pos_size, self._method, FLAGS, STREAM, Out(ctypes.c_int))
+
     def __init__(self, dst, src, *, pos_i, pos_j, method: str = "linear", relative: bool = False, halo=0,
                  origin: Optional[Sequence[int]] = None):
         dsts, srcs, d_arrays, s_arrays, p_arrays, self._halo = _float_pairs(
             "interpolate", dst, src, halo, method, METHODS, shared=(pos_i, pos_j), names=("pos_i", "pos_j"), ndims=(2, 3), kind="Field[IJ]",
             plural="position fields")
         self.method, self.relative = method, bool(relative)
-        lo_i, hi_i, lo_j, hi_j = self._halo
         self.origin = origin = _origin3(origin, self._halo)
-        # the common compute domain: what every array has left behind its origin and (in I and J) in front of its high ghost cells
-        rest = [tuple(s - o - h for s, o, h in zip(a.shape, origin, (hi_i, hi_j, 0))) for a in d_arrays + s_arrays + p_arrays]
-        domain = tuple(min(r[ax] for r in rest if len(r) > ax) for ax in range(3))
-        if min(domain) < 0:
-            raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in fields of shapes {[a.shape for a in d_arrays + s_arrays]}")
-        self.domain = domain
+        self.domain = domain = _common_domain(d_arrays + s_arrays + p_arrays, self._halo, origin, d_arrays + s_arrays)
         self._n = len(d_arrays)
-        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
-        for table, arrays in ((self._dst, d_arrays), (self._src, s_arrays)):
-            for n, a in enumerate(arrays):
-                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, origin)
+        self._dst, self._src = field_table(d_arrays, origin), field_table(s_arrays, origin)
         self._pos_i, self._pos_j = (_position_field(a, origin) for a in p_arrays)
         self._extent = _lib.domain3(domain)
         self._reach = (ctypes.c_int64 * 4)(*self._halo)
         self._size, self._pos_size, self._method = d_arrays[0].itemsize, p_arrays[0].itemsize, METHODS[method]
         self._flags = _lib.INTERP_RELATIVE if self.relative else 0
         # every check of the library, nothing enqueued; also: how many kernels
-        self.launches = _native(self._dst, self._src, self._n, self._pos_i, self._pos_j, self._extent, self._reach, self._size,
-                                self._pos_size, self._method, self._flags | _lib.INTERP_DRY_RUN, None)
+        self.launches, = self._dry_run()
         self._bind("interpolate", d_arrays + s_arrays + p_arrays, dsts + srcs + [pos_i, pos_j])
-
-    def __call__(self) -> None:
-        self._check_alive()
-        rc = self._lib.gt4mi_horizontal_interp(self._dst, self._src, self._n, ctypes.byref(self._pos_i), ctypes.byref(self._pos_j),
-                                               self._extent, self._reach, self._size, self._pos_size, self._method, self._flags,
-                                               self._current_stream().cuda_stream, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_horizontal_interp", rc)
 
 
 def interpolate(dst, src, *, pos_i, pos_j, method: str = "linear", relative: bool = False, halo=0,
@@ -180,15 +157,6 @@ def _edge_pair(edges, name: str):
     return out
 
 
-def _native_remap(dst, src, n: int, axis_i, axis_j, nk: int, size: int, method: int, flags: int, stream: Optional[int]) -> int:
-    launches = ctypes.c_int(0)
-    rc = _lib.load().gt4mi_horizontal_remap(dst, src, n, ctypes.byref(axis_i), ctypes.byref(axis_j), nk, size, method, flags, stream,
-                                            ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_horizontal_remap", rc)
-    return launches.value
-
-
 class HorizontalRemap(Bound):
     """The frozen form of :func:`remap_cells`: arguments are checked, the two overlap tables computed on the host
     (``gt4mi_overlap_table``) and copied to device arrays that the object OWNS, the library's dry run made and the native
@@ -197,6 +165,12 @@ class HorizontalRemap(Bound):
     ``src_extent`` / ``dst_extent`` are the (I, J) cells of the two grids, ``nk`` the levels, ``terms`` the table entries per axis,
     ``launches`` the kernels a call enqueues.  The object holds raw pointers and weak references to the CALLER's fields, not the
     arrays: it refuses to run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
+
+    _entry, _dry_run_bit = "gt4mi_horizontal_remap", _lib.HREMAP_DRY_RUN
+
+    def _arguments(self) -> tuple:
+        return (self._dst, self._src, self._n, ctypes.byref(self._axis_i), ctypes.byref(self._axis_j), self.nk, self._size, self._method,
+                FLAGS, STREAM, Out(ctypes.c_int))
 
     def __init__(self, dst, src, *, src_edges, dst_edges, method: str = "pcm", src_origin: Optional[Sequence[int]] = None,
                  dst_origin: Optional[Sequence[int]] = None):
@@ -243,22 +217,11 @@ class HorizontalRemap(Bound):
                                          *[real.data_ptr() + 8 * nnz * m for m in range(4)]))
         self._axis_i, self._axis_j = axes
         self._n = len(d_arrays)
-        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
-        for table, arrays, org in ((self._dst, d_arrays, d_origin), (self._src, s_arrays, s_origin)):
-            for n, a in enumerate(arrays):
-                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, org)
+        self._dst, self._src = field_table(d_arrays, d_origin), field_table(s_arrays, s_origin)
         self._size, self._method = d_arrays[0].itemsize, REMAP_METHODS[method]
         # every check of the library, nothing enqueued; also: how many kernels
-        self.launches = _native_remap(self._dst, self._src, self._n, self._axis_i, self._axis_j, self.nk, self._size, self._method,
-                                      _lib.HREMAP_DRY_RUN, None)
+        self.launches, = self._dry_run()
         self._bind("remap_cells", d_arrays + s_arrays, dsts + srcs)
-
-    def __call__(self) -> None:
-        self._check_alive()
-        rc = self._lib.gt4mi_horizontal_remap(self._dst, self._src, self._n, ctypes.byref(self._axis_i), ctypes.byref(self._axis_j), self.nk,
-                                              self._size, self._method, 0, self._current_stream().cuda_stream, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_horizontal_remap", rc)
 
 
 def remap_cells(dst, src, *, src_edges, dst_edges, method: str = "pcm", src_origin: Optional[Sequence[int]] = None,

@@ -32,24 +32,12 @@ import ctypes
 from typing import Optional, Sequence
 
 from . import _lib
-from ._bound import FLOATS, Bound, _origin3, _pair_lists, raise_refusal, refuse_host_arrays
+from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _common_domain, _origin3, _pair_lists, field_table, refuse_host_arrays
 from .storage.device_array import DeviceArray
 
 AXES = {"I": 0, "J": 1, "K": 2}
 PATHS = {_lib.LINE_PATH_LANES: "lanes", _lib.LINE_PATH_TILES: "tiles", _lib.LINE_PATH_ITEMS: "items"}
 COEFFICIENTS = ("lower", "diag", "upper")
-
-
-def _native(out, rhs, n: int, coefficients, extent, axis: int, size: int, flags: int, workspace, workspace_bytes: int, stream):
-    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
-    library's message.  Returns (workspace bytes needed, path, kernels enqueued)."""
-    needed, path, launches = ctypes.c_int64(0), ctypes.c_int(-1), ctypes.c_int(0)
-    lower, diag, upper = coefficients
-    rc = _lib.load().gt4mi_line_solve(out, rhs, n, ctypes.byref(lower), ctypes.byref(diag), ctypes.byref(upper), extent, axis, size, flags,
-                                      workspace, workspace_bytes, stream, ctypes.byref(needed), ctypes.byref(path), ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_line_solve", rc)
-    return needed.value, path.value, launches.value
 
 
 def _coefficient(a: DeviceArray, axis: int, start) -> "_lib.Field":
@@ -71,6 +59,13 @@ class LineSolve(Bound):
     anything else, slow), ``workspace`` the :class:`DeviceArray` that holds the elimination factors: its layout is the library's,
     and no result depends on what it held before a call.  The object holds raw pointers and weak references to the CALLER's
     objects, not the arrays: it refuses to run once one of them has died."""
+
+    _entry, _dry_run_bit = "gt4mi_line_solve", _lib.LINE_DRY_RUN
+
+    def _arguments(self) -> tuple:  # (no workspace until the first dry run has said how large it is)
+        lower, diag, upper = self._coefficients
+        return (self._out, self._rhs, self._n, ctypes.byref(lower), ctypes.byref(diag), ctypes.byref(upper), self._extent3, self._axis,
+                self._size, FLAGS, self._workspace_ptr, self._workspace_bytes, STREAM, Out(ctypes.c_int64), Out(ctypes.c_int), Out(ctypes.c_int))
 
     def __init__(self, out, rhs, *, lower, diag, upper, axis: str = "I", periodic: bool = False, halo=0,
                  origin: Optional[Sequence[int]] = None):
@@ -97,14 +92,11 @@ class LineSolve(Bound):
         # the common compute domain: what every IJK array has left behind its origin and in front of its high ghost cells; along
         # the line axis the arrays must agree, a line is never cut short silently
         full = [a for a in o_arrays + r_arrays + c_arrays if a.ndim == 3]
-        rest = [tuple(s - o - h for s, o, h in zip(a.shape, origin, (hi_i, hi_j, 0))) for a in full]
-        domain = tuple(min(r[x] for r in rest) for x in range(3))
-        if min(domain) < 0 or domain[2] < 1:
-            raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in fields of shapes {[a.shape for a in full]}")
-        for r in rest:
-            if r[ax] != domain[ax]:
-                raise ValueError(f"the fields of one call share their length along {axis}: {domain[ax]} and {r[ax]} differ")
-        self.domain = domain
+        self.domain = domain = _common_domain(full, self._halo, origin, full, least_k=1)
+        for a in full:
+            have = a.shape[ax] - origin[ax] - (hi_i, hi_j, 0)[ax]
+            if have != domain[ax]:
+                raise ValueError(f"the fields of one call share their length along {axis}: {domain[ax]} and {have} differ")
         #: the IJK box that is solved: the domain grown by the halo in I and J
         self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j, domain[2])
         #: the line length, and how many lines the box holds
@@ -115,17 +107,14 @@ class LineSolve(Bound):
                 raise ValueError(f"{name} has {a.shape[0]} items, a line of {self.n} points along {axis} needs {self.n}")
         start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
         self._n = len(o_arrays)
-        self._out, self._rhs = (_lib.Field * self._n)(), (_lib.Field * self._n)()
-        for table, arrays in ((self._out, o_arrays), (self._rhs, r_arrays)):
-            for n, a in enumerate(arrays):
-                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, start)
+        self._out, self._rhs = field_table(o_arrays, start), field_table(r_arrays, start)
         self._coefficients = tuple(_coefficient(a, ax, start) for a in c_arrays)
         self._extent3 = _lib.domain3(self.extent)
         self._axis, self._size = ax, o_arrays[0].itemsize
         self._flags = _lib.LINE_PERIODIC if self.periodic else 0
         # every check of the library, nothing enqueued; also: the workspace the call needs, its path and how many kernels it makes
-        needed, path, self.launches = _native(self._out, self._rhs, self._n, self._coefficients, self._extent3, ax, self._size,
-                                              self._flags | _lib.LINE_DRY_RUN, None, 0, None)
+        self._workspace_ptr, self._workspace_bytes = None, 0
+        needed, path, self.launches = self._dry_run()
         self.path = PATHS.get(path)
         arrays = o_arrays + r_arrays + c_arrays
         refuse_host_arrays("solve_lines", arrays)
@@ -134,19 +123,9 @@ class LineSolve(Bound):
         first = o_arrays[0].tensor
         #: the elimination factors of every line (and, for a periodic call, the closure's solution); private layout
         self.workspace = DeviceArray(torch.empty(max(needed // self._size, 1), dtype=first.dtype, device=first.device))
-        self._workspace_bytes = needed
-        _native(self._out, self._rhs, self._n, self._coefficients, self._extent3, ax, self._size, self._flags | _lib.LINE_DRY_RUN,
-                self.workspace.ptr, needed, None)  # (the workspace against every field)
+        self._workspace_ptr, self._workspace_bytes = self.workspace.ptr, needed
+        self._dry_run()  # (the workspace against every field)
         self._bind("solve_lines", arrays, outs + rhss + [lower, diag, upper])
-
-    def __call__(self) -> None:
-        self._check_alive()
-        lower, diag, upper = self._coefficients
-        rc = self._lib.gt4mi_line_solve(self._out, self._rhs, self._n, ctypes.byref(lower), ctypes.byref(diag), ctypes.byref(upper),
-                                        self._extent3, self._axis, self._size, self._flags, self.workspace.ptr, self._workspace_bytes,
-                                        self._current_stream().cuda_stream, None, None, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_line_solve", rc)
 
 
 def solve_lines(out, rhs, *, lower, diag, upper, axis: str = "I", periodic: bool = False, halo=0,

@@ -27,26 +27,23 @@ float64 -> float32 is one rounding to nearest even and float32 -> float64 is exa
 from __future__ import annotations
 
 import ctypes
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, List, Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from ._bound import FLOATS as _FLOATS, Bound, _as_list, _halo4, _origin3, _pair_lists, _shape3, _triple, raise_refusal, refuse_host_arrays
+from ._bound import (FLAGS, FLOATS as _FLOATS, STREAM, Bound, Out, _as_list, _halo4, _origin3, _pair_lists, _shape3, _triple, dry_run, field_table,
+                     refuse_host_arrays)
 from .storage.device_array import DeviceArray, as_device_array, torch_dtype
 
 PATH_ROWS, PATH_TILES, PATH_ITEMS = _lib.COPY_PATH_ROWS, _lib.COPY_PATH_TILES, _lib.COPY_PATH_ITEMS
 PATH_NAMES = {PATH_ROWS: "rows", PATH_TILES: "tiles", PATH_ITEMS: "items"}
 
 
-def _native(dst, src, n: int, extent, dsize: int, ssize: int, flags: int, stream: Optional[int]) -> Tuple[List[int], int]:
-    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
-    library's message.  Returns (path of every pair, kernels enqueued)."""
-    paths, launches = (ctypes.c_int * n)(), ctypes.c_int(0)
-    rc = _lib.load().gt4mi_field_copy(dst, src, n, extent, dsize, ssize, flags, stream, paths, ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_field_copy", rc)
-    return list(paths), launches.value
+def _copy_arguments(dst, src, n: int, extent, dsize: int, ssize: int) -> tuple:
+    """The argument list of ``gt4mi_field_copy``: of a :class:`FieldCopy`, and of the dry run a staged transfer makes before it has
+    anything to copy to."""
+    return dst, src, n, extent, dsize, ssize, FLAGS, STREAM, Out(ctypes.c_int * n), Out(ctypes.c_int)
 
 
 def _conversion(dst_dtype: np.dtype, src_dtype: np.dtype, convert: bool, who: str) -> int:
@@ -68,6 +65,11 @@ class FieldCopy(Bound):
     ``paths`` tells which path of the kernel every pair takes (``PATH_ROWS`` / ``PATH_TILES`` / ``PATH_ITEMS``), ``launches`` how
     many kernels a call enqueues.  The object holds raw pointers and weak references to the CALLER's objects, not the arrays:
     it refuses to run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
+
+    _entry, _dry_run_bit = "gt4mi_field_copy", _lib.COPY_DRY_RUN
+
+    def _arguments(self) -> tuple:
+        return _copy_arguments(self._dst, self._src, self._n, self._extent3, self._dsize, self._ssize)
 
     def __init__(self, dsts, srcs, *, halo=0, origin: Optional[Sequence[int]] = None, domain: Optional[Sequence[int]] = None,
                  convert: bool = False, dst_origin: Optional[Sequence[int]] = None, src_origin: Optional[Sequence[int]] = None):
@@ -98,23 +100,11 @@ class FieldCopy(Bound):
         #: the box that is copied: the domain grown by the halo in I and J
         self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j, domain[2])
         self._n = len(d_arrays)
-        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
-        for table, arrays, org in ((self._dst, d_arrays, d_origin), (self._src, s_arrays, s_origin)):
-            start = (org[0] - lo_i, org[1] - lo_j, org[2])
-            for n, a in enumerate(arrays):
-                table[n] = _lib.Field.make(a.ptr, _shape3(a), tuple(a.strides) + (0,) * (3 - a.ndim), start)
+        self._dst, self._src = (field_table(arrays, (org[0] - lo_i, org[1] - lo_j, org[2])) for arrays, org in ((d_arrays, d_origin), (s_arrays, s_origin)))
         self._extent3 = _lib.domain3(self.extent)
         # every check of the library, nothing enqueued; also: which paths, how many kernels
-        self.paths, self.launches = _native(self._dst, self._src, self._n, self._extent3, self._dsize, self._ssize,
-                                            self._flags | _lib.COPY_DRY_RUN, None)
+        self.paths, self.launches = self._dry_run()
         self._bind("copy_fields", d_arrays + s_arrays, dsts + srcs)
-
-    def __call__(self) -> None:
-        self._check_alive()
-        rc = self._lib.gt4mi_field_copy(self._dst, self._src, self._n, self._extent3, self._dsize, self._ssize, self._flags,
-                                        self._current_stream().cuda_stream, None, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_field_copy", rc)
 
 
 def copy_fields(dst, src, *, halo=0, origin: Optional[Sequence[int]] = None, domain: Optional[Sequence[int]] = None,
@@ -202,20 +192,18 @@ class _Staged:
     def _check_fields(self, arrays, halo4, origin, domain, box, download: bool) -> None:
         n = len(arrays)
         lo_i, _, lo_j, _ = halo4
-        fields, stage = (_lib.Field * n)(), (_lib.Field * n)()
+        stage = (_lib.Field * n)()
         size = self.dtype.itemsize
         strides = (box[1] * box[2] * size, box[2] * size, size)
         nbytes = box[0] * strides[0]
         top = max(a.ptr + sum(abs(s) * (m - 1) for s, m in zip(a.strides, a.shape)) + a.itemsize for a in arrays)
         base = -(-top // 4096) * 4096 + 4096  # (made-up addresses behind the last field: never dereferenced in a dry run)
-        for k, a in enumerate(arrays):
-            fields[k] = _lib.Field.make(a.ptr, _shape3(a), tuple(a.strides) + (0,) * (3 - a.ndim), (origin[0] - lo_i, origin[1] - lo_j, origin[2]))
+        fields = field_table(arrays, (origin[0] - lo_i, origin[1] - lo_j, origin[2]))
+        for k in range(n):
             stage[k] = _lib.Field.make(base + k * (-(-nbytes // 4096) * 4096), box, strides, (0, 0, 0))
-        flags = _lib.COPY_DRY_RUN | (_lib.COPY_CONVERT if self.dtype != self.field_dtype else 0)
-        if download:
-            _native(stage, fields, n, _lib.domain3(box), size, self.field_dtype.itemsize, flags, None)
-        else:
-            _native(fields, stage, n, _lib.domain3(box), self.field_dtype.itemsize, size, flags, None)
+        sides = (stage, fields, n, _lib.domain3(box), size, self.field_dtype.itemsize) if download else \
+                (fields, stage, n, _lib.domain3(box), self.field_dtype.itemsize, size)
+        dry_run(FieldCopy._entry, FieldCopy._dry_run_bit, _lib.COPY_CONVERT if self.dtype != self.field_dtype else 0, _copy_arguments(*sides))
 
     def _next_slot(self) -> int:
         """The slot whose turn it is, free to be overwritten: whatever was enqueued on it before has completed."""

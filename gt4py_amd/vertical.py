@@ -48,7 +48,7 @@ import ctypes
 from typing import Optional, Sequence
 
 from . import _lib
-from ._bound import Bound, _float_pairs, _origin3, raise_refusal
+from ._bound import FLAGS, STREAM, Bound, Out, _common_domain, _float_pairs, _origin3, field_table
 from .storage.device_array import DeviceArray
 
 METHODS = {"pcm": _lib.REMAP_PCM, "plm": _lib.REMAP_PLM}
@@ -57,25 +57,77 @@ INTERP_METHODS = {"nearest": _lib.VINTERP_NEAREST, "linear": _lib.VINTERP_LINEAR
 OUTSIDE = {"clamp": _lib.VINTERP_OUTSIDE_CLAMP, "linear": _lib.VINTERP_OUTSIDE_LINEAR, "fill": _lib.VINTERP_OUTSIDE_FILL}
 
 
-def _native(dst, src, n: int, src_edges, dst_edges, extent_ij, ns: int, nd: int, size: int, edge_size: int, method: int, flags: int,
-            stream: Optional[int]) -> int:
-    """The ctypes call; a refusal of the library becomes ``ValueError`` (``TypeError`` for what no kernel handles) with the
-    library's message.  Returns the kernels enqueued."""
-    launches = ctypes.c_int(0)
-    rc = _lib.load().gt4mi_vertical_remap(dst, src, n, ctypes.byref(src_edges), ctypes.byref(dst_edges), extent_ij, ns, nd, size,
-                                          edge_size, method, flags, stream, ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_vertical_remap", rc)
-    return launches.value
-
-
-def _edge_field(a: DeviceArray, start) -> "_lib.Field":
+def _shared_field(a: DeviceArray, start) -> "_lib.Field":
     if a.ndim == 1:  # Field[K]: every column reads the same items
         return _lib.Field.make(a.ptr, (1, 1, a.shape[0]), (0, 0, a.strides[0]), (0, 0, start[2]))
     return _lib.Field.make(a.ptr, a.shape, a.strides, start)
 
 
-class VerticalRemap(Bound):
+class _Columns(Bound):
+    """What :class:`VerticalRemap` and :class:`VerticalInterp` share: (dst, src) pairs of IJK fields and two shared fields along K,
+    one for the source levels and one for the target levels.  A subclass states its entry, its methods, what it calls itself and
+    its shared fields, how many more items than levels a shared field has, and its scalars behind ``method``."""
+
+    _who = ""
+    _methods: dict = {}
+    _names = ("", "")  # the shared fields: the keyword of the sources' one and of the targets' one
+    _plural = ""       # what the dtype message calls them
+    _surplus = 0       # items a shared field has along K beyond the levels: 1 for edges, 0 for coordinates
+
+    def _wrong_count(self, name: str, have: int, n: int, side: str) -> str:
+        """The message for a shared field ``name`` of ``have`` items along K where the ``side`` have ``n`` levels."""
+        raise NotImplementedError
+
+    def _scalars(self, **own) -> tuple:
+        """Checks the subclass's own keywords and returns the native arguments between ``method`` and the flags."""
+        return ()
+
+    def _arguments(self) -> tuple:
+        return (self._dst, self._src, self._n, *self._shared_refs, self._extent2, self.ns, self.nd, self._size, self._shared_size,
+                self._method, *self._own, FLAGS, STREAM, Out(ctypes.c_int))
+
+    def _columns(self, dst, src, shared, method: str, halo, origin, **own) -> None:
+        dsts, srcs, d_arrays, s_arrays, x_arrays, self._halo = _float_pairs(
+            self._who, dst, src, halo, method, self._methods, shared=shared, names=self._names, ndims=(1, 3), kind="Field[K]",
+            plural=self._plural)
+        self.method = method
+        self._own = self._scalars(**own)
+        lo_i, hi_i, lo_j, hi_j = self._halo
+        self.origin = origin = _origin3(origin, self._halo)
+        # levels: what every src / dst has behind the origin; a shared field has `_surplus` more
+        levels = []
+        for side, arrays, x, name in (("sources", s_arrays, x_arrays[0], self._names[0]), ("destinations", d_arrays, x_arrays[1], self._names[1])):
+            n = arrays[0].shape[2] - origin[2]
+            if n < 1:
+                raise ValueError(f"origin {origin} leaves no level in the {side} (shape {arrays[0].shape})")
+            for a in arrays:
+                if a.shape[2] - origin[2] != n:
+                    raise ValueError(f"the {side} of one call share their number of levels: {n} and {a.shape[2] - origin[2]} differ")
+            have = x.shape[-1] - origin[2]
+            if have != n + self._surplus:
+                raise ValueError(self._wrong_count(name, have, n, side))
+            levels.append(n)
+        self.ns, self.nd = levels
+        # the common IJ compute domain of the IJK arrays (a Field[K] has none)
+        self.domain = domain = _common_domain([a for a in d_arrays + s_arrays + x_arrays if a.ndim == 3], self._halo, origin,
+                                              d_arrays + s_arrays, axes=2)
+        #: the IJ box that is written: the domain grown by the halo
+        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j)
+        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
+        self._n = len(d_arrays)
+        self._dst, self._src = field_table(d_arrays, start), field_table(s_arrays, start)
+        fields = [_shared_field(a, start) for a in x_arrays]
+        for name, f in zip(self._names, fields):  # (the descriptors under the shared fields' names: `_src_edges`, `_dst_coord`, ...)
+            setattr(self, "_" + name, f)
+        self._shared_refs = tuple(ctypes.byref(f) for f in fields)
+        self._extent2 = (ctypes.c_int64 * 2)(*self.extent)
+        self._size, self._shared_size, self._method = d_arrays[0].itemsize, x_arrays[0].itemsize, self._methods[method]
+        # every check of the library, nothing enqueued; also: how many kernels
+        self.launches, = self._dry_run()
+        self._bind(self._who, d_arrays + s_arrays + x_arrays, dsts + srcs + list(shared))
+
+
+class VerticalRemap(_Columns):
     """The frozen form of :func:`remap_levels` (what ``FrozenStencil`` is for stencils): arguments are checked (through the
     library's dry run) and the native descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is
     current THEN.
@@ -84,56 +136,14 @@ class VerticalRemap(Bound):
     kernels a call enqueues.  The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it
     refuses to run once one of them has died.  (An exporter that cannot be weakly referenced is held instead.)"""
 
-    def __init__(self, dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0, origin: Optional[Sequence[int]] = None):
-        dsts, srcs, d_arrays, s_arrays, e_arrays, self._halo = _float_pairs(
-            "remap_levels", dst, src, halo, method, METHODS, shared=(src_edges, dst_edges), names=("src_edges", "dst_edges"), ndims=(1, 3),
-            kind="Field[K]", plural="edge fields")
-        self.method = method
-        lo_i, hi_i, lo_j, hi_j = self._halo
-        self.origin = origin = _origin3(origin, self._halo)
-        # levels: what every src / dst has behind the origin; an edge field has one more
-        levels = []
-        for side, arrays, edges, name in (("sources", s_arrays, e_arrays[0], "src_edges"), ("destinations", d_arrays, e_arrays[1], "dst_edges")):
-            n = arrays[0].shape[2] - origin[2]
-            if n < 1:
-                raise ValueError(f"origin {origin} leaves no level in the {side} (shape {arrays[0].shape})")
-            for a in arrays:
-                if a.shape[2] - origin[2] != n:
-                    raise ValueError(f"the {side} of one call share their number of levels: {n} and {a.shape[2] - origin[2]} differ")
-            have = edges.shape[-1] - origin[2]
-            if have != n + 1:
-                raise ValueError(f"{name} has {have} edges along K, {n} levels need {n + 1}")
-            levels.append(n)
-        self.ns, self.nd = levels
-        # the common IJ compute domain: what every IJK array has left behind its origin and in front of its high ghost cells
-        rest = [tuple(s - o - h for s, o, h in zip(a.shape[:2], origin[:2], (hi_i, hi_j))) for a in d_arrays + s_arrays + e_arrays if a.ndim == 3]
-        domain = tuple(min(r[ax] for r in rest) for ax in range(2))
-        if min(domain) < 0:
-            raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in fields of shapes {[a.shape for a in d_arrays + s_arrays]}")
-        self.domain = domain
-        #: the IJ box that is remapped: the domain grown by the halo
-        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j)
-        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
-        self._n = len(d_arrays)
-        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
-        for table, arrays in ((self._dst, d_arrays), (self._src, s_arrays)):
-            for n, a in enumerate(arrays):
-                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, start)
-        self._src_edges, self._dst_edges = (_edge_field(a, start) for a in e_arrays)
-        self._extent2 = (ctypes.c_int64 * 2)(*self.extent)
-        self._size, self._edge_size, self._method = d_arrays[0].itemsize, e_arrays[0].itemsize, METHODS[method]
-        # every check of the library, nothing enqueued; also: how many kernels
-        self.launches = _native(self._dst, self._src, self._n, self._src_edges, self._dst_edges, self._extent2, self.ns, self.nd,
-                                self._size, self._edge_size, self._method, _lib.REMAP_DRY_RUN, None)
-        self._bind("remap_levels", d_arrays + s_arrays + e_arrays, dsts + srcs + [src_edges, dst_edges])
+    _who, _entry, _dry_run_bit, _methods = "remap_levels", "gt4mi_vertical_remap", _lib.REMAP_DRY_RUN, METHODS
+    _names, _plural, _surplus = ("src_edges", "dst_edges"), "edge fields", 1
 
-    def __call__(self) -> None:
-        self._check_alive()
-        rc = self._lib.gt4mi_vertical_remap(self._dst, self._src, self._n, ctypes.byref(self._src_edges), ctypes.byref(self._dst_edges),
-                                            self._extent2, self.ns, self.nd, self._size, self._edge_size, self._method, 0,
-                                            self._current_stream().cuda_stream, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_vertical_remap", rc)
+    def _wrong_count(self, name: str, have: int, n: int, side: str) -> str:
+        return f"{name} has {have} edges along K, {n} levels need {n + 1}"
+
+    def __init__(self, dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0, origin: Optional[Sequence[int]] = None):
+        self._columns(dst, src, (src_edges, dst_edges), method, halo, origin)
 
 
 def remap_levels(dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0, origin: Optional[Sequence[int]] = None) -> None:
@@ -155,18 +165,7 @@ def remap_levels(dst, src, *, src_edges, dst_edges, method: str = "pcm", halo=0,
     VerticalRemap(dst, src, src_edges=src_edges, dst_edges=dst_edges, method=method, halo=halo, origin=origin)()
 
 
-def _native_interp(dst, src, n: int, src_coord, dst_coord, extent_ij, ns: int, nd: int, size: int, coord_size: int, method: int,
-                   outside: int, fill_value: float, flags: int, stream: Optional[int]) -> int:
-    """The ctypes call of ``gt4mi_vertical_interp``, refusals as in :func:`_native`.  Returns the kernels enqueued."""
-    launches = ctypes.c_int(0)
-    rc = _lib.load().gt4mi_vertical_interp(dst, src, n, ctypes.byref(src_coord), ctypes.byref(dst_coord), extent_ij, ns, nd, size,
-                                           coord_size, method, outside, fill_value, flags, stream, ctypes.byref(launches))
-    if rc != _lib.OK:
-        raise_refusal("gt4mi_vertical_interp", rc)
-    return launches.value
-
-
-class VerticalInterp(Bound):
+class VerticalInterp(_Columns):
     """The frozen form of :func:`interpolate_levels`: arguments are checked (through the library's dry run) and the native
     descriptors built once, ``__call__()`` makes only the ctypes call, on the stream that is current THEN.
 
@@ -175,62 +174,23 @@ class VerticalInterp(Bound):
     references to the CALLER's objects, not the arrays: it refuses to run once one of them has died.  (An exporter that cannot be
     weakly referenced is held instead.)"""
 
-    def __init__(self, dst, src, *, src_coord, dst_coord, method: str = "linear", outside: str = "clamp", fill_value: float = float("nan"),
-                 halo=0, origin: Optional[Sequence[int]] = None):
-        dsts, srcs, d_arrays, s_arrays, c_arrays, self._halo = _float_pairs(
-            "interpolate_levels", dst, src, halo, method, INTERP_METHODS, shared=(src_coord, dst_coord), names=("src_coord", "dst_coord"),
-            ndims=(1, 3), kind="Field[K]", plural="coordinate fields")
+    _who, _entry, _dry_run_bit, _methods = "interpolate_levels", "gt4mi_vertical_interp", _lib.VINTERP_DRY_RUN, INTERP_METHODS
+    _names, _plural, _surplus = ("src_coord", "dst_coord"), "coordinate fields", 0
+
+    def _wrong_count(self, name: str, have: int, n: int, side: str) -> str:
+        return f"{name} has {have} levels along K, the {side} have {n}"
+
+    def _scalars(self, outside, fill_value) -> tuple:
         if outside not in OUTSIDE:
             raise ValueError(f"outside must be one of {sorted(OUTSIDE)}, not {outside!r}")
         if isinstance(fill_value, bool) or not isinstance(fill_value, (int, float)):
             raise TypeError(f"fill_value must be a Python float, not {type(fill_value).__name__}")
-        self.method, self.outside, self.fill_value = method, outside, float(fill_value)
-        lo_i, hi_i, lo_j, hi_j = self._halo
-        self.origin = origin = _origin3(origin, self._halo)
-        # levels: what every src / dst has behind the origin; a coordinate field has as many
-        levels = []
-        for side, arrays, coord, name in (("sources", s_arrays, c_arrays[0], "src_coord"), ("destinations", d_arrays, c_arrays[1], "dst_coord")):
-            n = arrays[0].shape[2] - origin[2]
-            if n < 1:
-                raise ValueError(f"origin {origin} leaves no level in the {side} (shape {arrays[0].shape})")
-            for a in arrays:
-                if a.shape[2] - origin[2] != n:
-                    raise ValueError(f"the {side} of one call share their number of levels: {n} and {a.shape[2] - origin[2]} differ")
-            have = coord.shape[-1] - origin[2]
-            if have != n:
-                raise ValueError(f"{name} has {have} levels along K, the {side} have {n}")
-            levels.append(n)
-        self.ns, self.nd = levels
-        # the common IJ compute domain: what every IJK array has left behind its origin and in front of its high ghost cells
-        rest = [tuple(s - o - h for s, o, h in zip(a.shape[:2], origin[:2], (hi_i, hi_j))) for a in d_arrays + s_arrays + c_arrays if a.ndim == 3]
-        domain = tuple(min(r[ax] for r in rest) for ax in range(2))
-        if min(domain) < 0:
-            raise ValueError(f"halo {self._halo} and origin {origin} leave no domain in fields of shapes {[a.shape for a in d_arrays + s_arrays]}")
-        self.domain = domain
-        #: the IJ box that is interpolated: the domain grown by the halo
-        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j)
-        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
-        self._n = len(d_arrays)
-        self._dst, self._src = (_lib.Field * self._n)(), (_lib.Field * self._n)()
-        for table, arrays in ((self._dst, d_arrays), (self._src, s_arrays)):
-            for n, a in enumerate(arrays):
-                table[n] = _lib.Field.make(a.ptr, a.shape, a.strides, start)
-        self._src_coord, self._dst_coord = (_edge_field(a, start) for a in c_arrays)
-        self._extent2 = (ctypes.c_int64 * 2)(*self.extent)
-        self._size, self._coord_size = d_arrays[0].itemsize, c_arrays[0].itemsize
-        self._method, self._outside = INTERP_METHODS[method], OUTSIDE[outside]
-        # every check of the library, nothing enqueued; also: how many kernels
-        self.launches = _native_interp(self._dst, self._src, self._n, self._src_coord, self._dst_coord, self._extent2, self.ns, self.nd,
-                                       self._size, self._coord_size, self._method, self._outside, self.fill_value, _lib.VINTERP_DRY_RUN, None)
-        self._bind("interpolate_levels", d_arrays + s_arrays + c_arrays, dsts + srcs + [src_coord, dst_coord])
+        self.outside, self.fill_value = outside, float(fill_value)
+        return OUTSIDE[outside], self.fill_value
 
-    def __call__(self) -> None:
-        self._check_alive()
-        rc = self._lib.gt4mi_vertical_interp(self._dst, self._src, self._n, ctypes.byref(self._src_coord), ctypes.byref(self._dst_coord),
-                                             self._extent2, self.ns, self.nd, self._size, self._coord_size, self._method, self._outside,
-                                             self.fill_value, 0, self._current_stream().cuda_stream, None)
-        if rc != _lib.OK:
-            _lib.check("gt4mi_vertical_interp", rc)
+    def __init__(self, dst, src, *, src_coord, dst_coord, method: str = "linear", outside: str = "clamp", fill_value: float = float("nan"),
+                 halo=0, origin: Optional[Sequence[int]] = None):
+        self._columns(dst, src, (src_coord, dst_coord), method, halo, origin, outside=outside, fill_value=fill_value)
 
 
 def interpolate_levels(dst, src, *, src_coord, dst_coord, method: str = "linear", outside: str = "clamp", fill_value: float = float("nan"),
