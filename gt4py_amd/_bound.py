@@ -1,5 +1,5 @@
 """What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
-``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``linesolve.LineSolve``) share on the Python side: turning a refusal of the library into an
+``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``departure.DepartureInterp``, ``linesolve.LineSolve``) share on the Python side: turning a refusal of the library into an
 exception, normalising halo / origin / domain / field lists, the native field tables, the dry run, and binding a checked call to
 the caller's objects.
 
@@ -129,24 +129,27 @@ def _pair_lists(who: str, dst, src, halo, method=None, methods=None, shared=(), 
     return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4
 
 
-def _float_pairs(who: str, dst, src, halo, method, methods, *, shared, names: Sequence[str], ndims: Tuple[int, int], kind: str, plural: str):
-    """:func:`_pair_lists` for IJK fields of ONE float dtype and two shared fields ``names`` (of ``ndims`` dimensions: IJK or a
-    ``kind``) of one float dtype of their own; ``plural`` is what the last message calls them."""
+def _float_pairs(who: str, dst, src, halo, method, methods, *, shared, names: Sequence[str], ndims, kind: str, plural: str):
+    """:func:`_pair_lists` for IJK fields of ONE float dtype and the shared fields ``names`` (of ``ndims`` dimensions: IJK or a
+    ``kind``; one tuple for all of them or one tuple per field, ``(3,)`` for a field that must be IJK) of one float dtype of their
+    own; ``plural`` is what the last message calls them."""
     dsts, srcs, d_arrays, s_arrays, x_arrays, halo4 = _pair_lists(who, dst, src, halo, method, methods, shared)
     for a in d_arrays + s_arrays:
         if a.ndim != 3:
             raise ValueError(f"{who} takes IJK fields, not a field of {a.ndim} dimension(s)")
-    for name, a in zip(names, x_arrays):
-        if a.ndim not in ndims:
-            raise ValueError(f"{name} must be an IJK field or a {kind}, not a field of {a.ndim} dimension(s)")
+    per_field = ndims if isinstance(ndims[0], tuple) else (ndims,) * len(names)
+    for name, a, allowed in zip(names, x_arrays, per_field):
+        if a.ndim not in allowed:
+            raise ValueError(f"{name} must be an IJK field{f' or a {kind}' if len(allowed) > 1 else ''}, not a field of {a.ndim} dimension(s)")
     dtype = d_arrays[0].dtype
     for a in d_arrays + s_arrays:
         if a.dtype != dtype:
             raise TypeError(f"the fields of one call share a dtype: {dtype} and {a.dtype} differ")
     if dtype not in FLOATS:
         raise TypeError(f"{who} takes float32 or float64 fields, not {dtype}")
-    if x_arrays[0].dtype != x_arrays[1].dtype:
-        raise TypeError(f"{names[0]} and {names[1]} share a dtype: {x_arrays[0].dtype} and {x_arrays[1].dtype} differ")
+    for name, a in zip(names[1:], x_arrays[1:]):
+        if a.dtype != x_arrays[0].dtype:
+            raise TypeError(f"{names[0]} and {name} share a dtype: {x_arrays[0].dtype} and {a.dtype} differ")
     if x_arrays[0].dtype not in FLOATS:
         raise TypeError(f"{plural} are float32 or float64, not {x_arrays[0].dtype}")
     return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4

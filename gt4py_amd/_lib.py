@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_vertical_remap",
     "gt4mi_vertical_interp",
     "gt4mi_horizontal_interp",
+    "gt4mi_departure_interp",
     "gt4mi_overlap_table",
     "gt4mi_horizontal_remap",
     "gt4mi_line_solve",
@@ -118,7 +119,7 @@ REMAP_PCM, REMAP_PLM, REMAP_DRY_RUN = 0, 1, 256
 VINTERP_NEAREST, VINTERP_LINEAR, VINTERP_CUBIC, VINTERP_CUBIC_MONOTONE = 0, 1, 2, 3
 VINTERP_OUTSIDE_CLAMP, VINTERP_OUTSIDE_LINEAR, VINTERP_OUTSIDE_FILL = 0, 1, 2
 VINTERP_DRY_RUN = 256
-# gt4mi_horizontal_interp: methods, flags
+# gt4mi_horizontal_interp, gt4mi_departure_interp: methods, flags
 INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC, INTERP_CUBIC_MONOTONE = 0, 1, 2, 3
 INTERP_RELATIVE, INTERP_DRY_RUN = 1, 256
 # gt4mi_horizontal_remap: methods, flags
@@ -248,6 +249,8 @@ def _declare(lib: ctypes.CDLL) -> None:
                                           ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_horizontal_interp.restype = I
     lib.gt4mi_horizontal_interp.argtypes = [FP, FP, I, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_departure_interp.restype = I
+    lib.gt4mi_departure_interp.argtypes = [FP, FP, I, FP, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_overlap_table.restype = I
     lib.gt4mi_overlap_table.argtypes = [P, I, P, I, P, P, P, P, P, P, I, ctypes.POINTER(ctypes.c_int)]
     AP = ctypes.POINTER(OverlapAxis)

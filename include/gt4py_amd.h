@@ -427,6 +427,53 @@ int gt4mi_horizontal_interp(const gt4mi_field* dst, const gt4mi_field* src, int 
                             const gt4mi_field* pos_j, const int64_t extent[3], const int64_t reach[4], int elem_size,
                             int pos_elem_size, int method, int flags, void* stream, int* launches);
 
+/* ---- 3-d departure-point interpolation (NEW entry, additive: the ABI version stays 8; no reference counterpart -- GTScript takes
+ * compile-time horizontal offsets only, and gt4mi_horizontal_interp followed by gt4mi_vertical_interp is not this: the vertical entry
+ * reads the column at (i, j), not the one at the horizontal departure position) ---------------------------------------------------
+ * For every point (i, j, k) of the box [origin, origin + extent) of every dst[n] -- the compute domain -- writes the value of src[n] at
+ * the position (x_i, x_j, x_k) that pos_i / pos_j / pos_k hold for that point, for `nfields` pairs that share ONE triple of position
+ * fields, in ONE kernel launch per 8 pairs, on `stream`, without synchronisation or allocation.  `elem_size` (fields) and
+ * `pos_elem_size` (position fields) are 4 (float32) or 8 (float64) and need not match.  pos_i and pos_j may have byte stride 0 along K
+ * (a Field[IJ] shared by every level, exempt from the shape check on that axis); pos_k is a full IJK box.
+ * All three positions are in index units of the compute domain: 0.0 is domain point 0 along I and J and level 0 along K.  With
+ * GT4MI_INTERP_RELATIVE they are displacements on each of the three axes: x = double(own index) + p.  The readable box of a src is the
+ * domain grown by `reach` = {lo_i, hi_i, lo_j, hi_j} ghost cells along I and J, over all levels 0 ... extent[2] - 1: K has no ghost levels.
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/departure_interp.hip.h states it again, tests/departure_interp_ref.py restates it in
+ * plain Python).  All of it is float64, one IEEE rounding per operation, no FMA; float32 items and positions are widened exactly on load
+ * and the result is rounded once on store.
+ *   Axes I and J   steps 1-4 of gt4mi_horizontal_interp unchanged: clamp to [-lo, n - 1 + hi], floor, t, every index clamped on its own.
+ *   Axis K         the same four steps with lo = hi = 0: x_k is clamped to [0, nk - 1], b_k = floor(x_k) (0 for a NaN), t_k = x_k - b_k.
+ *   Plane value    for a level kk, P(kk) is exactly gt4mi_horizontal_interp's `out` for that level before any limiter: the rows are
+ *                  combined along I, then the same expression is applied along J.
+ *   GT4MI_INTERP_NEAREST         the level index is floor(x_k + 0.5), clamped; the bit pattern of the item at the three nearest indices is
+ *                                moved (a NaN payload survives); a NaN in any of the three positions stores the canonical quiet NaN
+ *   GT4MI_INTERP_LINEAR          levels b_k and b_k + 1, each clamped; out = w0k*P(b_k) + w1k*P(b_k+1) with w0k = 1 - t_k, w1k = t_k
+ *   GT4MI_INTERP_CUBIC           the rule of gt4mi_vertical_interp, not edge replication in K: where 1 <= b_k <= nk-3,
+ *                                out = ((w_-1*P(b_k-1) + w_0*P(b_k)) + w_1*P(b_k+1)) + w_2*P(b_k+2) with the Lagrange weights of t_k (those
+ *                                of gt4mi_horizontal_interp); otherwise (b_k < 1 or b_k > nk-3: the end intervals, and every interval
+ *                                when nk < 4) the linear formula along K over the two CUBIC plane values P(b_k) and P(b_k+1), and only
+ *                                those two planes are loaded.  nk = 1, 2 and 3 need no special case.
+ *   GT4MI_INTERP_CUBIC_MONOTONE  the cubic out, then out = mn if out < mn else (mx if out > mx else out), at every point (the end
+ *                                intervals of K included), with mn = min(min(min(c000, c100), min(c010, c110)), min(min(c001, c101),
+ *                                min(c011, c111))) over the eight corner items at the clamped indices b, b+1 of the three axes, index
+ *                                order (i, j, k), mx folded the same way; min(a, b) = b if b < a else a, max(a, b) = b if b > a else a;
+ *                                a NaN out stays NaN
+ * Consequences: a weight of zero still multiplies (0 * inf = NaN at an integer position next to an infinity); -0.0 may come back as
+ * +0.0; a NaN position makes every field of that point NaN and touches nothing else; no address depends on data beyond the clamped
+ * integers; the bits of a point do not depend on layout, strides, alignment, position in the call, number of fields in the call, or
+ * Field[IJ] versus IJK position fields holding the same items.  Periodic wrap is not part of the kernel: fill the ghost cells with
+ * gt4mi_halo_fill first.  A physical vertical coordinate is not either: convert it to a fractional level first.
+ * Refusals: null pointers, nfields < 1, an unknown method or flag, a negative reach (GT4MI_ERR_INVALID_ARGUMENT); an item size other
+ * than 4 or 8, a misaligned field (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS); the bytes of a
+ * dst box (first to last item) meeting those of any src readable box, of a position field or of another dst box (GT4MI_ERR_UNSUPPORTED);
+ * a dst stride of 0 on an extent above 1 (GT4MI_ERR_INVALID_ARGUMENT).  No byte outside the dst boxes changes.  An extent with a zero
+ * entry is GT4MI_OK, nothing enqueued.  Every check runs before the first launch; a refused call enqueues nothing.  With
+ * GT4MI_INTERP_DRY_RUN the checks run, *launches is set and no device is touched.  *launches (may be NULL) = the kernels the call
+ * enqueues: ceil(nfields / 8).  Methods and flags are those of gt4mi_horizontal_interp. */
+int gt4mi_departure_interp(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* pos_i,
+                           const gt4mi_field* pos_j, const gt4mi_field* pos_k, const int64_t extent[3], const int64_t reach[4],
+                           int elem_size, int pos_elem_size, int method, int flags, void* stream, int* launches);
+
 /* ---- conservative horizontal remapping between rectilinear grids (NEW entries, additive: the ABI version stays 8; no reference
  * counterpart -- a GTScript destination point (i, j) reads sources at compile-time constant offsets from (i, j) only: not 2*i, not a
  * run-time range of source cells, not a source field of another horizontal shape) ---------------------------------------------------
