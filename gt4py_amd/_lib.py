@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_halo_fill",
     "gt4mi_field_stats",
     "gt4mi_level_stats",
+    "gt4mi_line_stats",
     "gt4mi_field_copy",
     "gt4mi_vertical_remap",
     "gt4mi_vertical_interp",
@@ -110,6 +111,9 @@ STATS_COUNT, STATS_NONFINITE, STATS_SUM, STATS_SUM_ABS, STATS_SUM_SQ, STATS_MIN,
 STATS_DRY_RUN = 1
 # gt4mi_level_stats: the row after the eight slots, rows of a result block, tiles per level at most (part of the bit contract)
 LEVEL_STATS_MEAN, LEVEL_STATS_ROWS, LEVEL_STATS_MAX_TILES = 8, 9, 32
+# gt4mi_line_stats: the row after the eight slots, rows of a result block, items of a segment (part of the bit contract), paths
+LINE_STATS_MEAN, LINE_STATS_ROWS, LINE_STATS_SEGMENT = 8, 9, 256
+LINE_STATS_PATH_LANES, LINE_STATS_PATH_TILES, LINE_STATS_PATH_ITEMS = 0, 1, 2
 # gt4mi_field_copy: paths, flags
 COPY_PATH_ROWS, COPY_PATH_TILES, COPY_PATH_ITEMS = 0, 1, 2
 COPY_CONVERT, COPY_DRY_RUN = 1, 256
@@ -240,6 +244,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         f = getattr(lib, name)
         f.restype = I
         f.argtypes = [FP, FP, I, DOM, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_line_stats.restype = I
+    lib.gt4mi_line_stats.argtypes = [FP, FP, I, DOM, I, I, P, ctypes.c_int64, P, I, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_field_copy.restype = I
     lib.gt4mi_field_copy.argtypes = [FP, FP, I, DOM, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_vertical_remap.restype = I

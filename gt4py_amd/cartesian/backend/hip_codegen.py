@@ -408,7 +408,9 @@ class _Emitter:
                 if hit is not None:
                     return hit
             if self.vec_rows is not None and "I" in self.axes.get(name, ("I", "J", "K")):
-                return self.vec_rows[(name, e.offset[1] + self.vec_row, e.offset[2])][self.vec_component + e.offset[0]]
+                # (a field without J -- Field[IK] -- has ONE row for all the J rows of the lane's strip)
+                row = self.vec_row if "J" in self.axes.get(name, ("I", "J", "K")) else 0
+                return self.vec_rows[(name, e.offset[1] + row, e.offset[2])][self.vec_component + e.offset[0]]
             if (name, e.offset[2]) in reg and e.offset[:2] == (0, 0) and e.koffset is None:
                 return reg[(name, e.offset[2])]
         if name in self.plan.register_only:

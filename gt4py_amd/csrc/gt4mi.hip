@@ -13,6 +13,7 @@
 #include "halo_fill.hip.h"
 #include "field_stats.hip.h"
 #include "level_stats.hip.h"
+#include "line_stats.hip.h"
 #include "field_copy.hip.h"
 #include "vertical_remap.hip.h"
 #include "vertical_interp.hip.h"
@@ -215,6 +216,13 @@ int gt4mi_level_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
                       int* launches) {
     return gt4mi::level_stats(fields, others, nfields, domain, elem_size, workspace, workspace_bytes, result, flags,
                               static_cast<hipStream_t>(stream), workspace_needed, launches);
+}
+
+int gt4mi_line_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int axis, int elem_size,
+                     void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream, int64_t* workspace_needed,
+                     int* launches, int* path) {
+    return gt4mi::line_stats(fields, others, nfields, domain, axis, elem_size, workspace, workspace_bytes, result, flags,
+                             static_cast<hipStream_t>(stream), workspace_needed, launches, path);
 }
 
 int gt4mi_field_copy(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const int64_t extent[3], int dst_elem_size,

@@ -401,3 +401,192 @@ def level_stats(*fields, other: Union[None, Any, Sequence[Any]] = None, origin: 
     frozen = LevelStats(fields, others=others, origin=origin, domain=domain, halo=halo)
     frozen()
     return frozen.get()
+
+
+# ---- along a line: zonal means and their kin ------------------------------------------------------------------------------------
+#: the rows of a LineStats result block, in order: those of a LevelStats block
+LINE_ROWS = PROFILE_ROWS
+_AXES = {"I": 0, "J": 1, "K": 2}
+
+
+def _axis_index(axis) -> int:
+    """``"I"``, ``"J"``, ``"K"`` or 0, 1, 2 as 0, 1, 2."""
+    if isinstance(axis, str) and axis.upper() in _AXES:
+        return _AXES[axis.upper()]
+    if not isinstance(axis, bool) and isinstance(axis, (int, np.integer)) and 0 <= int(axis) <= 2:
+        return int(axis)
+    raise ValueError(f"axis must be 'I', 'J', 'K' or 0, 1, 2, not {axis!r}")
+
+
+def _np_minimum(a, b):
+    """IEEE-754-2019 minimum, element-wise: NaN if either is NaN, -0 below +0."""
+    return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a < b, a, np.where(b < a, b, np.where(np.signbit(a), a, b))))
+
+
+def _np_maximum(a, b):
+    return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a > b, a, np.where(b > a, b, np.where(np.signbit(a), b, a))))
+
+
+class Lines:
+    """The per-line values of one entry: numpy arrays of shape ``(nA, nB)`` -- A < B the two axes other than the line axis, so
+    ``[j, k]`` for lines along I -- for ``count``, ``nonfinite`` (int64), ``sum``, ``sum_abs``, ``sum_sq``, ``min``, ``max``,
+    ``dot`` and ``mean`` (float64), with the NaN and signed-zero rules of :class:`Stats` line by line.  ``lines[a, b]`` is the
+    :class:`Stats` of one line; index 0 is the first line of the domain."""
+
+    __slots__ = LINE_ROWS
+
+    def __init__(self, count, nonfinite, sum, sum_abs, sum_sq, min, max, dot, mean=None):  # noqa: A002 - the names of Stats
+        self.count, self.nonfinite = (np.array(v, dtype=np.int64, ndmin=2) for v in (count, nonfinite))
+        self.sum, self.sum_abs, self.sum_sq, self.min, self.max, self.dot = (
+            np.array(v, dtype=np.float64, ndmin=2) for v in (sum, sum_abs, sum_sq, min, max, dot))
+        if mean is None:
+            with np.errstate(all="ignore"):
+                mean = self.sum / self.count  # one IEEE division per line, as the kernel's
+        self.mean = np.array(mean, dtype=np.float64, ndmin=2)
+        if any(getattr(self, name).shape != self.count.shape or self.count.ndim != 2 for name in LINE_ROWS):
+            raise ValueError("the rows of a Lines record are two-dimensional and of one shape")
+
+    @classmethod
+    def from_rows(cls, rows) -> "Lines":
+        """From one ``(9, nB, nA)`` block of a :class:`LineStats` result."""
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 3 or rows.shape[0] != _lib.LINE_STATS_ROWS:
+            raise ValueError(f"a result block has shape (9, nB, nA), not {rows.shape}")
+        rows = rows.transpose(0, 2, 1)
+        return cls(*rows[:_lib.STATS_SLOTS], mean=rows[_lib.LINE_STATS_MEAN])
+
+    @property
+    def shape(self) -> tuple:
+        return self.count.shape
+
+    def __getitem__(self, index) -> Stats:
+        a, b = (int(i) for i in index)
+        return Stats(int(self.count[a, b]), int(self.nonfinite[a, b]), float(self.sum[a, b]), float(self.sum_abs[a, b]),
+                     float(self.sum_sq[a, b]), float(self.min[a, b]), float(self.max[a, b]), float(self.dot[a, b]))
+
+    @property
+    def norm2(self) -> np.ndarray:
+        with np.errstate(all="ignore"):
+            return np.sqrt(self.sum_sq)
+
+    @property
+    def max_abs(self) -> np.ndarray:
+        """max |x| per line (the CFL limit along a line); NaN where the line holds a NaN."""
+        return np.maximum(np.abs(self.min), np.abs(self.max))  # (numpy's maximum hands a NaN on)
+
+    @property
+    def all_finite(self) -> np.ndarray:
+        return self.nonfinite == 0
+
+    @property
+    def first_nonfinite(self) -> Optional[tuple]:
+        """``(a, b)`` of the first line with a NaN or +-Inf item -- lowest ``b``, then lowest ``a`` -- or ``None``."""
+        bad = np.flatnonzero(self.nonfinite.T)
+        return None if not bad.size else (int(bad[0] % self.shape[0]), int(bad[0] // self.shape[0]))
+
+    def __eq__(self, other) -> bool:
+        """Bit for bit, NaN equal to NaN."""
+        if not isinstance(other, Lines):
+            return NotImplemented
+        return all(np.array_equal(getattr(self, n), getattr(other, n), equal_nan=True)
+                   and np.array_equal(np.signbit(getattr(self, n)), np.signbit(getattr(other, n))) for n in LINE_ROWS)
+
+    __hash__ = None  # type: ignore[assignment]
+
+    def __repr__(self) -> str:
+        return f"Lines(shape={self.shape}, first_nonfinite={self.first_nonfinite})"
+
+
+def merge_lines(parts: Sequence[Lines]) -> Lines:
+    """Join the per-rank results of ranks that split the LINE axis (ranks along I for zonal statistics) on the host, line by line,
+    IN THE ORDER GIVEN; all parts have the same shape (``ValueError`` otherwise).  As with :func:`merge_profiles`: counts add
+    exactly, ``min`` / ``max`` are joined exactly (NaN if any is NaN, -0 below +0), the sums are added left to right in float64 --
+    reproducible for a fixed process grid and rank order, NOT bit for bit what one undecomposed call gives.  ``mean`` is recomputed
+    from the joined ``sum`` and ``count``.  Ranks that split another axis hold different lines: concatenate their arrays instead.
+    No collective is made here; gather first, in rank order."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_lines needs at least one Lines")
+    for p in parts:
+        if not isinstance(p, Lines):
+            raise TypeError(f"merge_lines joins Lines records, not {type(p).__name__}")
+        if p.shape != parts[0].shape:
+            raise ValueError(f"the parts of a decomposed run share their lines: shapes {parts[0].shape} and {p.shape} differ")
+    out = {name: getattr(parts[0], name) for name in Stats._fields}
+    with np.errstate(all="ignore"):
+        for p in parts[1:]:
+            for name in Stats._fields:
+                join = _np_minimum if name == "min" else _np_maximum if name == "max" else np.add
+                out[name] = join(out[name], getattr(p, name))
+    return Lines(**out)
+
+
+class LineStats(_StatsCall):
+    """The frozen form of :func:`line_stats`, with the arguments and defaults of :class:`FieldStats` and ``axis``: ``"I"`` (the
+    zonal statistics), ``"J"``, ``"K"`` or 0, 1, 2 -- the axis ALONG which every line of the domain is reduced.  Arguments are
+    checked (through the library's dry run), the descriptors, the workspace and the result buffer built ONCE; ``__call__()`` makes
+    only the ctypes call, on the stream that is current THEN, and does not synchronise; :meth:`get` synchronises that stream and
+    returns one :class:`Lines` per entry.
+
+    ``result`` is a float64 :class:`DeviceArray` of shape ``(n, 9, nB, nA)`` (rows in the order of :data:`LINE_ROWS`; A < B the two
+    other axes); :meth:`section` hands out one row of it as an ``(nA, nB)`` view, which a stencil takes as ``Field[JK]`` (axis
+    I), ``Field[IK]`` (axis J) or ``Field[IJ]`` (axis K) of float64 in the same stream with no synchronisation in between.  Every
+    call overwrites it.  ``path`` is the kernel the strides selected (``_lib.LINE_STATS_PATH_*``); it never changes the result.
+
+    The order of the additions of a line depends on its length alone (csrc/line_stats.hip.h): the same line gives the same bits
+    whatever the axis, the layout or the other lines are.  The object holds raw pointers and weak references to the CALLER's
+    objects, as :class:`FieldStats` does: it refuses to run once one of them has died."""
+
+    _who, _entry = "line_stats", "gt4mi_line_stats"
+
+    def __init__(self, fields: Sequence[Any], *, axis, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
+                 domain: Optional[Sequence[int]] = None, halo=0):
+        self.axis, self.path = _axis_index(axis), None
+        super().__init__(fields, others=others, origin=origin, domain=domain, halo=halo)
+
+    def _arguments(self) -> tuple:
+        return (self._fields, self._others, self._n, self._domain3, self.axis, self._itemsize, self._workspace_ptr, self._workspace_bytes,
+                self._result_ptr, FLAGS, STREAM, Out(ctypes.c_int64), Out(ctypes.c_int), Out(ctypes.c_int))
+
+    def _dry_run(self) -> list:
+        needed, launches, self.path = super()._dry_run()
+        return [needed, launches]
+
+    def _result_block(self) -> tuple:
+        a, b = (d for d in range(3) if d != self.axis)
+        return (_lib.LINE_STATS_ROWS, self.domain[b], self.domain[a])
+
+    def section(self, name: str, entry: int = 0) -> DeviceArray:
+        """The ``(nA, nB)`` device view (byte strides ``(8, 8 * nA)``, no copy) of one row of ``result``: ``name`` is a field of
+        :class:`Stats` or ``"mean"``.  It holds what the LAST call left there, in stream order: pass it to a stencil as
+        ``Field[JK, np.float64]`` (axis I), ``Field[IK, ...]`` (axis J) or ``Field[IJ, ...]`` (axis K) on the stream of that call
+        and no synchronisation is needed."""
+        if name not in LINE_ROWS:
+            raise ValueError(f"no section {name!r}: the rows are {', '.join(LINE_ROWS)}")
+        entry = int(entry)
+        if not 0 <= entry < self._n:
+            raise IndexError(f"entry {entry} of {self._n}")
+        return self.result[entry, LINE_ROWS.index(name)].transpose()
+
+    def get(self) -> List[Lines]:
+        """Synchronise the stream of the last call and return its results (``RuntimeError`` before the first call)."""
+        if self._stream is None:
+            raise RuntimeError("LineStats.get: the object has not been called yet")
+        self._stream.synchronize()
+        return [Lines.from_rows(block) for block in self.result.tensor.cpu().numpy()]
+
+
+def line_stats(*fields, axis, other: Union[None, Any, Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
+               domain: Optional[Sequence[int]] = None, halo=0) -> List[Lines]:
+    """Statistics of ``fields`` along every line of their compute domain along ``axis``, one :class:`Lines` each: the synchronous
+    one-shot form, with the arguments of :func:`field_stats`.  One pass (per 8 fields) and, for lines of more than one segment,
+    one finishing launch on the current stream, then a synchronisation of that stream.  With an IJ area weight as ``other``,
+    ``dot`` is the area-weighted sum along the line.  In a time loop build a :class:`LineStats` once instead and read it a step
+    late."""
+    if isinstance(other, (list, tuple)):
+        others = list(other)
+    else:
+        others = None if other is None else [other] * len(fields)
+    frozen = LineStats(fields, axis=axis, others=others, origin=origin, domain=domain, halo=halo)
+    frozen()
+    return frozen.get()

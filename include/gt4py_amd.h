@@ -249,6 +249,45 @@ int gt4mi_level_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
                       void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream,
                       int64_t* workspace_needed, int* launches);
 
+/* ---- statistics along the lines of I, J or K (NEW entry, additive: the ABI version stays 8; no reference counterpart -- GTScript has no
+ * reduction over I or J, gt4py leaves `field.sum(axis=0)` to numpy / cupy on its numpy / cupy storages) ------------------------------
+ * gt4mi_field_stats for EVERY LINE of the domain along `axis` (0: I, the zonal mean; 1: J; 2: K) at once: the eight GT4MI_STATS_* slots
+ * over the n = domain[axis] items of the line, with their meaning, NaN rules and signed-zero rules, plus the mean.  One pass over the
+ * field (8 entries per launch) plus, where a line has more than one segment, ONE finishing launch, on `stream`, without
+ * synchronisation or allocation.  Entries (a second field, which may be a broadcast weight such as an IJ cell area), flags and the
+ * checks of fields, workspace and result are those of gt4mi_field_stats.
+ *   workspace   *workspace_needed = nfields * lines * S * 8 * 8 bytes (lines = the product of the two other extents, S below)
+ *   result      result[((entry * 9 + row) * nB + b) * nA + a] (device memory, float64; nfields * 9 * lines * 8 bytes), A < B the two
+ *               remaining axes in I, J, K order: rows 0-7 are the slots, row GT4MI_LINE_STATS_MEAN = SUM / COUNT (one IEEE division).
+ *               Every (entry, row) is one contiguous section that a later kernel on the same stream can read as a JK (axis I), IK
+ *               (axis J) or IJ (axis K) field with strides (8, 8 * nA) bytes.
+ * THE ORDER OF THE ADDITIONS OF A LINE IS PART OF THE CONTRACT: it is a function of n alone (csrc/line_stats.hip.h states it,
+ * tests/line_stats_ref.py restates it in plain Python and in numpy) -- not of the axis, the layout, the path, pointers, strides, the
+ * number of entries in the call, the grid or anything about the device:
+ *   segments  G = GT4MI_LINE_STATS_SEGMENT items, S = ceil(n / G); segment s is the items m in [s G, min(n, (s + 1) G))
+ *   inside    four accumulator sets, set p takes the items with m mod 4 == p in increasing m (sums from +0.0, min from +inf, max from
+ *             -inf, counts from 0); a set whose sum |x| ended NaN sets min = max = NaN; the segment is (A0 (+) A1) (+) (A2 (+) A3),
+ *             all four sets taking part, also one that owned no item
+ *   across    the S segment values are halved level by level, new[i] = old[2i] (+) old[2i + 1], an odd last one carried up
+ * The same line gives the same bits, always; they are NOT the bits gt4mi_field_stats gives for that line as a domain of its own.
+ * *path (may be NULL) = which kernel the strides of the call select: GT4MI_LINE_STATS_PATH_LANES (an axis other than `axis` has unit
+ * stride in every field, 0 allowed in a second field: lanes along it, every step a coalesced row), GT4MI_LINE_STATS_PATH_TILES (`axis`
+ * itself has unit stride in every field: tiles of 64 lines x 128 bytes go through LDS), GT4MI_LINE_STATS_PATH_ITEMS (anything else:
+ * item by item, uncoalesced).  The path changes how the items reach the registers, never the result.
+ * Refused before anything is enqueued (GT4MI_ERR_INVALID_ARGUMENT unless noted): `fields` or `domain` NULL, nfields < 1, more than
+ * 65535 fields (UNSUPPORTED), an axis other than 0, 1 or 2, an empty domain, an item size other than 4 or 8 (UNSUPPORTED), unknown flag
+ * bits, what gt4mi_field_stats refuses of a field, the workspace or the result (NULL outside a dry run, too small, not aligned to 8
+ * bytes, overlapping a field or one another), and more than 2^30 (line, segment) pairs (UNSUPPORTED).
+ * *launches (may be NULL) = the kernels the call enqueues: ceil(nfields / 8), plus 1 where S > 1. */
+#ifndef GT4MI_LINE_STATS_SEGMENT
+#define GT4MI_LINE_STATS_SEGMENT 256 /* G: part of the bit contract; a build-time define only so that it could be measured */
+#endif
+enum { GT4MI_LINE_STATS_MEAN = 8, GT4MI_LINE_STATS_ROWS = 9 };
+enum { GT4MI_LINE_STATS_PATH_LANES = 0, GT4MI_LINE_STATS_PATH_TILES = 1, GT4MI_LINE_STATS_PATH_ITEMS = 2 };
+int gt4mi_line_stats(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int axis, int elem_size,
+                     void* workspace, int64_t workspace_bytes, double* result, int flags, void* stream, int64_t* workspace_needed,
+                     int* launches, int* path);
+
 /* ---- layout-converting field copy (NEW entry, additive: the ABI version stays 8.  Replaces what the reference does with numpy /
  * cupy slicing on its numpy / cupy storages and with `cp.asarray` (storage/cartesian/utils.py:187-189): moving a field between two
  * layouts, a storage and a dense buffer in numpy's C order among them) ------------------------------------------------------------
