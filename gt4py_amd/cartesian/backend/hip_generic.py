@@ -89,6 +89,7 @@ class _Variant:
         self.vec_functions: List[Any] = []  # the 16-byte-lane twin of a stage kernel, or None
         self.shared_functions: List[Any] = []  # ... and its form with temporaries shared between lanes (`_vecs`), or None
         self.tc_functions: List[Any] = []  # per kernel: the top-of-column-cache twins of a two-sweep column kernel
+        self.tc_levels: List[List[int]] = []  # ... and the register levels of each (the <n> of `_tc<n>`), in the same order
         for kern in program.kernels:
             fn = ctypes.c_void_p()
             _lib.check("gt4mi_module_function",
@@ -107,6 +108,7 @@ class _Variant:
                            lib.gt4mi_module_function(module, (kern.name + "_vecs").encode(), ctypes.byref(sfn)))
             self.shared_functions.append(sfn)
             tfns = []  # [(function, smallest domain K)], deepest cache first
+            kept = []
             if kern.top_cache is not None and no_alias:  # emitted under GT4MI_NO_ALIAS only
                 for n_reg, _, min_k in kern.top_cache:
                     tfn = ctypes.c_void_p()
@@ -116,7 +118,9 @@ class _Variant:
                     _lib.check("gt4mi_function_info", lib.gt4mi_function_info(tfn, None, ctypes.byref(scratch), None))
                     if scratch.value == 0:  # else the register levels did not fit: spills cost more than the cache saves
                         tfns.append((tfn, int(min_k)))
+                        kept.append(int(n_reg))
             self.tc_functions.append(tfns)
+            self.tc_levels.append(kept)
 
 
 #: scratch buffers (and the launch plans that point into them) are kept for this many HIP streams per stencil
@@ -224,6 +228,69 @@ def _check_aliases(plan, names: List[str], spans: List[Tuple[int, int]], views, 
                                  + ": the reference evaluates each right-hand side before it assigns, which kernels that "
                                    "read and write concurrently cannot reproduce -- pass separate arrays")
     return not involved
+
+
+def scratch_layout(plan, domain):
+    """({temporary: (byte offset, ni, nj, itemsize, oi, oj)}, bytes) of the scratch buffer of a plan on a domain; the
+    offsets count from a base on a PLACEMENT_PERIOD boundary."""
+    dI, dJ, dK = domain
+    layout, total = {}, 0
+    temp_dims = {t.name: tuple(t.data_dims) for t in plan.stencil.temporaries}
+    temp_levels = {t.name: (max(dK, 1) if "K" in t.axes else 1) for t in plan.stencil.temporaries}
+    for name, (dt, ((ilo, ihi), (jlo, jhi))) in plan.scratch.items():
+        oi = -(-(-ilo) // 4) * 4  # the domain's first column on a 16-byte boundary
+        ni = -(-(dI + ihi + oi) // 32) * 32  # rows padded like the storage preset
+        nj = dJ + jhi - jlo
+        # equally shaped temporaries must not sit at the same address modulo 4 MiB (see
+        # storage/allocators.py:_placement_shift): temporary n starts at n * 1 MiB (mod 4 MiB) of a
+        # buffer whose base is brought to a 4 MiB boundary below
+        n_elem = int(np.prod(temp_dims.get(name, ()) or (1,)))  # data dimensions: outermost
+        nbytes = -(-(ni * nj * temp_levels[name] * n_elem * dt.itemsize) // 256) * 256
+        if nbytes >= PLACEMENT_MIN_BYTES:
+            total = -(-total // PLACEMENT_PERIOD) * PLACEMENT_PERIOD + (len(layout) % 4) * PLACEMENT_STEP
+        layout[name] = (total, ni, nj, dt.itemsize, oi, -jlo)
+        total += nbytes
+    return layout, total
+
+
+def select_twin(kern, twins, lead: int, no_alias: bool, geometry, domain, levels=None):
+    """Which twin of a stage kernel a call launches, and on what grid: (label, grid, block) with the label one of
+    "point" | "vec" | "vecs" | "tc<n>", or (None, None, None) when the stage has nothing to do.  A pure function of the
+    kernel record, of which twins the compiled variant has -- ``twins``: (`_vec` exists, `_vecs` exists, ((n, smallest
+    domain K) of every `_tc<n>`, deepest first)) --, of the common lead of the API fields, of whether the arguments are
+    free of aliases, of ``geometry`` (name -> (origin pointer, J stride, K stride in items, item size)) and of the domain.
+    ``levels``: the K levels of this launch (the domain's; 1 for a stage the host launches plane by plane)."""
+    has_vec, has_shared, tc = twins
+    dI, dJ, dK = domain
+    if levels is None:
+        levels = dK
+    (ilo, ihi), (jlo, jhi) = kern.extent
+    label = "point"
+    for n_reg, min_k in tc:  # deepest first: the most levels that stay in registers + LDS between the two sweeps
+        if dK >= min_k:
+            label = f"tc{n_reg}"
+            break
+    ni, nj = dI + ihi - ilo, dJ + jhi - jlo
+    if ni <= 0 or nj <= 0 or levels <= 0:
+        return None, None, None
+    nk = levels if kern.mapping == "ijk" else 1
+    if has_shared and no_alias and (kern.shared_preferred or not has_vec) and lead < kern.shared_vec and all(
+            (geometry[n][0] - lead * geometry[n][3]) % (kern.shared_vec * geometry[n][3]) == 0
+            and geometry[n][1] % kern.shared_vec == 0 and geometry[n][2] % kern.shared_vec == 0 for n in kern.shared_fields):
+        # temporaries shared between lanes: waves overlap by the halo lanes
+        per_wave = (64 - 2 * kern.shared_halo) * kern.shared_vec
+        grid = (-(-(ni + lead) // (per_wave * (kern.block[0] // 64))), -(-nj // (kern.block[1] * kern.shared_rows)), nk)
+        return "vecs", grid, tuple(kern.block)
+    if has_vec and no_alias and lead < kern.vec and all(
+            (geometry[n][0] - lead * geometry[n][3]) % (kern.vec * geometry[n][3]) == 0 and geometry[n][1] % kern.vec == 0
+            and geometry[n][2] % kern.vec == 0 for n in kern.vec_fields):
+        # every lane's vector is naturally aligned (after the lead)
+        block = kern.vec_block or kern.block
+        need = -(-(ni + lead) // kern.vec)  # lanes along I
+        if block[1] == 1 and block[0] == 256 and -(-need // 320) * 320 < -(-need // 256) * 256:
+            block = (320, 1, 1)  # five waves: fewer idle lanes than a second workgroup per row
+        return "vec", (-(-need // block[0]), -(-nj // (block[1] * kern.vec_rows)), nk), tuple(block)
+    return label, (-(-ni // kern.block[0]), -(-nj // kern.block[1]), nk), tuple(kern.block)
 
 
 class HipGenericStencilObject(StencilObject):
@@ -341,22 +408,7 @@ class HipGenericStencilObject(StencilObject):
             key = (stream, dI, dJ, dK)
             entry = cls._gt_scratch_.get(key)
             if entry is None:
-                layout, total = {}, 0
-                temp_dims = {t.name: tuple(t.data_dims) for t in plan.stencil.temporaries}
-                temp_levels = {t.name: (max(dK, 1) if "K" in t.axes else 1) for t in plan.stencil.temporaries}
-                for name, (dt, ((ilo, ihi), (jlo, jhi))) in plan.scratch.items():
-                    oi = -(-(-ilo) // 4) * 4  # the domain's first column on a 16-byte boundary
-                    ni = -(-(dI + ihi + oi) // 32) * 32  # rows padded like the storage preset
-                    nj = dJ + jhi - jlo
-                    # equally shaped temporaries must not sit at the same address modulo 4 MiB (see
-                    # storage/allocators.py:_placement_shift): temporary n starts at n * 1 MiB (mod 4 MiB) of a
-                    # buffer whose base is brought to a 4 MiB boundary below
-                    n_elem = int(np.prod(temp_dims.get(name, ()) or (1,)))  # data dimensions: outermost
-                    nbytes = -(-(ni * nj * temp_levels[name] * n_elem * dt.itemsize) // 256) * 256
-                    if nbytes >= PLACEMENT_MIN_BYTES:
-                        total = -(-total // PLACEMENT_PERIOD) * PLACEMENT_PERIOD + (len(layout) % 4) * PLACEMENT_STEP
-                    layout[name] = (total, ni, nj, dt.itemsize, oi, -jlo)
-                    total += nbytes
+                layout, total = scratch_layout(plan, (dI, dJ, dK))
                 # zeros, not empty: a temporary that is assigned under a condition only is read (and ignored) where the
                 # condition does not hold, and a byte that is neither 0 nor 1 read as a C++ bool is undefined behaviour
                 # the compiler builds on -- stale memory made a mask temporary of an `elif` chain produce wrong stores
@@ -423,36 +475,24 @@ class HipGenericStencilObject(StencilObject):
                 per_level[k] = ctypes.byref(copy)
             return per_level[k]
 
-        def geometry_of(kern, fn, vfn, tfns, sfn, levels: int):
-            (ilo, ihi), (jlo, jhi) = kern.extent
-            for tfn, min_k in tfns:  # deepest first: the most levels that stay in registers + LDS between the two sweeps
-                if dK >= min_k:
-                    fn = tfn
-                    break
-            ni, nj = dI + ihi - ilo, dJ + jhi - jlo
-            if ni <= 0 or nj <= 0 or levels <= 0:
+        def geometry_of(kern, fn, vfn, tfns, sfn, tcn, levels: int):
+            twins = (vfn is not None, sfn is not None, tuple((n_reg, min_k) for n_reg, (_, min_k) in zip(tcn, tfns)))
+            label, grid, block = select_twin(kern, twins, args.lead, no_alias, geometry, (dI, dJ, dK), levels)
+            if label is None:
                 return None
-            nk = levels if kern.mapping == "ijk" else 1
-            if sfn is not None and no_alias and (kern.shared_preferred or vfn is None) and args.lead < kern.shared_vec and all(
-                    (geometry[n][0] - args.lead * geometry[n][3]) % (kern.shared_vec * geometry[n][3]) == 0
-                    and geometry[n][1] % kern.shared_vec == 0 and geometry[n][2] % kern.shared_vec == 0 for n in kern.shared_fields):
-                # temporaries shared between lanes: waves overlap by the halo lanes
-                per_wave = (64 - 2 * kern.shared_halo) * kern.shared_vec
-                grid = _U3(-(-(ni + args.lead) // (per_wave * (kern.block[0] // 64))), -(-nj // (kern.block[1] * kern.shared_rows)), nk)
-                return sfn, grid, _U3(*kern.block)
-            if vfn is not None and no_alias and args.lead < kern.vec and all(
-                    (geometry[n][0] - args.lead * geometry[n][3]) % (kern.vec * geometry[n][3]) == 0 and geometry[n][1] % kern.vec == 0
-                    and geometry[n][2] % kern.vec == 0 for n in kern.vec_fields):
-                # every lane's vector is naturally aligned (after the lead)
-                block = kern.vec_block or kern.block
-                need = -(-(ni + args.lead) // kern.vec)  # lanes along I
-                if block[1] == 1 and block[0] == 256 and -(-need // 320) * 320 < -(-need // 256) * 256:
-                    block = (320, 1, 1)  # five waves: fewer idle lanes than a second workgroup per row
-                return vfn, _U3(-(-need // block[0]), -(-nj // (block[1] * kern.vec_rows)), nk), _U3(*block)
-            return fn, _U3(-(-ni // kern.block[0]), -(-nj // kern.block[1]), nk), _U3(*kern.block)
+            chosen[kern.name] = label
+            if label == "vecs":
+                fn = sfn
+            elif label == "vec":
+                fn = vfn
+            elif label != "point":
+                fn = tfns[tcn.index(int(label[2:]))][0]
+            return fn, _U3(*grid), _U3(*block)
 
         triples = list(zip(program.kernels, variant.functions, variant.vec_functions, variant.tc_functions,
-                           variant.shared_functions))
+                           variant.shared_functions, variant.tc_levels))
+        chosen: Dict[str, str] = {}  # kernel -> label of the twin select_twin chose
+        sequence: List[str] = []  # the kernel of every launch
         n = 0
         while n < len(triples):
             kern = triples[n][0]
@@ -460,6 +500,7 @@ class HipGenericStencilObject(StencilObject):
                 g = geometry_of(*triples[n], dK)
                 if g is not None:
                     launches.append((*g, args_ref))
+                    sequence.append(kern.name)
                 n += 1
                 continue
             # the stages of one sequential block with cross-column dependencies: once per K level, in sweep order
@@ -471,9 +512,10 @@ class HipGenericStencilObject(StencilObject):
             levels = range(k0, k1) if order != "backward" else range(k1 - 1, k0 - 1, -1)
             body = [geometry_of(*t, 1) for t in triples[n:m]]
             for k in levels:
-                for g in body:
+                for t, g in zip(triples[n:m], body):
                     if g is not None:
                         launches.append((*g, level_args(k)))
+                        sequence.append(t[0].name)
             n = m
         # the scratch buffer must outlive every cached plan that points into it
         n = len(launches)
@@ -483,4 +525,6 @@ class HipGenericStencilObject(StencilObject):
                      (ctypes.c_uint32 * (3 * n))(*[v for _, g, _, _ in launches for v in g]),
                      (ctypes.c_uint32 * (3 * n))(*[v for _, _, b, _ in launches for v in b]),
                      (ctypes.c_void_p * n)(*[ctypes.addressof(a._obj) for _, _, _, a in launches]))
-        return args, launches, (cls._gt_scratch_.get((stream, dI, dJ, dK)), keep_args, batch)
+        # (last: which twin every launch is, [(kernel, label)] -- for tests and diagnostics, nothing here reads it)
+        return args, launches, (cls._gt_scratch_.get((stream, dI, dJ, dK)), keep_args, batch,
+                                (vkey, [(name, chosen[name]) for name in sequence]))
