@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_overlap_table",
     "gt4mi_horizontal_remap",
     "gt4mi_line_solve",
+    "gt4mi_line_scan",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -131,6 +132,10 @@ HREMAP_PCM, HREMAP_PLM, HREMAP_DRY_RUN = 0, 1, 256
 # gt4mi_line_solve: paths, flags
 LINE_PATH_LANES, LINE_PATH_TILES, LINE_PATH_ITEMS = 0, 1, 2
 LINE_PERIODIC, LINE_DRY_RUN = 1, 256
+# gt4mi_line_scan: ops, paths, flags
+SCAN_SUM, SCAN_MAX, SCAN_MIN = 0, 1, 2
+SCAN_PATH_LANES, SCAN_PATH_TILES, SCAN_PATH_ITEMS = 0, 1, 2
+SCAN_EXCLUSIVE, SCAN_REVERSE, SCAN_WIDE, SCAN_DRY_RUN = 1, 2, 4, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -266,6 +271,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_line_solve.restype = I
     lib.gt4mi_line_solve.argtypes = [FP, FP, I, FP, FP, FP, DOM, I, I, I, P, ctypes.c_int64, P, ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_line_scan.restype = I
+    lib.gt4mi_line_scan.argtypes = [FP, FP, I, FP, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

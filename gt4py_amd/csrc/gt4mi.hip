@@ -21,6 +21,7 @@
 #include "departure_interp.hip.h"
 #include "horizontal_remap.hip.h"
 #include "line_solve.hip.h"
+#include "line_scan.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -276,6 +277,11 @@ int gt4mi_line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfields
                      int64_t workspace_bytes, void* stream, int64_t* workspace_needed, int* path, int* launches) {
     return gt4mi::line_solve(out, rhs, nfields, lower, diag, upper, extent, axis, elem_size, flags, workspace, workspace_bytes,
                              static_cast<hipStream_t>(stream), workspace_needed, path, launches);
+}
+
+int gt4mi_line_scan(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* weight, const int64_t extent[3], int axis,
+                    int elem_size, int op, int flags, void* stream, int* path, int* launches) {
+    return gt4mi::line_scan(dst, src, nfields, weight, extent, axis, elem_size, op, flags, static_cast<hipStream_t>(stream), path, launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

@@ -454,16 +454,16 @@ inline void line_launch(const LineArgs& a, int path, hipStream_t stream) {
 }
 
 // The path of a call and its lane axis: `unit[ax]` = every field of the call has unit item stride along ax (a coefficient may
-// also be broadcast along an axis that is not the line axis).
-inline int line_plan(const gt4mi_field* out, const gt4mi_field* rhs, int nfields, const gt4mi_field* const coef[3], const int64_t extent[3],
-                     int axis, int elem_size, int* lane_axis) {
+// also be broadcast along an axis that is not the line axis).  `coef`: the `ncoef` fields every pair reads (line_scan: its weight, or none).
+inline int line_plan(const gt4mi_field* out, const gt4mi_field* rhs, int nfields, const gt4mi_field* const* coef, int ncoef,
+                     const int64_t extent[3], int axis, int elem_size, int* lane_axis) {
     const int other0 = axis == 0 ? 1 : 0, other1 = axis == 2 ? 1 : 2;
     bool unit[3];
     for (int ax = 0; ax < 3; ++ax) {
         unit[ax] = true;
         for (int n = 0; n < nfields; ++n)
             if (out[n].stride[ax] != elem_size || rhs[n].stride[ax] != elem_size) unit[ax] = false;
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < ncoef; ++c)
             if (coef[c]->stride[ax] != elem_size && !(ax != axis && coef[c]->stride[ax] == 0)) unit[ax] = false;
     }
     *lane_axis = other0;
@@ -517,7 +517,7 @@ inline int line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfield
     if (int rc = check_pairs_disjoint("line_solve", out, rhs, nfields, extent, extent, elem_size, elem_size, nullptr, shared, 3, &LINE_ROLES))
         return rc;
     int lane_axis = 0;
-    const int which = line_plan(out, rhs, nfields, coef, extent, axis, elem_size, &lane_axis);
+    const int which = line_plan(out, rhs, nfields, coef, 3, extent, axis, elem_size, &lane_axis);
     const int order[3] = {axis, lane_axis, 3 - axis - lane_axis};
     const int64_t lines = extent[order[1]] * extent[order[2]];
     if (lines > (int64_t)INT32_MAX - LINE_BLOCK) return fail(GT4MI_ERR_UNSUPPORTED, "line_solve: too many lines for one launch");

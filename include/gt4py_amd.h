@@ -639,6 +639,50 @@ int gt4mi_line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfields
                      const gt4mi_field* upper, const int64_t extent[3], int axis, int elem_size, int flags, void* workspace,
                      int64_t workspace_bytes, void* stream, int64_t* workspace_needed, int* path, int* launches);
 
+/* ---- prefix scans along I, J or K (NEW entry, additive: the ABI version stays 8; the reference has no scan: its users slice a storage and
+ * call numpy / cupy `cumsum` or `maximum.accumulate` on the slice -- one call and one fresh array per field, the order of the float
+ * additions whatever the library picks -- or write a FORWARD / BACKWARD stencil, which exists along K only and takes one field) ----------
+ * For every line along `axis` (0 = I, 1 = J, 2 = K) of the box [origin, origin + extent) and each of `nfields` (dst, src) pairs, dst gets
+ * the running sum, maximum or minimum (`op`) of src along the line, at every point of it, in ONE kernel launch per 8 pairs, on `stream`,
+ * without synchronisation, allocation or workspace.  `elem_size` is 4 (float32) or 8 (float64) and is the item size of EVERY field.
+ * `weight` (may be NULL; GT4MI_SCAN_SUM only) holds the terms' factors -- the grid spacing of an integral -- and is never written; it
+ * may have byte stride 0 along the two axes other than `axis`: a 1-d array of n items that every line shares broadcasts without a copy
+ * and is exempt from the shape check on those axes.  A src stride of 0 broadcasts too; a dst stride of 0 on an extent above 1 is
+ * GT4MI_ERR_INVALID_ARGUMENT.
+ * dst[k] may BE src[k] -- the same first item and the same strides: an in-place scan.  Every other meeting of the bytes of a dst box (first
+ * to last item) with a src box, another dst box or the weight is refused.
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/line_scan.hip.h states it again, tests/line_scan_ref.py restates it in plain Python and in
+ * numpy).  T is the fields' type; A is double where GT4MI_SCAN_WIDE is set, op is GT4MI_SCAN_SUM and T is float, else T (GT4MI_SCAN_WIDE
+ * has no effect on float64 fields or on MAX and MIN).  x[0 .. n), n = extent[axis], is the line in scan order: from the low end, with
+ * GT4MI_SCAN_REVERSE from the far end (the BACKWARD sweep); w is the weight in the same order.
+ *   SUM  t[m] = A(x[m]), or A(x[m]) * A(w[m]) with one rounding in A
+ *        s[0] = t[0]   (NOT 0 + t[0]: a leading -0.0 stays -0.0, as in numpy.cumsum)
+ *        s[m] = s[m-1] + t[m]   one rounding in A, no FMA, strictly sequential
+ *   MAX  s[0] = x[0] ;  s[m] = s[m-1] if (s[m-1] != s[m-1] or s[m-1] > x[m]) else x[m]
+ *        a NaN, once met, stays; on a tie (signed zeros included) the newer item is taken; it is a select: bit patterns (NaN payloads)
+ *        are moved, not computed.  Not fmax / fmin, which drop NaNs.
+ *   MIN  the same with <.
+ *   dst[m] = T(s[m]) ;  with GT4MI_SCAN_EXCLUSIVE dst[0] = the identity (+0.0 for SUM, -inf for MAX, +inf for MIN) and dst[m] = T(s[m-1])
+ * dst is written at the item's own index, also in a reverse scan.  The float sum is numpy.cumsum along that axis bit for bit, with
+ * GT4MI_SCAN_WIDE numpy.cumsum(x, dtype=float64).astype(float32).  The order is sequential because lines are plentiful: parallelism comes
+ * across lines; a box of few, long lines is served correctly and not fast (a segmented parallel scan, whose order of additions would
+ * depend on the length, is out of scope).  Every loop counts to n; no loop bound and no address depends on field data: a NaN or an inf
+ * reaches the rest of its line as written above and no other line.  No byte outside the dst boxes is written.
+ * *path (may be NULL) = which kernel the strides of the call select, by the rule of gt4mi_line_solve: GT4MI_SCAN_PATH_LANES (an axis
+ * other than `axis` has unit stride in every field: lanes along it, every step a coalesced row), GT4MI_SCAN_PATH_TILES (`axis` itself has
+ * unit stride in every field: a lane owns a line, tiles of 64 lines x 128 bytes go through LDS), GT4MI_SCAN_PATH_ITEMS (anything else:
+ * one lane per line, item by item, correct and slow).  The bits do not depend on the path.
+ * Refusals: null pointers, nfields < 1, an invalid extent, axis or op, an unknown flag, a weight with MAX or MIN
+ * (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a misaligned field, a forbidden overlap (GT4MI_ERR_UNSUPPORTED); a box
+ * that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS).  An extent with a zero entry is GT4MI_OK, nothing enqueued.  Every check runs
+ * before the first launch; a refused call enqueues nothing.  With GT4MI_SCAN_DRY_RUN the checks run, *path and *launches are set and no
+ * device is touched.  *launches (may be NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_SCAN_SUM = 0, GT4MI_SCAN_MAX = 1, GT4MI_SCAN_MIN = 2 };
+enum { GT4MI_SCAN_PATH_LANES = 0, GT4MI_SCAN_PATH_TILES = 1, GT4MI_SCAN_PATH_ITEMS = 2 };
+enum { GT4MI_SCAN_EXCLUSIVE = 1, GT4MI_SCAN_REVERSE = 2, GT4MI_SCAN_WIDE = 4, GT4MI_SCAN_DRY_RUN = 256 };
+int gt4mi_line_scan(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* weight, const int64_t extent[3], int axis,
+                    int elem_size, int op, int flags, void* stream, int* path, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
