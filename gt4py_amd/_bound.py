@@ -155,6 +155,62 @@ def _float_pairs(who: str, dst, src, halo, method, methods, *, shared, names: Se
     return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4
 
 
+#: the line axes of ``solve_lines``, ``scan_lines`` and (with 0, 1, 2 and lower case as well) ``line_stats``
+AXES = {"I": 0, "J": 1, "K": 2}
+
+
+def _coefficient(a: DeviceArray, axis: int, start) -> "_lib.Field":
+    """A field every line reads: IJK, or 1-d along ``axis`` (broadcast: stride 0 along the two other axes)."""
+    if a.ndim == 1:  # n items along the line axis: every line reads the same ones
+        shape, strides, origin = [1, 1, 1], [0, 0, 0], [0, 0, 0]
+        shape[axis], strides[axis] = a.shape[0], a.strides[0]
+        return _lib.Field.make(a.ptr, shape, strides, origin)
+    return _lib.Field.make(a.ptr, a.shape, a.strides, start)
+
+
+def _line_pairs(who: str, dst, src, axis, halo, origin, *, shared, names: Sequence[str], sharing: str, own_checks=None,
+                roles=("destination(s)", "source(s)")):
+    """:func:`_pair_lists` for a call along the lines of ``axis``, in the order the checks have always had: the axis,
+    ``own_checks()`` (the caller's other names), IJK fields and shared fields ``names`` that are IJK or 1-d along the axis, ONE
+    float dtype (``sharing``: what its message calls them), the common compute domain -- along the line axis the arrays must
+    agree, a line is never cut short silently -- and the length of every 1-d shared field.  Adds to what :func:`_pair_lists`
+    returns: origin, domain, ``extent`` (the IJK box: the domain grown by the halo in I and J), ``n`` (the line length),
+    ``lines`` (how many the box holds), ``ax`` (the axis as 0, 1, 2), ``start`` (the box's first point in every IJK array)."""
+    dsts, srcs, d_arrays, s_arrays, x_arrays, halo4 = _pair_lists(who, dst, src, halo, shared=shared, roles=roles)
+    if axis not in AXES:
+        raise ValueError(f"axis must be one of {sorted(AXES)}, not {axis!r}")
+    if own_checks is not None:
+        own_checks()
+    ax = AXES[axis]
+    for a in d_arrays + s_arrays:
+        if a.ndim != 3:
+            raise ValueError(f"{who} takes IJK fields, not a field of {a.ndim} dimension(s)")
+    for name, a in zip(names, x_arrays):
+        if a.ndim not in (1, 3):
+            raise ValueError(f"{name} must be an IJK field or a 1-d array along {axis}, not a field of {a.ndim} dimension(s)")
+    dtype = d_arrays[0].dtype
+    for a in d_arrays + s_arrays + x_arrays:
+        if a.dtype != dtype:
+            raise TypeError(f"{sharing} of one call share a dtype: {dtype} and {a.dtype} differ")
+    if dtype not in FLOATS:
+        raise TypeError(f"{who} takes float32 or float64 fields, not {dtype}")
+    lo_i, hi_i, lo_j, hi_j = halo4
+    origin = _origin3(origin, halo4)
+    full = [a for a in d_arrays + s_arrays + x_arrays if a.ndim == 3]
+    domain = _common_domain(full, halo4, origin, full, least_k=1)
+    for a in full:
+        have = a.shape[ax] - origin[ax] - (hi_i, hi_j, 0)[ax]
+        if have != domain[ax]:
+            raise ValueError(f"the fields of one call share their length along {axis}: {domain[ax]} and {have} differ")
+    extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j, domain[2])
+    n, lines = extent[ax], extent[(ax + 1) % 3] * extent[(ax + 2) % 3]
+    for name, a in zip(names, x_arrays):
+        if a.ndim == 1 and a.shape[0] != n:
+            raise ValueError(f"{name} has {a.shape[0]} items, a line of {n} points along {axis} needs {n}")
+    start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
+    return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4, origin, domain, extent, n, lines, ax, start
+
+
 def refuse_host_arrays(who: str, arrays) -> None:
     for a in arrays:
         if not a.tensor.is_cuda:

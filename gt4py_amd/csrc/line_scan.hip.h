@@ -20,13 +20,13 @@
 // checked against every field's shape; no loop bound and no address depends on field data.  A lane owns its line from the first
 // load to the last store, which is why dst[n] may BE src[n] (the same box): an item is stored after it was loaded, by the same lane.
 //
-// THREE PATHS, chosen by line_solve's rule (line_plan) and reported as GT4MI_SCAN_PATH_*:
+// THREE PATHS, chosen by the family's rule (line_geometry.hip.h: LinePlan) and reported as GT4MI_SCAN_PATH_*:
 //   LANES  an axis OTHER than the line axis has unit stride in every field (0 = broadcast in the weight): lanes run along it, a lane
 //          owns a line, every step is a coalesced row segment.  The carries stay in registers, the field loop sits inside the step.
 //          The loads of the NEXT SCAN_AHEAD steps are issued before the arithmetic and the stores of the SCAN_AHEAD steps in hand
 //          (two register buffers): up to 2 x SCAN_AHEAD rows per field are in flight per lane.  Read once, written once.
 //   TILES  the LINE axis has unit stride in every field: a workgroup IS one wave and moves tiles of 64 lines x one 128-byte run along
-//          the line through LDS (line_solve.hip.h's line_tile_move, field_copy.hip.h's padded pitch); a lane scans its run of the
+//          the line through LDS (line_geometry.hip.h's line_tile_move, field_copy.hip.h's padded pitch); a lane scans its run of the
 //          tile sequentially, the carry stays in a register from tile to tile; a reverse scan walks the tiles from the far end.  The
 //          tiles are private to the wave: the barriers are wave barriers.
 //   ITEMS  anything else: one lane per line, item by item, uncoalesced: correct and slow (the LANES kernel, one step in hand).
@@ -37,9 +37,7 @@
 
 #include <type_traits>
 
-#include "common.hip.h"
-#include "field_args.hip.h"
-#include "line_solve.hip.h"  // LineTile, line_tile_move, line_plan
+#include "line_geometry.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -86,9 +84,9 @@ __device__ __forceinline__ T scan_step(A& s, T x, T w, bool first, int op, bool 
 template <typename T, typename A, int NF, int AHEAD>
 __global__ void __launch_bounds__(SCAN_BLOCK)
 line_scan_march_kernel(const ScanArgs a) {
-    const int64_t line = (int64_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    if (line >= (int64_t)a.na * a.nb) return;
-    const int64_t ib = line / a.na, ia = line - ib * a.na;
+    const LineLane l = line_lane(SCAN_BLOCK, blockIdx.x, a.na, (int64_t)a.na * a.nb);
+    if (!l.ok) return;
+    const int64_t ia = l.ia(), ib = l.ib();
     const int n = a.n, nf = a.nf, op = a.op;
     const bool weighted = a.w.p != nullptr, exclusive = a.exclusive != 0;
     // scan position m is item first + dir * m of the line
@@ -157,11 +155,9 @@ line_scan_tile_kernel(const ScanArgs a) {
     __shared__ T tw[LINE_TILE_LINES][L::PITCH];  // the weight's run
     __shared__ T tf[LINE_TILE_LINES][L::PITCH];  // the field in hand
     const int lane = (int)threadIdx.x;
-    const int64_t lines = (int64_t)a.na * a.nb;
-    const int64_t line = (int64_t)blockIdx.x * LINE_TILE_LINES + lane;
-    const bool ok = line < lines;
-    const int64_t mine = ok ? line : 0;  // (a lane without a line computes on line 0's addresses and neither loads nor stores)
-    const int64_t ib = mine / a.na, ia = mine - ib * a.na;
+    const LineLane l = line_lane(LINE_TILE_LINES, blockIdx.x, a.na, (int64_t)a.na * a.nb);
+    const bool ok = l.ok;
+    const int64_t ia = l.ia(), ib = l.ib();
     const int n = a.n, nf = a.nf, op = a.op;
     const bool weighted = a.w.p != nullptr, exclusive = a.exclusive != 0, reverse = a.reverse != 0;
     const int64_t ow = ia * a.w.s[1] + ib * a.w.s[2];
@@ -207,48 +203,36 @@ const BoxChecks SCAN_CHECKS = {"line_scan", "extent", "only a src or the weight 
 const PairRoles SCAN_ROLES = {"dst", "src", true};  // a dst may BE its own src (the same box), and meet nothing else
 
 template <typename T, typename A>
-inline void scan_launch(const ScanArgs& a, int path, hipStream_t stream) {
-    const int64_t lines = (int64_t)a.na * a.nb;
+inline void scan_launch(const ScanArgs& a, const LineGrid& g, hipStream_t stream) {
     with_pair_entries(a.nf, [&](auto nf) {
         constexpr int NF = decltype(nf)::value;
-        if (path == GT4MI_SCAN_PATH_TILES)
-            hipLaunchKernelGGL((line_scan_tile_kernel<T, A, NF>), dim3((unsigned)cdiv(lines, LINE_TILE_LINES)), dim3(LINE_TILE_LINES), 0, stream, a);
-        else if (path == GT4MI_SCAN_PATH_LANES)
-            hipLaunchKernelGGL((line_scan_march_kernel<T, A, NF, SCAN_AHEAD>), dim3((unsigned)cdiv(lines, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, stream, a);
-        else
-            hipLaunchKernelGGL((line_scan_march_kernel<T, A, NF, 1>), dim3((unsigned)cdiv(lines, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, stream, a);
+        line_launch(g.path, g.lines, SCAN_BLOCK, line_scan_tile_kernel<T, A, NF>, line_scan_march_kernel<T, A, NF, SCAN_AHEAD>,
+                    line_scan_march_kernel<T, A, NF, 1>, a, stream);
     });
 }
 
 // every check, then (unless `flags` carries GT4MI_SCAN_DRY_RUN) the launches
 inline int line_scan(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* weight, const int64_t extent[3], int axis,
                      int elem_size, int op, int flags, hipStream_t stream, int* path, int* launches) {
-    static_assert(GT4MI_SCAN_PATH_LANES == GT4MI_LINE_PATH_LANES && GT4MI_SCAN_PATH_TILES == GT4MI_LINE_PATH_TILES &&
-                  GT4MI_SCAN_PATH_ITEMS == GT4MI_LINE_PATH_ITEMS, "line_plan's paths are reported as they are");
     if (launches) *launches = 0;
     if (path) *path = -1;
-    if (dst == nullptr || src == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: %s is null", dst == nullptr ? "dst" : "src");
-    if (extent == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: extent is null");
-    if (nfields < 1) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: nfields = %d, at least one pair is needed", nfields);
-    for (int ax = 0; ax < 3; ++ax)
-        if (extent[ax] < 0 || extent[ax] > INT32_MAX)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: invalid extent %lld along axis %d", (long long)extent[ax], ax);
-    if (axis < 0 || axis > 2) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: axis %d is not 0 (I), 1 (J) or 2 (K)", axis);
-    if (op != GT4MI_SCAN_SUM && op != GT4MI_SCAN_MAX && op != GT4MI_SCAN_MIN)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: op %d is not GT4MI_SCAN_SUM, GT4MI_SCAN_MAX or GT4MI_SCAN_MIN", op);
-    if (flags & ~(GT4MI_SCAN_EXCLUSIVE | GT4MI_SCAN_REVERSE | GT4MI_SCAN_WIDE | GT4MI_SCAN_DRY_RUN))
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: unknown bits in flags 0x%x", (unsigned)flags);
-    if (elem_size != 4 && elem_size != 8)
-        return fail(GT4MI_ERR_UNSUPPORTED, "line_scan: item size %d is not supported (float32 or float64)", elem_size);
-    if (weight != nullptr && op != GT4MI_SCAN_SUM)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: a weight goes with GT4MI_SCAN_SUM only, op is %d", op);
+    int weight_free = 0;  // a 1-d weight
+    if (int rc = line_front(
+            SCAN_CHECKS, SCAN_ROLES, dst, src, nfields, nullptr, extent, axis, elem_size,
+            [&]() -> int {
+                if (op != GT4MI_SCAN_SUM && op != GT4MI_SCAN_MAX && op != GT4MI_SCAN_MIN)
+                    return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: op %d is not GT4MI_SCAN_SUM, GT4MI_SCAN_MAX or GT4MI_SCAN_MIN", op);
+                const bool unknown = (flags & ~(GT4MI_SCAN_EXCLUSIVE | GT4MI_SCAN_REVERSE | GT4MI_SCAN_WIDE | GT4MI_SCAN_DRY_RUN)) != 0;
+                return unknown ? fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: unknown bits in flags 0x%x", (unsigned)flags) : GT4MI_OK;
+            },
+            [&]() -> int {
+                if (weight == nullptr || op == GT4MI_SCAN_SUM) return GT4MI_OK;
+                return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_scan: a weight goes with GT4MI_SCAN_SUM only, op is %d", op);
+            },
+            &weight_free))
+        return rc;
     const bool dry = (flags & GT4MI_SCAN_DRY_RUN) != 0;
     const bool wide = (flags & GT4MI_SCAN_WIDE) != 0 && op == GT4MI_SCAN_SUM && elem_size == 4;
-    const int weight_free = 7 & ~(1 << axis);  // a 1-d weight: stride 0 along the two other axes, no shape to check there
-    for (int k = 0; k < nfields; ++k) {
-        if (int rc = check_box_field(SCAN_CHECKS, "dst", k, dst[k], extent, elem_size, true)) return rc;
-        if (int rc = check_box_field(SCAN_CHECKS, "src", k, src[k], extent, elem_size, false)) return rc;
-    }
     if (weight != nullptr)
         if (int rc = check_box_field(SCAN_CHECKS, "weight", 0, *weight, extent, elem_size, false, weight_free)) return rc;
     if (extent[0] == 0 || extent[1] == 0 || extent[2] == 0) return GT4MI_OK;
@@ -257,22 +241,22 @@ inline int line_scan(const gt4mi_field* dst, const gt4mi_field* src, int nfields
     if (int rc = check_pairs_disjoint("line_scan", dst, src, nfields, extent, extent, elem_size, elem_size, nullptr, shared, weight != nullptr ? 1 : 0,
                                       &SCAN_ROLES))
         return rc;
-    int lane_axis = 0;
-    const int which = line_plan(dst, src, nfields, &weight, weight != nullptr ? 1 : 0, extent, axis, elem_size, &lane_axis);
-    const int order[3] = {axis, lane_axis, 3 - axis - lane_axis};
-    const int64_t lines = extent[order[1]] * extent[order[2]];
-    if (lines > (int64_t)INT32_MAX - LINE_TILE_LINES) return fail(GT4MI_ERR_UNSUPPORTED, "line_scan: too many lines for one launch");
-    if (path) *path = which;
+    LinePlan plan(axis, elem_size);
+    for (int k = 0; k < nfields; ++k) plan.strict(dst[k]), plan.strict(src[k]);
+    plan.loose(weight);
+    LineGrid g;
+    if (int rc = line_grid("line_scan", plan, extent, LINE_TILE_LINES, &g)) return rc;
+    if (path) *path = g.path;
     if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
     if (dry) return GT4MI_OK;
     ScanArgs a{};
-    if (weight != nullptr) a.w = shared_field(*weight, elem_size, order);
-    a.n = (int)extent[axis], a.na = (int)extent[order[1]], a.nb = (int)extent[order[2]];
+    if (weight != nullptr) a.w = shared_field(*weight, elem_size, g.order);
+    a.n = (int)extent[axis], a.na = g.na, a.nb = g.nb;
     a.op = op, a.exclusive = (flags & GT4MI_SCAN_EXCLUSIVE) != 0, a.reverse = (flags & GT4MI_SCAN_REVERSE) != 0;
     int next = 0;
-    while (next_pair_batch(a, dst, src, &next, nfields, elem_size, order)) {
-        if (wide) scan_launch<float, double>(a, which, stream);
-        else with_item_type(elem_size, [&](auto t) { scan_launch<decltype(t), decltype(t)>(a, which, stream); });
+    while (next_pair_batch(a, dst, src, &next, nfields, elem_size, g.order)) {
+        if (wide) scan_launch<float, double>(a, g, stream);
+        else with_item_type(elem_size, [&](auto t) { scan_launch<decltype(t), decltype(t)>(a, g, stream); });
         GT4MI_HIP_CHECK(hipGetLastError());
     }
     return GT4MI_OK;

@@ -44,8 +44,7 @@
 
 #include <type_traits>
 
-#include "common.hip.h"
-#include "field_args.hip.h"
+#include "line_geometry.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -53,8 +52,6 @@ namespace gt4mi {
 
 constexpr int LINE_BLOCK = 256;      // lanes (= lines) of a workgroup on the LANES / ITEMS paths
 constexpr int LINE_AHEAD = 4;        // steps whose loads are in flight on the LANES path
-constexpr int LINE_TILE_LINES = 64;  // TILES: lines of a tile = lanes of the wave that owns it
-constexpr int LINE_TILE_BYTES = 128; // TILES: the run along the line a tile covers
 
 // Every stride (ITEMS) is permuted by the host: [0] the line axis, [1] the lane axis A, [2] the remaining axis B.
 struct LineArgs {
@@ -70,9 +67,9 @@ struct LineArgs {
 template <typename T, int NF, int AHEAD>
 __global__ void __launch_bounds__(LINE_BLOCK)
 line_solve_march_kernel(const LineArgs a) {
-    const int64_t line = (int64_t)blockIdx.x * LINE_BLOCK + threadIdx.x;
-    if (line >= (int64_t)a.na * a.nb) return;
-    const int64_t ib = line / a.na, ia = line - ib * a.na;
+    const LineLane l = line_lane(LINE_BLOCK, blockIdx.x, a.na, (int64_t)a.na * a.nb);
+    if (!l.ok) return;
+    const int64_t line = l.line, ia = l.ia(), ib = l.ib();
     const int n = a.n, nf = a.nf;
     const bool periodic = a.periodic != 0;
     const T* const pa = reinterpret_cast<const T*>(a.lo.p) + ia * a.lo.s[1] + ib * a.lo.s[2];
@@ -230,51 +227,7 @@ line_solve_march_kernel(const LineArgs a) {
     }
 }
 
-// ---- TILES ------------------------------------------------------------------------------------------------------------------
-// One wave = one workgroup = LINE_TILE_LINES consecutive lines.  tile[l][r]: line l of the wave, item r of the run.
-template <typename T>
-struct LineTile {
-    static constexpr int R = LINE_TILE_BYTES / (int)sizeof(T);   // items of a run: 32 (float) / 16 (double)
-    static constexpr int PITCH = R + 1;                          // odd in items of 4 / 8 bytes: see the header
-    static constexpr int LINES_PER_PASS = LINE_TILE_LINES / R;   // lines one load / store instruction of the wave covers
-    static constexpr int PASSES = R;                             // = LINE_TILE_LINES / LINES_PER_PASS
-};
-
-// Move the run [m0, m0 + R) of the wave's lines between global memory and a tile; `off` is THIS lane's line offset (items) in the
-// field (the line axis has item stride 1 on this path), `ok` whether this lane's line exists.  Lane l moves item (l % R) of line
-// (pass * LINES_PER_PASS + l / R): consecutive lanes on consecutive items.  Item `skip` of the line (-1: none) is not moved: a[0] and
-// c[n-1], which the contract never reads, stay out of the tile (their slots are never used).  A load takes a pointer to const.
-template <typename T, bool LOAD>
-__device__ __forceinline__ void line_tile_move(T (*tile)[LineTile<T>::PITCH], std::conditional_t<LOAD, const T, T>* base, int64_t off, bool ok,
-                                               int m0, int n, int skip = -1) {
-    using L = LineTile<T>;
-    const int lane = (int)threadIdx.x;
-    const int r = lane % L::R, sub = lane / L::R;
-    // (offsets as two 32-bit halves through the cross-lane read)
-    const int off_lo = (int)(uint32_t)(uint64_t)off, off_hi = (int)(uint32_t)((uint64_t)off >> 32);
-    // every load of the move is issued before the first LDS store (a wave is alone on its SIMD: nothing else hides the latency)
-    T v[L::PASSES];
-    uint32_t there = 0;
-#pragma unroll
-    for (int p = 0; p < L::PASSES; ++p) {
-        const int l = p * L::LINES_PER_PASS + sub;
-        const int64_t o = (int64_t)(((uint64_t)(uint32_t)__shfl(off_hi, l) << 32) | (uint64_t)(uint32_t)__shfl(off_lo, l));
-        const bool here = __shfl((int)ok, l) != 0 && m0 + r < n && m0 + r != skip;
-        there |= (uint32_t)here << p;
-        if constexpr (LOAD) {
-            v[p] = T(0);
-            if (here) v[p] = base[o + (m0 + r)];
-        } else {
-            if (here) base[o + (m0 + r)] = tile[l][r];
-        }
-    }
-    if constexpr (LOAD) {
-#pragma unroll
-        for (int p = 0; p < L::PASSES; ++p)
-            if (there >> p & 1u) tile[p * L::LINES_PER_PASS + sub][r] = v[p];
-    }
-}
-
+// ---- TILES (the tiles and their moves: line_geometry.hip.h) --------------------------------------------------------------
 template <typename T, int NF>
 __global__ void __launch_bounds__(LINE_TILE_LINES)
 line_solve_tile_kernel(const LineArgs a) {
@@ -285,11 +238,9 @@ line_solve_tile_kernel(const LineArgs a) {
     __shared__ T tc[LINE_TILE_LINES][L::PITCH];  // c; cp / q of the run in the later passes
     __shared__ T tf[LINE_TILE_LINES][L::PITCH];  // the field in hand
     const int lane = (int)threadIdx.x;
-    const int64_t lines = (int64_t)a.na * a.nb;
-    const int64_t line = (int64_t)blockIdx.x * LINE_TILE_LINES + lane;
-    const bool ok = line < lines;
-    const int64_t mine = ok ? line : 0;  // (a lane without a line computes on line 0's addresses and neither loads nor stores)
-    const int64_t ib = mine / a.na, ia = mine - ib * a.na;
+    const LineLane l = line_lane(LINE_TILE_LINES, blockIdx.x, a.na, (int64_t)a.na * a.nb);
+    const bool ok = l.ok;
+    const int64_t mine = l.mine(), ia = l.ia(), ib = l.ib();
     const int n = a.n, nf = a.nf;
     const bool periodic = a.periodic != 0;
     const int64_t pitch = a.pitch;
@@ -439,43 +390,6 @@ line_solve_tile_kernel(const LineArgs a) {
 const BoxChecks LINE_CHECKS = {"line_solve", "extent", "only a rhs or a coefficient may be broadcast", false, false};
 const PairRoles LINE_ROLES = {"out", "rhs", true};  // an out may BE its own rhs (the same box), and meet nothing else
 
-template <typename T>
-inline void line_launch(const LineArgs& a, int path, hipStream_t stream) {
-    const int64_t lines = (int64_t)a.na * a.nb;
-    with_pair_entries(a.nf, [&](auto nf) {
-        constexpr int NF = decltype(nf)::value;
-        if (path == GT4MI_LINE_PATH_TILES)
-            hipLaunchKernelGGL((line_solve_tile_kernel<T, NF>), dim3((unsigned)cdiv(lines, LINE_TILE_LINES)), dim3(LINE_TILE_LINES), 0, stream, a);
-        else if (path == GT4MI_LINE_PATH_LANES)
-            hipLaunchKernelGGL((line_solve_march_kernel<T, NF, LINE_AHEAD>), dim3((unsigned)cdiv(lines, LINE_BLOCK)), dim3(LINE_BLOCK), 0, stream, a);
-        else
-            hipLaunchKernelGGL((line_solve_march_kernel<T, NF, 1>), dim3((unsigned)cdiv(lines, LINE_BLOCK)), dim3(LINE_BLOCK), 0, stream, a);
-    });
-}
-
-// The path of a call and its lane axis: `unit[ax]` = every field of the call has unit item stride along ax (a coefficient may
-// also be broadcast along an axis that is not the line axis).  `coef`: the `ncoef` fields every pair reads (line_scan: its weight, or none).
-inline int line_plan(const gt4mi_field* out, const gt4mi_field* rhs, int nfields, const gt4mi_field* const* coef, int ncoef,
-                     const int64_t extent[3], int axis, int elem_size, int* lane_axis) {
-    const int other0 = axis == 0 ? 1 : 0, other1 = axis == 2 ? 1 : 2;
-    bool unit[3];
-    for (int ax = 0; ax < 3; ++ax) {
-        unit[ax] = true;
-        for (int n = 0; n < nfields; ++n)
-            if (out[n].stride[ax] != elem_size || rhs[n].stride[ax] != elem_size) unit[ax] = false;
-        for (int c = 0; c < ncoef; ++c)
-            if (coef[c]->stride[ax] != elem_size && !(ax != axis && coef[c]->stride[ax] == 0)) unit[ax] = false;
-    }
-    *lane_axis = other0;
-    if (unit[axis] && extent[axis] > 1) return GT4MI_LINE_PATH_TILES;
-    for (int ax : {other0, other1})
-        if (unit[ax] && extent[ax] > 1) {
-            *lane_axis = ax;
-            return GT4MI_LINE_PATH_LANES;
-        }
-    return GT4MI_LINE_PATH_ITEMS;
-}
-
 // every check, then (unless `flags` carries GT4MI_LINE_DRY_RUN) the launches
 inline int line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfields, const gt4mi_field* lower, const gt4mi_field* diag,
                       const gt4mi_field* upper, const int64_t extent[3], int axis, int elem_size, int flags, void* workspace,
@@ -483,49 +397,43 @@ inline int line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfield
     if (launches) *launches = 0;
     if (workspace_needed) *workspace_needed = 0;
     if (path) *path = -1;
-    if (out == nullptr || rhs == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: %s is null", out == nullptr ? "out" : "rhs");
-    if (lower == nullptr || diag == nullptr || upper == nullptr)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: %s is null", lower == nullptr ? "lower" : diag == nullptr ? "diag" : "upper");
-    if (extent == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: extent is null");
-    if (nfields < 1) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: nfields = %d, at least one pair is needed", nfields);
-    for (int ax = 0; ax < 3; ++ax)
-        if (extent[ax] < 0 || extent[ax] > INT32_MAX)
-            return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: invalid extent %lld along axis %d", (long long)extent[ax], ax);
-    if (axis < 0 || axis > 2) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: axis %d is not 0 (I), 1 (J) or 2 (K)", axis);
-    if (flags & ~(GT4MI_LINE_PERIODIC | GT4MI_LINE_DRY_RUN))
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: unknown bits in flags 0x%x", (unsigned)flags);
-    if (elem_size != 4 && elem_size != 8)
-        return fail(GT4MI_ERR_UNSUPPORTED, "line_solve: item size %d is not supported (float32 or float64)", elem_size);
     const bool periodic = (flags & GT4MI_LINE_PERIODIC) != 0, dry = (flags & GT4MI_LINE_DRY_RUN) != 0;
+    const char* const missing = lower == nullptr ? "lower" : diag == nullptr ? "diag" : upper == nullptr ? "upper" : nullptr;
+    const auto empty = [&] { return extent[0] == 0 || extent[1] == 0 || extent[2] == 0; };
+    int coef_free = 0;  // a 1-d coefficient
+    if (int rc = line_front(
+            LINE_CHECKS, LINE_ROLES, out, rhs, nfields, missing, extent, axis, elem_size,
+            [&]() -> int {
+                const bool unknown = (flags & ~(GT4MI_LINE_PERIODIC | GT4MI_LINE_DRY_RUN)) != 0;
+                return unknown ? fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: unknown bits in flags 0x%x", (unsigned)flags) : GT4MI_OK;
+            },
+            [&]() -> int {
+                if (!periodic || empty() || extent[axis] >= 3) return GT4MI_OK;
+                return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: a periodic line needs at least 3 points, the extent along axis %d is %lld",
+                            axis, (long long)extent[axis]);
+            },
+            &coef_free))
+        return rc;
     const int64_t n = extent[axis];
-    const bool empty = extent[0] == 0 || extent[1] == 0 || extent[2] == 0;
-    if (periodic && !empty && n < 3)
-        return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: a periodic line needs at least 3 points, the extent along axis %d is %lld", axis,
-                    (long long)n);
-    const int coef_free = 7 & ~(1 << axis);  // a 1-d coefficient: stride 0 along the two other axes, no shape to check there
     const gt4mi_field* const coef[3] = {lower, diag, upper};
     const char* const coef_names[3] = {"lower", "diag", "upper"};
-    for (int k = 0; k < nfields; ++k) {
-        if (int rc = check_box_field(LINE_CHECKS, "out", k, out[k], extent, elem_size, true)) return rc;
-        if (int rc = check_box_field(LINE_CHECKS, "rhs", k, rhs[k], extent, elem_size, false)) return rc;
-    }
     for (int c = 0; c < 3; ++c)
         if (int rc = check_box_field(LINE_CHECKS, coef_names[c], 0, *coef[c], extent, elem_size, false, coef_free)) return rc;
-    if (empty) return GT4MI_OK;
+    if (empty()) return GT4MI_OK;
     const NamedSpan shared[3] = {{"lower", box_span(*lower, extent, elem_size)}, {"diag", box_span(*diag, extent, elem_size)},
                                  {"upper", box_span(*upper, extent, elem_size)}};
     if (int rc = check_pairs_disjoint("line_solve", out, rhs, nfields, extent, extent, elem_size, elem_size, nullptr, shared, 3, &LINE_ROLES))
         return rc;
-    int lane_axis = 0;
-    const int which = line_plan(out, rhs, nfields, coef, 3, extent, axis, elem_size, &lane_axis);
-    const int order[3] = {axis, lane_axis, 3 - axis - lane_axis};
-    const int64_t lines = extent[order[1]] * extent[order[2]];
-    if (lines > (int64_t)INT32_MAX - LINE_BLOCK) return fail(GT4MI_ERR_UNSUPPORTED, "line_solve: too many lines for one launch");
+    LinePlan plan(axis, elem_size);
+    for (int k = 0; k < nfields; ++k) plan.strict(out[k]), plan.strict(rhs[k]);
+    for (int c = 0; c < 3; ++c) plan.loose(coef[c]);
+    LineGrid g;
+    if (int rc = line_grid("line_solve", plan, extent, LINE_BLOCK, &g)) return rc;
     // a workspace row: the lines rounded up to whole 256-byte segments
-    const int64_t pitch = cdiv(lines, 256 / elem_size) * (256 / elem_size);
+    const int64_t pitch = cdiv(g.lines, 256 / elem_size) * (256 / elem_size);
     const int64_t needed = pitch * n * elem_size * (periodic ? 2 : 1);
     if (workspace_needed) *workspace_needed = needed;
-    if (path) *path = which;
+    if (path) *path = g.path;
     if (!dry && workspace == nullptr) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_solve: workspace is null");
     if (workspace != nullptr) {
         if (workspace_bytes < needed)
@@ -543,15 +451,22 @@ inline int line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfield
     if (launches) *launches = (int)cdiv(nfields, PAIR_MAX_FIELDS);
     if (dry) return GT4MI_OK;
     LineArgs a{};
-    a.lo = shared_field(*lower, elem_size, order), a.di = shared_field(*diag, elem_size, order), a.up = shared_field(*upper, elem_size, order);
+    a.lo = shared_field(*lower, elem_size, g.order), a.di = shared_field(*diag, elem_size, g.order), a.up = shared_field(*upper, elem_size, g.order);
     a.cp = static_cast<char*>(workspace);
     a.q = a.cp + (periodic ? pitch * n * elem_size : 0);
     a.pitch = pitch;
-    a.n = (int)n, a.na = (int)extent[order[1]], a.nb = (int)extent[order[2]], a.periodic = periodic;
+    a.n = (int)n, a.na = g.na, a.nb = g.nb, a.periodic = periodic;
     // (a later launch of the call forms cp and q again, in the same workspace and to the same bits: launches are stream-ordered)
     int next = 0;
-    while (next_pair_batch(a, out, rhs, &next, nfields, elem_size, order)) {
-        with_item_type(elem_size, [&](auto t) { line_launch<decltype(t)>(a, which, stream); });
+    while (next_pair_batch(a, out, rhs, &next, nfields, elem_size, g.order)) {
+        with_item_type(elem_size, [&](auto t) {
+            using T = decltype(t);
+            with_pair_entries(a.nf, [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                line_launch(g.path, g.lines, LINE_BLOCK, line_solve_tile_kernel<T, NF>, line_solve_march_kernel<T, NF, LINE_AHEAD>,
+                            line_solve_march_kernel<T, NF, 1>, a, stream);
+            });
+        });
         GT4MI_HIP_CHECK(hipGetLastError());
     }
     return GT4MI_OK;

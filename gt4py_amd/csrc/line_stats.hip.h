@@ -28,12 +28,12 @@
 // No float atomics, no ticket, flag or spin, no workgroup waits for another, no scratch, and no address or loop bound depends on
 // field data: every loop counts to n, G or the items of a tile, which the host has checked against every field's shape.
 //
-// THREE PATHS, chosen by the host from the strides (reported as GT4MI_LINE_STATS_PATH_*), THE SAME ADDITIONS:
+// THREE PATHS, chosen by the host from the strides (line_geometry.hip.h: LinePlan; reported as GT4MI_LINE_STATS_PATH_*), THE SAME ADDITIONS:
 //   LANES  an axis OTHER than the line axis has unit stride in every field of the call (0 is allowed in an `other`): lanes run
 //          along it, a thread marches over the at most G items of its pair, every step a coalesced row segment; the loads of
 //          STATS_BATCH groups of 4 steps are issued before their adds.  On I-contiguous storage: axis J and K.
 //   TILES  the LINE axis has unit stride: a workgroup IS one wave and takes 64 lines of ONE segment; tiles of 64 lines x one
-//          128-byte run go through LDS with line_solve.hip.h's transposition and padded pitch (LineTile, line_tile_move: item
+//          128-byte run go through LDS with line_geometry.hip.h's transposition and padded pitch (LineTile, line_tile_move: item
 //          loads, so any origin alignment works, and a run that ends inside a tile is masked), global access coalesced along the
 //          line; the lane adds its run from LDS in m order.  `a` and `b` each have a tile; the tiles are private to the wave and
 //          the barriers are wave barriers.  On I-contiguous storage: axis I.
@@ -43,7 +43,7 @@
 #pragma once
 
 #include "field_stats.hip.h"
-#include "line_solve.hip.h"
+#include "line_geometry.hip.h"
 
 namespace gt4mi {
 
@@ -213,13 +213,11 @@ line_stats_tile_kernel(const LineStatsArgs g) {
     __shared__ T ta[LINE_TILE_LINES][L::PITCH];
     __shared__ T tb[SECOND ? LINE_TILE_LINES : 1][L::PITCH];
     const LineStatsEntry f = line_stats_entry(g);
-    const int lane = (int)threadIdx.x;
     const unsigned waves = (unsigned)((g.lines + LINE_TILE_LINES - 1) / LINE_TILE_LINES);  // per segment
     const int s = (int)(blockIdx.x / waves);
-    const int64_t w = (int64_t)(blockIdx.x - (unsigned)s * waves) * LINE_TILE_LINES + lane;
-    const bool ok = w < g.lines;
-    const int64_t mine = ok ? w : 0;  // (a lane without a line computes on line 0's addresses and neither loads nor stores)
-    const int64_t y = mine / g.nx, x = mine - y * g.nx;
+    const LineLane l = line_lane(LINE_TILE_LINES, blockIdx.x - (unsigned)s * waves, g.nx, g.lines);
+    const bool ok = l.ok;
+    const int64_t w = l.line, x = l.ia(), y = l.ib();
     const int m0 = s * LINE_STATS_SEGMENT;
     const int rest = g.n - m0;
     const int count = rest < LINE_STATS_SEGMENT ? rest : LINE_STATS_SEGMENT;
@@ -278,30 +276,6 @@ line_stats_finish_kernel(const double* __restrict__ partials, double* __restrict
     line_stats_store_row(result, blockIdx.z, slot, line_stats_section_index(w, nx, ny, swap), lines, n, x);
 }
 
-// The path of a call and its lane axis: `unit[ax]` = every field of the call has unit item stride along ax (an `other` may also
-// be broadcast along an axis that is not the line axis).
-inline int line_stats_plan(const gt4mi_field* fields, const gt4mi_field* others, int nfields, const int64_t domain[3], int axis,
-                           int elem_size, int* lane_axis) {
-    const int other0 = axis == 0 ? 1 : 0, other1 = axis == 2 ? 1 : 2;
-    bool unit[3];
-    for (int ax = 0; ax < 3; ++ax) {
-        unit[ax] = true;
-        for (int k = 0; k < nfields; ++k) {
-            if (fields[k].stride[ax] != elem_size) unit[ax] = false;
-            if (const gt4mi_field* o = stats_other(others, k))
-                if (o->stride[ax] != elem_size && !(ax != axis && o->stride[ax] == 0)) unit[ax] = false;
-        }
-    }
-    *lane_axis = other0;
-    if (unit[axis] && domain[axis] > 1) return GT4MI_LINE_STATS_PATH_TILES;
-    for (int ax : {other0, other1})
-        if (unit[ax] && domain[ax] > 1) {
-            *lane_axis = ax;
-            return GT4MI_LINE_STATS_PATH_LANES;
-        }
-    return GT4MI_LINE_STATS_PATH_ITEMS;
-}
-
 template <typename T>
 inline void line_stats_launch(const LineStatsArgs& a, int nf, int path, bool second, hipStream_t stream) {
     if (path == GT4MI_LINE_STATS_PATH_TILES) {
@@ -334,8 +308,10 @@ inline int line_stats(const gt4mi_field* fields, const gt4mi_field* others, int 
     if (flags & ~GT4MI_STATS_DRY_RUN) return fail(GT4MI_ERR_INVALID_ARGUMENT, "line_stats: unknown bits in flags 0x%x", (unsigned)flags);
     const bool dry = (flags & GT4MI_STATS_DRY_RUN) != 0;
     if (int rc = stats_check_fields("line_stats", fields, others, nfields, domain, elem_size)) return rc;
+    LinePlan plan(axis, elem_size);  // (every entry of the call, not only those of the first launch)
+    for (int k = 0; k < nfields; ++k) plan.strict(fields[k]), plan.loose(stats_other(others, k));
     int lane_axis = 0;
-    const int which = line_stats_plan(fields, others, nfields, domain, axis, elem_size, &lane_axis);
+    const int which = plan.path(domain, &lane_axis);
     const int order[3] = {axis, lane_axis, 3 - axis - lane_axis};
     const int64_t n = domain[axis], lines = domain[order[1]] * domain[order[2]], segments = cdiv(n, LINE_STATS_SEGMENT);
     if ((double)lines * (double)segments > (double)LINE_STATS_MAX_PAIRS)

@@ -39,7 +39,7 @@ from typing import Any, List, NamedTuple, Optional, Sequence, Union
 import numpy as np
 
 from . import _lib
-from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _box_of, _halo4, _shape3, refuse_host_arrays
+from ._bound import AXES, FLAGS, FLOATS, STREAM, Bound, Out, _box_of, _halo4, _shape3, refuse_host_arrays
 from .storage.device_array import DeviceArray, as_device_array
 
 
@@ -195,6 +195,34 @@ class _StatsCall(Bound):
         if rc != _lib.OK:
             _lib.check(self._entry, rc)
 
+    _name = ""      # the class's name in get()'s refusal
+    _record = None  # what get() makes of one entry's block of the result
+
+    def get(self) -> list:
+        """Synchronise the stream of the last call and return its results, one record per entry (``RuntimeError`` before the
+        first call)."""
+        if self._stream is None:
+            raise RuntimeError(f"{self._name}.get: the object has not been called yet")
+        self._stream.synchronize()
+        return [self._record(block) for block in self.result.tensor.cpu().numpy()]
+
+    def _row(self, what: str, name: str, entry: int) -> DeviceArray:
+        """Row ``name`` of entry ``entry`` of ``result``, as the device holds it; ``what``: what the caller calls it."""
+        if name not in PROFILE_ROWS:
+            raise ValueError(f"no {what} {name!r}: the rows are {', '.join(PROFILE_ROWS)}")
+        entry = int(entry)
+        if not 0 <= entry < self._n:
+            raise IndexError(f"entry {entry} of {self._n}")
+        return self.result[entry, PROFILE_ROWS.index(name)]
+
+
+def _one_shot(frozen_class, fields, other, **kwargs):
+    """The synchronous form of a frozen call: ``other`` for every field or one per field, freeze, call, get."""
+    others = list(other) if isinstance(other, (list, tuple)) else None if other is None else [other] * len(fields)
+    frozen = frozen_class(fields, others=others, **kwargs)
+    frozen()
+    return frozen.get()
+
 
 class FieldStats(_StatsCall):
     """The frozen form of :func:`field_stats`: arguments are checked (through the library's dry run), the descriptors, the
@@ -207,17 +235,10 @@ class FieldStats(_StatsCall):
     The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it refuses to run once one of
     them has died.  (An exporter that cannot be weakly referenced is held instead, so its memory stays valid.)"""
 
-    _who, _entry = "field_stats", "gt4mi_field_stats"
+    _who, _entry, _name, _record = "field_stats", "gt4mi_field_stats", "FieldStats", Stats.from_row
 
     def _result_block(self) -> tuple:
         return (_lib.STATS_SLOTS,)
-
-    def get(self) -> List[Stats]:
-        """Synchronise the stream of the last call and return its results (``RuntimeError`` before the first call)."""
-        if self._stream is None:
-            raise RuntimeError("FieldStats.get: the object has not been called yet")
-        self._stream.synchronize()
-        return [Stats.from_row(row) for row in self.result.tensor.cpu().numpy()]
 
 
 def field_stats(*fields, other=None, origin: Optional[Sequence[int]] = None, domain: Optional[Sequence[int]] = None,
@@ -237,13 +258,7 @@ def field_stats(*fields, other=None, origin: Optional[Sequence[int]] = None, dom
 
     Raises ``ValueError`` / ``TypeError`` (with the library's message) before any GPU work.  In a time loop build a
     :class:`FieldStats` once instead and read it a step late."""
-    if isinstance(other, (list, tuple)):
-        others = list(other)
-    else:
-        others = None if other is None else [other] * len(fields)
-    frozen = FieldStats(fields, others=others, origin=origin, domain=domain, halo=halo)
-    frozen()
-    return frozen.get()
+    return _one_shot(FieldStats, fields, other, origin=origin, domain=domain, halo=halo)
 
 
 # ---- per level: K profiles ---------------------------------------------------------------------------------------------------
@@ -251,24 +266,66 @@ def field_stats(*fields, other=None, origin: Optional[Sequence[int]] = None, dom
 PROFILE_ROWS = Stats._fields + ("mean",)
 
 
-class Profile:
+class _Rows:
+    """What :class:`Profile` and :class:`Lines` share: the nine rows as numpy arrays of ``_ndim`` dimensions and one shape
+    (``_shape_error``: the refusal of anything else), the :class:`Stats` of one index, what follows from the rows, and equality."""
+
+    __slots__ = PROFILE_ROWS
+    _ndim, _shape_error = 0, ""
+
+    def __init__(self, count, nonfinite, sum, sum_abs, sum_sq, min, max, dot, mean=None):  # noqa: A002 - the names of Stats
+        nd = self._ndim
+        self.count, self.nonfinite = (np.array(v, dtype=np.int64, ndmin=nd) for v in (count, nonfinite))
+        self.sum, self.sum_abs, self.sum_sq, self.min, self.max, self.dot = (
+            np.array(v, dtype=np.float64, ndmin=nd) for v in (sum, sum_abs, sum_sq, min, max, dot))
+        if mean is None:
+            with np.errstate(all="ignore"):
+                mean = self.sum / self.count  # one IEEE division per level or line, as the kernel's
+        self.mean = np.array(mean, dtype=np.float64, ndmin=nd)
+        if any(getattr(self, name).shape != self.count.shape or self.count.ndim != nd for name in PROFILE_ROWS):
+            raise ValueError(self._shape_error)
+
+    def __getitem__(self, index) -> Stats:
+        if self._ndim == 2:
+            a, b = index
+            index = int(a), int(b)
+        else:
+            index = int(index)
+        return Stats(int(self.count[index]), int(self.nonfinite[index]), float(self.sum[index]), float(self.sum_abs[index]),
+                     float(self.sum_sq[index]), float(self.min[index]), float(self.max[index]), float(self.dot[index]))
+
+    @property
+    def norm2(self) -> np.ndarray:
+        with np.errstate(all="ignore"):
+            return np.sqrt(self.sum_sq)
+
+    @property
+    def max_abs(self) -> np.ndarray:
+        """max |x| per level or line (the CFL limit differs from one to the next); NaN where it holds a NaN."""
+        return np.maximum(np.abs(self.min), np.abs(self.max))  # (numpy's maximum hands a NaN on)
+
+    @property
+    def all_finite(self) -> np.ndarray:
+        return self.nonfinite == 0
+
+    def __eq__(self, other) -> bool:
+        """Bit for bit, NaN equal to NaN."""
+        if not isinstance(other, type(self)):
+            return NotImplemented
+        return all(np.array_equal(getattr(self, n), getattr(other, n), equal_nan=True)
+                   and np.array_equal(np.signbit(getattr(self, n)), np.signbit(getattr(other, n))) for n in PROFILE_ROWS)
+
+    __hash__ = None  # type: ignore[assignment]
+
+
+class Profile(_Rows):
     """The per-level values of one entry: numpy arrays of length ``nk`` for ``count``, ``nonfinite`` (int64), ``sum``,
     ``sum_abs``, ``sum_sq``, ``min``, ``max``, ``dot`` and ``mean`` (float64), with the NaN and signed-zero rules of
     :class:`Stats` level by level.  ``profile[k]`` is the :class:`Stats` of level ``k``; index 0 is the first level of the
     domain (``origin[2]``)."""
 
-    __slots__ = PROFILE_ROWS
-
-    def __init__(self, count, nonfinite, sum, sum_abs, sum_sq, min, max, dot, mean=None):  # noqa: A002 - the names of Stats
-        self.count, self.nonfinite = (np.array(v, dtype=np.int64, ndmin=1) for v in (count, nonfinite))
-        self.sum, self.sum_abs, self.sum_sq, self.min, self.max, self.dot = (
-            np.array(v, dtype=np.float64, ndmin=1) for v in (sum, sum_abs, sum_sq, min, max, dot))
-        if mean is None:
-            with np.errstate(all="ignore"):
-                mean = self.sum / self.count  # one IEEE division per level, as the kernel's
-        self.mean = np.array(mean, dtype=np.float64, ndmin=1)
-        if any(getattr(self, name).shape != self.count.shape or self.count.ndim != 1 for name in PROFILE_ROWS):
-            raise ValueError("the rows of a Profile are one-dimensional and of one length")
+    __slots__ = ()
+    _ndim, _shape_error = 1, "the rows of a Profile are one-dimensional and of one length"
 
     @classmethod
     def from_rows(cls, rows) -> "Profile":
@@ -285,25 +342,6 @@ class Profile:
     def __len__(self) -> int:
         return self.nk
 
-    def __getitem__(self, k: int) -> Stats:
-        k = int(k)
-        return Stats(int(self.count[k]), int(self.nonfinite[k]), float(self.sum[k]), float(self.sum_abs[k]), float(self.sum_sq[k]),
-                     float(self.min[k]), float(self.max[k]), float(self.dot[k]))
-
-    @property
-    def norm2(self) -> np.ndarray:
-        with np.errstate(all="ignore"):
-            return np.sqrt(self.sum_sq)
-
-    @property
-    def max_abs(self) -> np.ndarray:
-        """max |x| per level (the vertical CFL limit differs from level to level); NaN where the level holds a NaN."""
-        return np.maximum(np.abs(self.min), np.abs(self.max))  # (numpy's maximum hands a NaN on)
-
-    @property
-    def all_finite(self) -> np.ndarray:
-        return self.nonfinite == 0
-
     @property
     def first_nonfinite(self) -> Optional[int]:
         """The lowest level index with a NaN or +-Inf item, or ``None``."""
@@ -314,15 +352,6 @@ class Profile:
         """The levels joined left to right as :func:`merge` does: exact counts and extremes, sums added in level order.  NOT
         the bits of :func:`field_stats` over the whole domain, whose additions are ordered by the whole domain."""
         return merge([self[k] for k in range(self.nk)])
-
-    def __eq__(self, other) -> bool:
-        """Bit for bit, NaN equal to NaN."""
-        if not isinstance(other, Profile):
-            return NotImplemented
-        return all(np.array_equal(getattr(self, n), getattr(other, n), equal_nan=True)
-                   and np.array_equal(np.signbit(getattr(self, n)), np.signbit(getattr(other, n))) for n in PROFILE_ROWS)
-
-    __hash__ = None  # type: ignore[assignment]
 
     def __repr__(self) -> str:
         return f"Profile(nk={self.nk}, first_nonfinite={self.first_nonfinite})"
@@ -360,7 +389,7 @@ class LevelStats(_StatsCall):
     The object holds raw pointers and weak references to the CALLER's objects, as :class:`FieldStats` does: it refuses to run
     once one of them has died."""
 
-    _who, _entry = "level_stats", "gt4mi_level_stats"
+    _who, _entry, _name, _record = "level_stats", "gt4mi_level_stats", "LevelStats", Profile.from_rows
 
     def _result_block(self) -> tuple:
         return (_lib.LEVEL_STATS_ROWS, self.domain[2])
@@ -373,19 +402,7 @@ class LevelStats(_StatsCall):
         """The contiguous ``(nk,)`` device view of one row of ``result``: ``name`` is a field of :class:`Stats` or ``"mean"``.
         It holds what the LAST call left there, in stream order: pass it to a stencil as ``Field[K, np.float64]`` on the
         stream of that call and no synchronisation is needed."""
-        if name not in PROFILE_ROWS:
-            raise ValueError(f"no profile {name!r}: the rows are {', '.join(PROFILE_ROWS)}")
-        entry = int(entry)
-        if not 0 <= entry < self._n:
-            raise IndexError(f"entry {entry} of {self._n}")
-        return self.result[entry, PROFILE_ROWS.index(name)]
-
-    def get(self) -> List[Profile]:
-        """Synchronise the stream of the last call and return its results (``RuntimeError`` before the first call)."""
-        if self._stream is None:
-            raise RuntimeError("LevelStats.get: the object has not been called yet")
-        self._stream.synchronize()
-        return [Profile.from_rows(block) for block in self.result.tensor.cpu().numpy()]
+        return self._row("profile", name, entry)
 
 
 def level_stats(*fields, other: Union[None, Any, Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
@@ -394,25 +411,18 @@ def level_stats(*fields, other: Union[None, Any, Sequence[Any]] = None, origin: 
     with the arguments of :func:`field_stats`.  One pass (per 8 fields) and one finishing launch on the current stream, then a
     synchronisation of that stream.  With an IJ area weight as ``other``, ``dot`` is the area-weighted level sum.  In a time
     loop build a :class:`LevelStats` once instead and read it a step late."""
-    if isinstance(other, (list, tuple)):
-        others = list(other)
-    else:
-        others = None if other is None else [other] * len(fields)
-    frozen = LevelStats(fields, others=others, origin=origin, domain=domain, halo=halo)
-    frozen()
-    return frozen.get()
+    return _one_shot(LevelStats, fields, other, origin=origin, domain=domain, halo=halo)
 
 
 # ---- along a line: zonal means and their kin ------------------------------------------------------------------------------------
 #: the rows of a LineStats result block, in order: those of a LevelStats block
 LINE_ROWS = PROFILE_ROWS
-_AXES = {"I": 0, "J": 1, "K": 2}
 
 
 def _axis_index(axis) -> int:
     """``"I"``, ``"J"``, ``"K"`` or 0, 1, 2 as 0, 1, 2."""
-    if isinstance(axis, str) and axis.upper() in _AXES:
-        return _AXES[axis.upper()]
+    if isinstance(axis, str) and axis.upper() in AXES:
+        return AXES[axis.upper()]
     if not isinstance(axis, bool) and isinstance(axis, (int, np.integer)) and 0 <= int(axis) <= 2:
         return int(axis)
     raise ValueError(f"axis must be 'I', 'J', 'K' or 0, 1, 2, not {axis!r}")
@@ -427,24 +437,14 @@ def _np_maximum(a, b):
     return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a > b, a, np.where(b > a, b, np.where(np.signbit(a), b, a))))
 
 
-class Lines:
+class Lines(_Rows):
     """The per-line values of one entry: numpy arrays of shape ``(nA, nB)`` -- A < B the two axes other than the line axis, so
     ``[j, k]`` for lines along I -- for ``count``, ``nonfinite`` (int64), ``sum``, ``sum_abs``, ``sum_sq``, ``min``, ``max``,
     ``dot`` and ``mean`` (float64), with the NaN and signed-zero rules of :class:`Stats` line by line.  ``lines[a, b]`` is the
     :class:`Stats` of one line; index 0 is the first line of the domain."""
 
-    __slots__ = LINE_ROWS
-
-    def __init__(self, count, nonfinite, sum, sum_abs, sum_sq, min, max, dot, mean=None):  # noqa: A002 - the names of Stats
-        self.count, self.nonfinite = (np.array(v, dtype=np.int64, ndmin=2) for v in (count, nonfinite))
-        self.sum, self.sum_abs, self.sum_sq, self.min, self.max, self.dot = (
-            np.array(v, dtype=np.float64, ndmin=2) for v in (sum, sum_abs, sum_sq, min, max, dot))
-        if mean is None:
-            with np.errstate(all="ignore"):
-                mean = self.sum / self.count  # one IEEE division per line, as the kernel's
-        self.mean = np.array(mean, dtype=np.float64, ndmin=2)
-        if any(getattr(self, name).shape != self.count.shape or self.count.ndim != 2 for name in LINE_ROWS):
-            raise ValueError("the rows of a Lines record are two-dimensional and of one shape")
+    __slots__ = ()
+    _ndim, _shape_error = 2, "the rows of a Lines record are two-dimensional and of one shape"
 
     @classmethod
     def from_rows(cls, rows) -> "Lines":
@@ -459,39 +459,11 @@ class Lines:
     def shape(self) -> tuple:
         return self.count.shape
 
-    def __getitem__(self, index) -> Stats:
-        a, b = (int(i) for i in index)
-        return Stats(int(self.count[a, b]), int(self.nonfinite[a, b]), float(self.sum[a, b]), float(self.sum_abs[a, b]),
-                     float(self.sum_sq[a, b]), float(self.min[a, b]), float(self.max[a, b]), float(self.dot[a, b]))
-
-    @property
-    def norm2(self) -> np.ndarray:
-        with np.errstate(all="ignore"):
-            return np.sqrt(self.sum_sq)
-
-    @property
-    def max_abs(self) -> np.ndarray:
-        """max |x| per line (the CFL limit along a line); NaN where the line holds a NaN."""
-        return np.maximum(np.abs(self.min), np.abs(self.max))  # (numpy's maximum hands a NaN on)
-
-    @property
-    def all_finite(self) -> np.ndarray:
-        return self.nonfinite == 0
-
     @property
     def first_nonfinite(self) -> Optional[tuple]:
         """``(a, b)`` of the first line with a NaN or +-Inf item -- lowest ``b``, then lowest ``a`` -- or ``None``."""
         bad = np.flatnonzero(self.nonfinite.T)
         return None if not bad.size else (int(bad[0] % self.shape[0]), int(bad[0] // self.shape[0]))
-
-    def __eq__(self, other) -> bool:
-        """Bit for bit, NaN equal to NaN."""
-        if not isinstance(other, Lines):
-            return NotImplemented
-        return all(np.array_equal(getattr(self, n), getattr(other, n), equal_nan=True)
-                   and np.array_equal(np.signbit(getattr(self, n)), np.signbit(getattr(other, n))) for n in LINE_ROWS)
-
-    __hash__ = None  # type: ignore[assignment]
 
     def __repr__(self) -> str:
         return f"Lines(shape={self.shape}, first_nonfinite={self.first_nonfinite})"
@@ -537,7 +509,7 @@ class LineStats(_StatsCall):
     whatever the axis, the layout or the other lines are.  The object holds raw pointers and weak references to the CALLER's
     objects, as :class:`FieldStats` does: it refuses to run once one of them has died."""
 
-    _who, _entry = "line_stats", "gt4mi_line_stats"
+    _who, _entry, _name, _record = "line_stats", "gt4mi_line_stats", "LineStats", Lines.from_rows
 
     def __init__(self, fields: Sequence[Any], *, axis, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
                  domain: Optional[Sequence[int]] = None, halo=0):
@@ -561,19 +533,7 @@ class LineStats(_StatsCall):
         :class:`Stats` or ``"mean"``.  It holds what the LAST call left there, in stream order: pass it to a stencil as
         ``Field[JK, np.float64]`` (axis I), ``Field[IK, ...]`` (axis J) or ``Field[IJ, ...]`` (axis K) on the stream of that call
         and no synchronisation is needed."""
-        if name not in LINE_ROWS:
-            raise ValueError(f"no section {name!r}: the rows are {', '.join(LINE_ROWS)}")
-        entry = int(entry)
-        if not 0 <= entry < self._n:
-            raise IndexError(f"entry {entry} of {self._n}")
-        return self.result[entry, LINE_ROWS.index(name)].transpose()
-
-    def get(self) -> List[Lines]:
-        """Synchronise the stream of the last call and return its results (``RuntimeError`` before the first call)."""
-        if self._stream is None:
-            raise RuntimeError("LineStats.get: the object has not been called yet")
-        self._stream.synchronize()
-        return [Lines.from_rows(block) for block in self.result.tensor.cpu().numpy()]
+        return self._row("section", name, entry).transpose()
 
 
 def line_stats(*fields, axis, other: Union[None, Any, Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
@@ -583,10 +543,4 @@ def line_stats(*fields, axis, other: Union[None, Any, Sequence[Any]] = None, ori
     one finishing launch on the current stream, then a synchronisation of that stream.  With an IJ area weight as ``other``,
     ``dot`` is the area-weighted sum along the line.  In a time loop build a :class:`LineStats` once instead and read it a step
     late."""
-    if isinstance(other, (list, tuple)):
-        others = list(other)
-    else:
-        others = None if other is None else [other] * len(fields)
-    frozen = LineStats(fields, axis=axis, others=others, origin=origin, domain=domain, halo=halo)
-    frozen()
-    return frozen.get()
+    return _one_shot(LineStats, fields, other, axis=axis, origin=origin, domain=domain, halo=halo)

@@ -27,8 +27,7 @@ import ctypes
 from typing import Optional, Sequence
 
 from . import _lib
-from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _common_domain, _origin3, _pair_lists, field_table
-from .linesolve import AXES, _coefficient
+from ._bound import FLAGS, STREAM, Bound, Out, _coefficient, _line_pairs, field_table
 
 OPS = {"sum": _lib.SCAN_SUM, "max": _lib.SCAN_MAX, "min": _lib.SCAN_MIN}
 PATHS = {_lib.SCAN_PATH_LANES: "lanes", _lib.SCAN_PATH_TILES: "tiles", _lib.SCAN_PATH_ITEMS: "items"}
@@ -55,45 +54,18 @@ class LineScan(Bound):
     def __init__(self, dst, src, *, axis: str = "I", op: str = "sum", exclusive: bool = False, reverse: bool = False, weight=None,
                  wide: bool = False, halo=0, origin: Optional[Sequence[int]] = None):
         shared = () if weight is None else (weight,)
-        dsts, srcs, d_arrays, s_arrays, w_arrays, self._halo = _pair_lists("scan_lines", dst, src, halo, shared=shared)
-        if axis not in AXES:
-            raise ValueError(f"axis must be one of {sorted(AXES)}, not {axis!r}")
-        if op not in OPS:
-            raise ValueError(f"op must be one of {sorted(OPS)}, not {op!r}")
-        if weight is not None and op != "sum":
-            raise ValueError(f"a weight goes with op='sum' only, not with op={op!r}")
+
+        def names() -> None:
+            if op not in OPS:
+                raise ValueError(f"op must be one of {sorted(OPS)}, not {op!r}")
+            if weight is not None and op != "sum":
+                raise ValueError(f"a weight goes with op='sum' only, not with op={op!r}")
+
+        #: ``extent``: the IJK box that is scanned (the domain grown by the halo in I and J); ``n``, ``lines``: its lines' length and number
+        (dsts, srcs, d_arrays, s_arrays, w_arrays, self._halo, self.origin, self.domain, self.extent, self.n, self.lines, ax,
+         start) = _line_pairs("scan_lines", dst, src, axis, halo, origin, shared=shared, names=("weight",),
+                              sharing="the fields and the weight", own_checks=names)
         self.axis, self.op, self.exclusive, self.reverse, self.wide = axis, op, bool(exclusive), bool(reverse), bool(wide)
-        ax = AXES[axis]
-        for a in d_arrays + s_arrays:
-            if a.ndim != 3:
-                raise ValueError(f"scan_lines takes IJK fields, not a field of {a.ndim} dimension(s)")
-        for a in w_arrays:
-            if a.ndim not in (1, 3):
-                raise ValueError(f"weight must be an IJK field or a 1-d array along {axis}, not a field of {a.ndim} dimension(s)")
-        dtype = d_arrays[0].dtype
-        for a in d_arrays + s_arrays + w_arrays:
-            if a.dtype != dtype:
-                raise TypeError(f"the fields and the weight of one call share a dtype: {dtype} and {a.dtype} differ")
-        if dtype not in FLOATS:
-            raise TypeError(f"scan_lines takes float32 or float64 fields, not {dtype}")
-        lo_i, hi_i, lo_j, hi_j = self._halo
-        self.origin = origin = _origin3(origin, self._halo)
-        # the common compute domain, as in LineSolve: along the line axis the arrays must agree, a line is never cut short silently
-        full = [a for a in d_arrays + s_arrays + w_arrays if a.ndim == 3]
-        self.domain = domain = _common_domain(full, self._halo, origin, full, least_k=1)
-        for a in full:
-            have = a.shape[ax] - origin[ax] - (hi_i, hi_j, 0)[ax]
-            if have != domain[ax]:
-                raise ValueError(f"the fields of one call share their length along {axis}: {domain[ax]} and {have} differ")
-        #: the IJK box that is scanned: the domain grown by the halo in I and J
-        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j, domain[2])
-        #: the line length, and how many lines the box holds
-        self.n = self.extent[ax]
-        self.lines = self.extent[(ax + 1) % 3] * self.extent[(ax + 2) % 3]
-        for a in w_arrays:
-            if a.ndim == 1 and a.shape[0] != self.n:
-                raise ValueError(f"weight has {a.shape[0]} items, a line of {self.n} points along {axis} needs {self.n}")
-        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
         self._n = len(d_arrays)
         self._dst, self._src = field_table(d_arrays, start), field_table(s_arrays, start)
         self._weight = _coefficient(w_arrays[0], ax, start) if w_arrays else None

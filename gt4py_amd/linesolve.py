@@ -32,20 +32,11 @@ import ctypes
 from typing import Optional, Sequence
 
 from . import _lib
-from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _common_domain, _origin3, _pair_lists, field_table, refuse_host_arrays
+from ._bound import AXES, FLAGS, STREAM, Bound, Out, _coefficient, _line_pairs, field_table, refuse_host_arrays  # noqa: F401 - AXES is public here
 from .storage.device_array import DeviceArray
 
-AXES = {"I": 0, "J": 1, "K": 2}
 PATHS = {_lib.LINE_PATH_LANES: "lanes", _lib.LINE_PATH_TILES: "tiles", _lib.LINE_PATH_ITEMS: "items"}
 COEFFICIENTS = ("lower", "diag", "upper")
-
-
-def _coefficient(a: DeviceArray, axis: int, start) -> "_lib.Field":
-    if a.ndim == 1:  # n items along the line axis: every line reads the same ones
-        shape, strides, origin = [1, 1, 1], [0, 0, 0], [0, 0, 0]
-        shape[axis], strides[axis] = a.shape[0], a.strides[0]
-        return _lib.Field.make(a.ptr, shape, strides, origin)
-    return _lib.Field.make(a.ptr, a.shape, a.strides, start)
 
 
 class LineSolve(Bound):
@@ -69,43 +60,11 @@ class LineSolve(Bound):
 
     def __init__(self, out, rhs, *, lower, diag, upper, axis: str = "I", periodic: bool = False, halo=0,
                  origin: Optional[Sequence[int]] = None):
-        outs, rhss, o_arrays, r_arrays, c_arrays, self._halo = _pair_lists("solve_lines", out, rhs, halo, shared=(lower, diag, upper),
-                                                                               roles=("out field(s)", "rhs field(s)"))
-        if axis not in AXES:
-            raise ValueError(f"axis must be one of {sorted(AXES)}, not {axis!r}")
         self.axis, self.periodic = axis, bool(periodic)
-        ax = AXES[axis]
-        for a in o_arrays + r_arrays:
-            if a.ndim != 3:
-                raise ValueError(f"solve_lines takes IJK fields, not a field of {a.ndim} dimension(s)")
-        for name, a in zip(COEFFICIENTS, c_arrays):
-            if a.ndim not in (1, 3):
-                raise ValueError(f"{name} must be an IJK field or a 1-d array along {axis}, not a field of {a.ndim} dimension(s)")
-        dtype = o_arrays[0].dtype
-        for a in o_arrays + r_arrays + c_arrays:
-            if a.dtype != dtype:
-                raise TypeError(f"the fields and coefficients of one call share a dtype: {dtype} and {a.dtype} differ")
-        if dtype not in FLOATS:
-            raise TypeError(f"solve_lines takes float32 or float64 fields, not {dtype}")
-        lo_i, hi_i, lo_j, hi_j = self._halo
-        self.origin = origin = _origin3(origin, self._halo)
-        # the common compute domain: what every IJK array has left behind its origin and in front of its high ghost cells; along
-        # the line axis the arrays must agree, a line is never cut short silently
-        full = [a for a in o_arrays + r_arrays + c_arrays if a.ndim == 3]
-        self.domain = domain = _common_domain(full, self._halo, origin, full, least_k=1)
-        for a in full:
-            have = a.shape[ax] - origin[ax] - (hi_i, hi_j, 0)[ax]
-            if have != domain[ax]:
-                raise ValueError(f"the fields of one call share their length along {axis}: {domain[ax]} and {have} differ")
-        #: the IJK box that is solved: the domain grown by the halo in I and J
-        self.extent = (domain[0] + lo_i + hi_i, domain[1] + lo_j + hi_j, domain[2])
-        #: the line length, and how many lines the box holds
-        self.n = self.extent[ax]
-        self.lines = self.extent[(ax + 1) % 3] * self.extent[(ax + 2) % 3]
-        for name, a in zip(COEFFICIENTS, c_arrays):
-            if a.ndim == 1 and a.shape[0] != self.n:
-                raise ValueError(f"{name} has {a.shape[0]} items, a line of {self.n} points along {axis} needs {self.n}")
-        start = (origin[0] - lo_i, origin[1] - lo_j, origin[2])
+        #: ``extent``: the IJK box that is solved (the domain grown by the halo in I and J); ``n``, ``lines``: its lines' length and number
+        (outs, rhss, o_arrays, r_arrays, c_arrays, self._halo, self.origin, self.domain, self.extent, self.n, self.lines, ax,
+         start) = _line_pairs("solve_lines", out, rhs, axis, halo, origin, shared=(lower, diag, upper), names=COEFFICIENTS,
+                              sharing="the fields and coefficients", roles=("out field(s)", "rhs field(s)"))
         self._n = len(o_arrays)
         self._out, self._rhs = field_table(o_arrays, start), field_table(r_arrays, start)
         self._coefficients = tuple(_coefficient(a, ax, start) for a in c_arrays)

@@ -247,6 +247,15 @@ def test_the_path_follows_the_strides():
         for axis, path in enumerate((T, L, L)):
             got = _call(pair, w, domain=domain, axis=axis, elem_size=size, workspace=None, result=None)
             assert got[::4] == (0, path) and path == R.expected_path([layouts["I-contiguous"]], [weight], domain, axis, size), (axis, got)
+        # nine entries are two launches: only the NINTH has a second field, and that alone breaks unit stride -- the rule looks at
+        # every entry of the call, not at the eight of the first launch
+        nine = (_lib.Field * 9)(*[_field(0x10000 + 0x1000000 * n, shape, layouts["I-contiguous"], (0, 0, 0)) for n in range(9)])
+        others = (_lib.Field * 9)()  # (data == NULL: no second field)
+        others[8] = _field(0x40000000, shape, layouts["every other item"], (0, 0, 0))
+        for axis, alone in enumerate((T, L, L)):
+            assert _call(nine, nfields=9, domain=domain, axis=axis, elem_size=size, workspace=None, result=None)[::4] == (0, alone)
+            got = _call(nine, others, nfields=9, domain=domain, axis=axis, elem_size=size, workspace=None, result=None)
+            assert got[::4] == (0, X) and X == R.expected_path([layouts["I-contiguous"]] * 9, [layouts["every other item"]], domain, axis, size), (axis, got)
         # lines of one item, and one lane: extents of 1 select nothing
         one = ctypes.byref(_field(shape=shape, strides=layouts["I-contiguous"], origin=(0, 0, 0)))
         assert _call(one, domain=(1, nj, nk), axis=0, elem_size=size, workspace=None, result=None)[4] == X
