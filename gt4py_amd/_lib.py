@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_vertical_interp",
     "gt4mi_horizontal_interp",
     "gt4mi_departure_interp",
+    "gt4mi_point_sample",
     "gt4mi_overlap_table",
     "gt4mi_horizontal_remap",
     "gt4mi_line_solve",
@@ -127,6 +128,8 @@ VINTERP_DRY_RUN = 256
 # gt4mi_horizontal_interp, gt4mi_departure_interp: methods, flags
 INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC, INTERP_CUBIC_MONOTONE = 0, 1, 2, 3
 INTERP_RELATIVE, INTERP_DRY_RUN = 1, 256
+# gt4mi_point_sample (methods: INTERP_*): flags
+SAMPLE_FILL, SAMPLE_DRY_RUN = 2, 256
 # gt4mi_horizontal_remap: methods, flags
 HREMAP_PCM, HREMAP_PLM, HREMAP_DRY_RUN = 0, 1, 256
 # gt4mi_line_solve: paths, flags
@@ -263,6 +266,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_horizontal_interp.argtypes = [FP, FP, I, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_departure_interp.restype = I
     lib.gt4mi_departure_interp.argtypes = [FP, FP, I, FP, FP, FP, DOM, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_point_sample.restype = I
+    lib.gt4mi_point_sample.argtypes = [FP, FP, I, FP, FP, FP, ctypes.c_int64, DOM, DOM, I, I, I, I, D, P, ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_overlap_table.restype = I
     lib.gt4mi_overlap_table.argtypes = [P, I, P, I, P, P, P, P, P, P, I, ctypes.POINTER(ctypes.c_int)]
     AP = ctypes.POINTER(OverlapAxis)

@@ -88,6 +88,50 @@ __device__ __forceinline__ double departure_plane(const T* s, const int64_t si, 
     return interp_combine<N>(wj, rows);
 }
 
+// What a point needs along K for the methods that combine planes (all but nearest): levels b_k, b_k + 1 (each clamped) with the weights
+// 1 - t_k, t_k -- linear, the end intervals of the cubics, the corners -- and, for the cubics, the four levels and Lagrange weights;
+// `full`: the four-level formula applies, 1 <= b_k <= nk - 3, where b_k - 1 ... b_k + 2 are levels of the field.
+struct DepartureLevels {
+    int64_t kl[2], kc[4];
+    double wl[2], wc[4];
+    bool full;
+    double w_lo, w_hi;  // the weights of P(b_k) and P(b_k + 1) in the formula that applies
+};
+
+template <bool CUBIC>
+__device__ __forceinline__ void departure_levels(double xk, int k, bool relative, int nk, DepartureLevels& lv) {
+    bool nan_k;
+    interp_axis<GT4MI_INTERP_LINEAR>(xk, k, relative, 0, nk - 1, lv.kl, lv.wl, nan_k);
+    lv.kc[0] = lv.kc[1] = lv.kc[2] = lv.kc[3] = 0;
+    lv.wc[0] = lv.wc[1] = lv.wc[2] = lv.wc[3] = 0.0;
+    lv.full = false;
+    if constexpr (CUBIC) {
+        interp_axis<GT4MI_INTERP_CUBIC>(xk, k, relative, 0, nk - 1, lv.kc, lv.wc, nan_k);
+        lv.full = lv.kl[0] >= 1 && lv.kl[0] <= (int64_t)nk - 3;  // (x_k is clamped to [0, nk - 1]: kl[0] IS b_k)
+    }
+    lv.w_lo = lv.full ? lv.wc[1] : lv.wl[0], lv.w_hi = lv.full ? lv.wc[2] : lv.wl[1];
+}
+
+// One entry's value at a point (`s`: the entry's src at domain point (0, 0, 0), `st` its strides in items): the planes one after
+// another, each reduced to P and folded into the K combination, then the limiter over the eight corners.
+template <typename T, int METHOD>
+__device__ __forceinline__ double departure_value(const T* s, const int64_t (&st)[3], const int64_t (&ii)[InterpTaps<METHOD>::N],
+                                                  const int64_t (&jj)[InterpTaps<METHOD>::N], const double (&wi)[InterpTaps<METHOD>::N],
+                                                  const double (&wj)[InterpTaps<METHOD>::N], const DepartureLevels& lv) {
+    constexpr int N = InterpTaps<METHOD>::N;
+    constexpr bool CUBIC = METHOD == GT4MI_INTERP_CUBIC || METHOD == GT4MI_INTERP_CUBIC_MONOTONE;
+    constexpr bool MONOTONE = METHOD == GT4MI_INTERP_CUBIC_MONOTONE;
+    double mn = 0.0, mx = 0.0, out = 0.0;
+    if (CUBIC && lv.full) out = lv.wc[0] * departure_plane<T, N, MONOTONE>(s + lv.kc[0] * st[2], st[0], st[1], ii, jj, wi, wj, false, false, mn, mx);
+    const double p_lo = departure_plane<T, N, MONOTONE>(s + lv.kl[0] * st[2], st[0], st[1], ii, jj, wi, wj, true, true, mn, mx);
+    out = (CUBIC && lv.full) ? out + lv.w_lo * p_lo : lv.w_lo * p_lo;
+    const double p_hi = departure_plane<T, N, MONOTONE>(s + lv.kl[1] * st[2], st[0], st[1], ii, jj, wi, wj, true, false, mn, mx);
+    out = out + lv.w_hi * p_hi;
+    if (CUBIC && lv.full) out = out + lv.wc[3] * departure_plane<T, N, MONOTONE>(s + lv.kc[3] * st[2], st[0], st[1], ii, jj, wi, wj, false, false, mn, mx);
+    if constexpr (MONOTONE) out = out < mn ? mn : (out > mx ? mx : out);
+    return out;
+}
+
 // T: item type of the fields, P: of the positions, METHOD: GT4MI_INTERP_*, NF: entries the field loop is unrolled for (a.nf <= NF)
 template <typename T, typename P, int METHOD, int NF>
 __global__ void __launch_bounds__(DEPARTURE_TILE_I * DEPARTURE_TILE_J)
@@ -134,32 +178,13 @@ departure_interp_kernel(const DepartureArgs a) {
                 reinterpret_cast<U*>(e.dst)[k * e.d[2] + j * e.d[1] + i * e.d[0]] = nan ? InterpBits<T>::QNAN : v;
             }
         } else {
-            // levels b_k, b_k + 1 (each clamped) and the weights 1 - t_k, t_k: linear, the end intervals of the cubics, the corners
-            int64_t kl[2];
-            double wl[2];
-            bool nan_k;
-            interp_axis<GT4MI_INTERP_LINEAR>(xk, k, relative, 0, nk - 1, kl, wl, nan_k);
-            int64_t kc[4] = {0, 0, 0, 0};
-            double wc[4] = {0.0, 0.0, 0.0, 0.0};
-            bool full = false;  // the four-level formula: 1 <= b_k <= nk - 3, where b_k - 1 ... b_k + 2 are levels of the field
-            if constexpr (CUBIC) {
-                interp_axis<GT4MI_INTERP_CUBIC>(xk, k, relative, 0, nk - 1, kc, wc, nan_k);
-                full = kl[0] >= 1 && kl[0] <= (int64_t)nk - 3;  // (x_k is clamped to [0, nk - 1]: kl[0] IS b_k)
-            }
-            const double w_lo = full ? wc[1] : wl[0], w_hi = full ? wc[2] : wl[1];
+            DepartureLevels lv;
+            departure_levels<CUBIC>(xk, k, relative, nk, lv);
 #pragma unroll
             for (int n = 0; n < NF; ++n) {
                 if (n >= nf) continue;
                 const PairEntry& e = a.e[n];
-                const T* const s = reinterpret_cast<const T*>(e.src);
-                double mn = 0.0, mx = 0.0, out = 0.0;
-                if (CUBIC && full) out = wc[0] * departure_plane<T, N, MONOTONE>(s + kc[0] * e.s[2], e.s[0], e.s[1], ii, jj, wi, wj, false, false, mn, mx);
-                const double p_lo = departure_plane<T, N, MONOTONE>(s + kl[0] * e.s[2], e.s[0], e.s[1], ii, jj, wi, wj, true, true, mn, mx);
-                out = (CUBIC && full) ? out + w_lo * p_lo : w_lo * p_lo;
-                const double p_hi = departure_plane<T, N, MONOTONE>(s + kl[1] * e.s[2], e.s[0], e.s[1], ii, jj, wi, wj, true, false, mn, mx);
-                out = out + w_hi * p_hi;
-                if (CUBIC && full) out = out + wc[3] * departure_plane<T, N, MONOTONE>(s + kc[3] * e.s[2], e.s[0], e.s[1], ii, jj, wi, wj, false, false, mn, mx);
-                if constexpr (MONOTONE) out = out < mn ? mn : (out > mx ? mx : out);
+                const double out = departure_value<T, METHOD>(reinterpret_cast<const T*>(e.src), e.s, ii, jj, wi, wj, lv);
                 reinterpret_cast<T*>(e.dst)[k * e.d[2] + j * e.d[1] + i * e.d[0]] = (T)out;
             }
         }

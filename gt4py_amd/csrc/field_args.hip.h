@@ -1,10 +1,10 @@
 // Host-side helpers that the multi-field utility entries (halo_fill, field_stats, level_stats, field_copy, vertical_remap,
-// horizontal_interp, departure_interp, horizontal_remap, line_solve, line_scan) share: where a field's origin item is, which bytes its box touches, the per-field argument check and
+// horizontal_interp, departure_interp, point_sample, horizontal_remap, line_solve, line_scan) share: where a field's origin item is, which bytes its box touches, the per-field argument check and
 // the "no dst meets anything that is read" sweep.  What differs between the entries is DATA (BoxChecks, the arguments of
 // check_box_field): a new entry states its differences here instead of copying a check function.  The messages are part of
 // the library's behaviour (tests/test_refusal_messages.py holds them byte for byte).
 //
-// The PAIR entries (vertical_remap, horizontal_interp, departure_interp, horizontal_remap, line_solve, line_scan) take (written, read) pairs, up to
+// The PAIR entries (vertical_remap, horizontal_interp, departure_interp, point_sample, horizontal_remap, line_solve, line_scan) take (written, read) pairs, up to
 // PAIR_MAX_FIELDS per launch, the descriptors passed by value, the kernel instantiated for 1, 4 and 8 entries.  Such an entry states
 // its own args struct (`PairEntry e[PAIR_MAX_FIELDS]` first, then its SharedFields and scalars, and an `int nf`), its kernel
 // template with NF as a parameter, its scalar checks and its BoxChecks.  From here it takes the checks above, shared_field for what

@@ -19,6 +19,7 @@
 #include "vertical_interp.hip.h"
 #include "horizontal_interp.hip.h"
 #include "departure_interp.hip.h"
+#include "point_sample.hip.h"
 #include "horizontal_remap.hip.h"
 #include "line_solve.hip.h"
 #include "line_scan.hip.h"
@@ -258,6 +259,13 @@ int gt4mi_departure_interp(const gt4mi_field* dst, const gt4mi_field* src, int n
                            int elem_size, int pos_elem_size, int method, int flags, void* stream, int* launches) {
     return gt4mi::departure_interp(dst, src, nfields, pos_i, pos_j, pos_k, extent, reach, elem_size, pos_elem_size, method, flags,
                                    static_cast<hipStream_t>(stream), launches);
+}
+
+int gt4mi_point_sample(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* pos_i, const gt4mi_field* pos_j,
+                       const gt4mi_field* pos_k, int64_t npoints, const int64_t extent[3], const int64_t reach[4], int elem_size,
+                       int pos_elem_size, int method, int flags, double fill_value, void* stream, int* launches) {
+    return gt4mi::point_sample(dst, src, nfields, pos_i, pos_j, pos_k, npoints, extent, reach, elem_size, pos_elem_size, method, flags,
+                               fill_value, static_cast<hipStream_t>(stream), launches);
 }
 
 int gt4mi_overlap_table(const double* src_edges, int ns, const double* dst_edges, int nd, int32_t* ptr, int32_t* cell, double* w,

@@ -513,6 +513,52 @@ int gt4mi_departure_interp(const gt4mi_field* dst, const gt4mi_field* src, int n
                            const gt4mi_field* pos_j, const gt4mi_field* pos_k, const int64_t extent[3], const int64_t reach[4],
                            int elem_size, int pos_elem_size, int method, int flags, void* stream, int* launches);
 
+/* ---- sampling at a list of run-time positions (NEW entry, additive: the ABI version stays 8; no reference counterpart -- GTScript takes
+ * compile-time horizontal offsets only and writes fields of the shape it reads: a station's sounding, a cross-section along a path or
+ * the values along a track have another shape than the fields, and gt4py leaves them to fancy indexing on its numpy / cupy storages) ---
+ * Samples `nfields` fields at `npoints` positions that ONE set of position arrays holds, in ONE kernel launch per 8 fields, on `stream`,
+ * without synchronisation or allocation.  `extent` is the compute domain (ni, nj, nk) of every src[n], `reach` = {lo_i, hi_i, lo_j, hi_j}
+ * the ghost cells a gather may read as for gt4mi_horizontal_interp: the readable box of a src is the domain grown by the reach along I
+ * and J, over all levels; it must fit the array.
+ * Column mode (pos_k == NULL): for every point p < npoints and every level k < extent[2], dst[n] at (p, k) is the value of src[n] at
+ * level k and the horizontal position (pos_i[p], pos_j[p]): a sounding per point, a curtain per path.  THE ARITHMETIC IS THAT OF
+ * gt4mi_horizontal_interp in absolute mode, all of it: steps 1-4 per axis, the four methods GT4MI_INTERP_NEAREST / LINEAR / CUBIC /
+ * CUBIC_MONOTONE, the canonical quiet NaN at a NaN position for nearest, bit patterns moved for nearest.
+ * Point mode (pos_k != NULL): dst[n] at p is the value of src[n] at the 3-d position (pos_i[p], pos_j[p], pos_k[p]), by THE ARITHMETIC
+ * OF gt4mi_departure_interp in absolute mode, its K rule included: K has no ghost levels (pos_k is clamped to [0, nk - 1]) and the
+ * cubics use the linear formula over the two cubic plane values in the end intervals.  A physical vertical coordinate is not a level:
+ * convert it with gt4mi_vertical_interp first.  (csrc/point_sample.hip.h calls the device functions of the two interpolators, it
+ * restates nothing; tests/point_sample_ref.py restates the contract through tests/horizontal_interp_ref.py and
+ * tests/departure_interp_ref.py.)
+ * A dst[n] is a gt4mi_field whose axis 0 is the point and axis 1 the level: its box is (npoints, extent[2], 1) in column mode and
+ * (npoints, 1, 1) in point mode, any strides.  pos_i / pos_j / pos_k are 1-d: axis 0 is the point, the box is (npoints, 1, 1); their
+ * items are `pos_elem_size` 4 (float32) or 8 (float64) whatever `elem_size` (the fields', 4 or 8) is.  Positions are in index units of
+ * the compute domain: 0.0 is domain point 0 (the origin of src[n]) and level 0.  They are read at LAUNCH time, not at call time: a
+ * caller may rewrite the arrays between two calls with the same arguments (a moving platform, a trajectory).
+ * Flags: GT4MI_SAMPLE_FILL -- a point is FILLED if any of its position items satisfies p < xmin, p > xmax or p != p, with xmin = -lo and
+ * xmax = n - 1 + hi as doubles along I and J and, in point mode, xmin = 0 and xmax = nk - 1 along K (a point exactly at xmin or xmax is
+ * not filled, +-inf is); a filled point receives `fill_value`, rounded once to the item type, in every field and every level; every
+ * other point receives exactly the bits it receives without the flag.  Without the flag the behaviour is the interpolators': positions
+ * are clamped to the readable box and a NaN position gives NaN.  GT4MI_SAMPLE_DRY_RUN -- the checks run, *launches is set and no device
+ * is touched.
+ * Consequences: a weight of zero still multiplies (0 * inf = NaN at an integer position next to an infinity); -0.0 may come back as
+ * +0.0; no address depends on data beyond the clamped integers (a filled point reads at its clamped position and drops what it read);
+ * the bits of a sample do not depend on layout, strides or alignment, on the number of fields in the call or its position among
+ * them, on the number or order of the points, or on the device; they are the bits gt4mi_horizontal_interp (column mode) or
+ * gt4mi_departure_interp (point mode) writes for a point with the same position items.  Periodic wrap is not part of the kernel: fill
+ * the ghost cells with gt4mi_halo_fill first.
+ * Refusals: null pointers (pos_k excepted), nfields < 1, npoints < 0, an unknown method or flag, a negative reach
+ * (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a misaligned field (GT4MI_ERR_UNSUPPORTED); a box that does not fit
+ * its field -- for a src the readable box -- (GT4MI_ERR_OUT_OF_BOUNDS); the bytes of a dst box (first to last item) meeting those of any
+ * src readable box, of a position array or of another dst box (GT4MI_ERR_UNSUPPORTED); a dst stride of 0 on an extent above 1
+ * (GT4MI_ERR_INVALID_ARGUMENT).  No byte outside the dst boxes changes.  npoints == 0 or an extent with a zero entry is GT4MI_OK,
+ * nothing enqueued.  Every check runs before the first launch; a refused call enqueues nothing.  *launches (may be NULL) = the kernels
+ * the call enqueues: ceil(nfields / 8).  Methods are those of gt4mi_horizontal_interp. */
+enum { GT4MI_SAMPLE_FILL = 2, GT4MI_SAMPLE_DRY_RUN = 256 };
+int gt4mi_point_sample(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* pos_i, const gt4mi_field* pos_j,
+                       const gt4mi_field* pos_k, int64_t npoints, const int64_t extent[3], const int64_t reach[4], int elem_size,
+                       int pos_elem_size, int method, int flags, double fill_value, void* stream, int* launches);
+
 /* ---- conservative horizontal remapping between rectilinear grids (NEW entries, additive: the ABI version stays 8; no reference
  * counterpart -- a GTScript destination point (i, j) reads sources at compile-time constant offsets from (i, j) only: not 2*i, not a
  * run-time range of source cells, not a source field of another horizontal shape) ---------------------------------------------------
