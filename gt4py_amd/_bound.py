@@ -1,5 +1,5 @@
 """What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
-``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``departure.DepartureInterp``, ``sampling.Sample``, ``linesolve.LineSolve``, ``linescan.LineScan``) share on the Python side: turning a refusal of the library into an
+``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``departure.DepartureInterp``, ``sampling.Sample``, ``linesolve.LineSolve``, ``linescan.LineScan``, ``linefind.LineFind``) share on the Python side: turning a refusal of the library into an
 exception, normalising halo / origin / domain / field lists, the native field tables, the dry run, and binding a checked call to
 the caller's objects.
 
@@ -155,7 +155,7 @@ def _float_pairs(who: str, dst, src, halo, method, methods, *, shared, names: Se
     return dsts, srcs, d_arrays, s_arrays, x_arrays, halo4
 
 
-#: the line axes of ``solve_lines``, ``scan_lines`` and (with 0, 1, 2 and lower case as well) ``line_stats``
+#: the line axes of ``solve_lines``, ``scan_lines`` and (with 0, 1, 2 and lower case as well) ``line_stats`` and ``find_lines``
 AXES = {"I": 0, "J": 1, "K": 2}
 
 

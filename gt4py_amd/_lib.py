@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_horizontal_remap",
     "gt4mi_line_solve",
     "gt4mi_line_scan",
+    "gt4mi_line_find",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -139,6 +140,11 @@ LINE_PERIODIC, LINE_DRY_RUN = 1, 256
 SCAN_SUM, SCAN_MAX, SCAN_MIN = 0, 1, 2
 SCAN_PATH_LANES, SCAN_PATH_TILES, SCAN_PATH_ITEMS = 0, 1, 2
 SCAN_EXCLUSIVE, SCAN_REVERSE, SCAN_WIDE, SCAN_DRY_RUN = 1, 2, 4, 256
+# gt4mi_line_find (paths: LINE_PATH_*): modes, directions, rows of a result block, flags
+FIND_CROSSING, FIND_ARGMAX, FIND_ARGMIN = 0, 1, 2
+FIND_ANY, FIND_RISING, FIND_FALLING = 0, 1, 2
+FIND_POSITION, FIND_COORD, FIND_EXTRA, FIND_ROWS = 0, 1, 2, 3
+FIND_REVERSE, FIND_DRY_RUN = 1, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -278,6 +284,9 @@ def _declare(lib: ctypes.CDLL) -> None:
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_line_scan.restype = I
     lib.gt4mi_line_scan.argtypes = [FP, FP, I, FP, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_line_find.restype = I
+    lib.gt4mi_line_find.argtypes = [FP, I, FP, DOM, I, I, I, I, ctypes.POINTER(D), D, P, I, P, ctypes.POINTER(ctypes.c_int),
+                                    ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

@@ -23,6 +23,7 @@
 #include "horizontal_remap.hip.h"
 #include "line_solve.hip.h"
 #include "line_scan.hip.h"
+#include "line_find.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -290,6 +291,13 @@ int gt4mi_line_solve(const gt4mi_field* out, const gt4mi_field* rhs, int nfields
 int gt4mi_line_scan(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* weight, const int64_t extent[3], int axis,
                     int elem_size, int op, int flags, void* stream, int* path, int* launches) {
     return gt4mi::line_scan(dst, src, nfields, weight, extent, axis, elem_size, op, flags, static_cast<hipStream_t>(stream), path, launches);
+}
+
+int gt4mi_line_find(const gt4mi_field* fields, int nfields, const gt4mi_field* coord, const int64_t extent[3], int axis, int elem_size,
+                    int what, int direction, const double* level, double missing, double* result, int flags, void* stream, int* path,
+                    int* launches) {
+    return gt4mi::line_find(fields, nfields, coord, extent, axis, elem_size, what, direction, level, missing, result, flags,
+                            static_cast<hipStream_t>(stream), path, launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

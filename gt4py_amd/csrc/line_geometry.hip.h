@@ -1,4 +1,4 @@
-// What the utilities that work along the lines of I, J or K (line_solve, line_stats, line_scan) share: the rule that picks one of
+// What the utilities that work along the lines of I, J or K (line_solve, line_stats, line_scan, line_find) share: the rule that picks one of
 // their three paths (TILES, LANES, ITEMS: each entry's header says what its kernels do there) from the strides, which line a lane
 // owns, the tiles of the TILES path, and -- for the two pair entries -- the front of the host entry, the grid of lines and the
 // launch.  A further line utility states its kernels and its own checks and takes its geometry from here.
@@ -19,7 +19,7 @@ constexpr int LINE_TILE_BYTES = 128; // TILES: the run along the line a tile cov
 static_assert(GT4MI_LINE_STATS_PATH_LANES == GT4MI_LINE_PATH_LANES && GT4MI_SCAN_PATH_LANES == GT4MI_LINE_PATH_LANES &&
               GT4MI_LINE_STATS_PATH_TILES == GT4MI_LINE_PATH_TILES && GT4MI_SCAN_PATH_TILES == GT4MI_LINE_PATH_TILES &&
               GT4MI_LINE_STATS_PATH_ITEMS == GT4MI_LINE_PATH_ITEMS && GT4MI_SCAN_PATH_ITEMS == GT4MI_LINE_PATH_ITEMS,
-              "LinePlan's paths are reported as they are by all three entries");
+              "LinePlan's paths are reported as they are by all four entries (line_find reports GT4MI_LINE_PATH_* itself)");
 
 // ---- the path rule ------------------------------------------------------------------------------------------------------------
 // The path of a call and its lane axis.  The entry feeds every field of the call, one at a time: `strict` a field that must have

@@ -729,6 +729,53 @@ enum { GT4MI_SCAN_EXCLUSIVE = 1, GT4MI_SCAN_REVERSE = 2, GT4MI_SCAN_WIDE = 4, GT
 int gt4mi_line_scan(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const gt4mi_field* weight, const int64_t extent[3], int axis,
                     int elem_size, int op, int flags, void* stream, int* path, int* launches);
 
+/* ---- first-crossing and extremum search along I, J or K (NEW entry, additive: the ABI version stays 8; the reference has no search: its
+ * users write a FORWARD stencil with a carried flag -- one field per call, along K only -- or chain cupy passes: a compare, `argmax` of the
+ * mask, two gathers and the arithmetic, each with fresh arrays) --------------------------------------------------------------------------
+ * For every line along `axis` (0 = I, 1 = J, 2 = K) of the box [origin, origin + extent) and each of `nfields` fields, finds WHERE on the
+ * line something happens (`what`): where the line first crosses level[k] (GT4MI_FIND_CROSSING), or where its maximum / minimum lies
+ * (GT4MI_FIND_ARGMAX / GT4MI_FIND_ARGMIN), in ONE kernel launch per 8 fields, on `stream`, without synchronisation, allocation or
+ * workspace.  `elem_size` is 4 (float32) or 8 (float64) and is the item size of EVERY field and of the coord.  No field is written.
+ * `coord` (may be NULL) is the coordinate along the line (a height); it may have byte stride 0 along the two axes other than `axis`: a 1-d
+ * array of n items that every line shares broadcasts without a copy and is exempt from the shape check on those axes.  A field stride of
+ * 0 on an extent above 1 is GT4MI_ERR_INVALID_ARGUMENT.  `level` (GT4MI_FIND_CROSSING only, NULL otherwise) points to `nfields` doubles in
+ * HOST memory, read during the call and passed to the kernels by value; `missing` is what a line without a crossing gets.
+ * `result` holds nfields x 3 x nB x nA doubles, result[((k * 3 + row) * nB + b) * nA + a], A < B the two axes other than `axis` (the layout
+ * of gt4mi_line_stats): row GT4MI_FIND_POSITION, GT4MI_FIND_COORD, GT4MI_FIND_EXTRA (the value at an extremum, the number of crossings of
+ * a line).  It is aligned to 8 bytes and meets no field and not the coord.  No byte outside it is written.
+ * THE CONTRACT (csrc/line_find.hip.h states it again, tests/line_find_ref.py restates it in plain Python and in numpy).  All comparisons and
+ * arithmetic are IEEE float64 on the items converted exactly, one rounding per operation, no FMA.  n = extent[axis]; y[q] = x[q], with
+ * GT4MI_FIND_REVERSE x[n-1-q]: the line in scan order; zc[q] the coord's item at the same place; idx(q) = q, reverse n-1-q: positions stay
+ * in the forward index units of the box.
+ *   ARGMAX    the candidate starts as item 0; item q replaces it if the candidate is not a NaN and (y[q] is a NaN or y[q] > candidate).  So
+ *             the first NaN met wins and stays, the first of equal items stays (-0.0 == +0.0): numpy.argmax of y.  ARGMIN: the same with <.
+ *             position = double(idx(q*)) ;  coord = zc[q*], without a coord = position ;  value = double(y[q*]) (a NaN is a NaN; its
+ *             payload is not part of the contract)
+ *   CROSSING  pair q in [0, n-1) rises through L if y[q] < L && y[q+1] >= L and falls if y[q] > L && y[q+1] <= L; `direction` selects
+ *             GT4MI_FIND_RISING, GT4MI_FIND_FALLING or either (GT4MI_FIND_ANY), in scan order.  y[0] == L counts as found at q = 0 with
+ *             t = 0 for every direction: position = double(idx(0)), coord = zc[0].  A comparison with a NaN is false: a NaN item makes no
+ *             crossing, a NaN level finds nothing.  crossings = the number of selected pairs on the whole line, plus one if y[0] == L.
+ *             At the first found pair:  t = (L - y[q]) / (y[q+1] - y[q])   (the denominator is not zero by the condition)
+ *               position = double(q) + t, reverse double(n-1-q) - t ;  coord = zc[q] + t * (zc[q+1] - zc[q]), without a coord = position
+ *             A line with none: position = coord = missing, crossings = 0.  n = 1 has no pair: only y[0] == L finds something.
+ * Every loop counts to n, there is no early exit; no loop bound and no address depends on field data.  A line's three items depend on
+ * that line alone: not on layout, axis, path, the other fields of the call or the device.
+ * *path (may be NULL) = which kernel the strides of the call select, by the rule of gt4mi_line_solve with every field strict and the coord
+ * loose: GT4MI_LINE_PATH_LANES, GT4MI_LINE_PATH_TILES or GT4MI_LINE_PATH_ITEMS.  The result does not depend on the path.
+ * Refusals: null pointers, nfields < 1, an invalid extent, axis, `what` or `direction`, an unknown flag, a level or a direction with an
+ * extremum, no level with a crossing, a result that is null, misaligned or meets a field or the coord (GT4MI_ERR_INVALID_ARGUMENT); an item
+ * size other than 4 or 8, a misaligned field, more lines than one launch counts (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field
+ * (GT4MI_ERR_OUT_OF_BOUNDS).  An extent with a zero entry is GT4MI_OK, nothing enqueued.  Every check runs before the first launch; a
+ * refused call enqueues nothing.  With GT4MI_FIND_DRY_RUN the checks run, *path and *launches are set and no device is touched; `result`
+ * may then be NULL (a result that is passed is checked).  *launches (may be NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_FIND_CROSSING = 0, GT4MI_FIND_ARGMAX = 1, GT4MI_FIND_ARGMIN = 2 };
+enum { GT4MI_FIND_ANY = 0, GT4MI_FIND_RISING = 1, GT4MI_FIND_FALLING = 2 };
+enum { GT4MI_FIND_POSITION = 0, GT4MI_FIND_COORD = 1, GT4MI_FIND_EXTRA = 2, GT4MI_FIND_ROWS = 3 };
+enum { GT4MI_FIND_REVERSE = 1, GT4MI_FIND_DRY_RUN = 256 };
+int gt4mi_line_find(const gt4mi_field* fields, int nfields, const gt4mi_field* coord, const int64_t extent[3], int axis, int elem_size,
+                    int what, int direction, const double* level, double missing, double* result, int flags, void* stream, int* path,
+                    int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
