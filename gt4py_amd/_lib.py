@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_line_solve",
     "gt4mi_line_scan",
     "gt4mi_line_find",
+    "gt4mi_field_histogram",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -145,6 +146,12 @@ FIND_CROSSING, FIND_ARGMAX, FIND_ARGMIN = 0, 1, 2
 FIND_ANY, FIND_RISING, FIND_FALLING = 0, 1, 2
 FIND_POSITION, FIND_COORD, FIND_EXTRA, FIND_ROWS = 0, 1, 2, 3
 FIND_REVERSE, FIND_DRY_RUN = 1, 256
+# gt4mi_field_histogram: limits, the counters behind the bins, rows, paths, flags
+HISTOGRAM_MAX_FIELDS, HISTOGRAM_MAX_BINS, HISTOGRAM_EXTRA = 8, 4096, 3
+HISTOGRAM_BELOW, HISTOGRAM_ABOVE, HISTOGRAM_NAN = 0, 1, 2
+HISTOGRAM_WHOLE, HISTOGRAM_BY_K = 0, 1
+HISTOGRAM_PATH_ROWS, HISTOGRAM_PATH_ITEMS = 0, 1
+HISTOGRAM_ACCUMULATE, HISTOGRAM_EDGES_PER_FIELD, HISTOGRAM_DRY_RUN = 1, 2, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -287,6 +294,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_line_find.restype = I
     lib.gt4mi_line_find.argtypes = [FP, I, FP, DOM, I, I, I, I, ctypes.POINTER(D), D, P, I, P, ctypes.POINTER(ctypes.c_int),
                                     ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_field_histogram.restype = I
+    lib.gt4mi_field_histogram.argtypes = [FP, I, DOM, I, I, P, ctypes.POINTER(D), I, P, I, P, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

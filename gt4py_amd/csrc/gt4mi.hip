@@ -24,6 +24,7 @@
 #include "line_solve.hip.h"
 #include "line_scan.hip.h"
 #include "line_find.hip.h"
+#include "field_histogram.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -298,6 +299,12 @@ int gt4mi_line_find(const gt4mi_field* fields, int nfields, const gt4mi_field* c
                     int* launches) {
     return gt4mi::line_find(fields, nfields, coord, extent, axis, elem_size, what, direction, level, missing, result, flags,
                             static_cast<hipStream_t>(stream), path, launches);
+}
+
+int gt4mi_field_histogram(const gt4mi_field* fields, int nfields, const int64_t extent[3], int elem_size, int nbins, const double* edges,
+                          const double* edges_host, int by, int64_t* result, int flags, void* stream, int* path, int* launches) {
+    return gt4mi::field_histogram(fields, nfields, extent, elem_size, nbins, edges, edges_host, by, result, flags,
+                                  static_cast<hipStream_t>(stream), path, launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

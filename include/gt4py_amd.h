@@ -776,6 +776,56 @@ int gt4mi_line_find(const gt4mi_field* fields, int nfields, const gt4mi_field* c
                     int what, int direction, const double* level, double missing, double* result, int flags, void* stream, int* path,
                     int* launches);
 
+/* ---- histograms of fields, whole box or per level (NEW entry, additive: the ABI version stays 8; the reference has no reduction and no
+ * result of another shape than its fields: its users call numpy / cupy `histogram`, or `searchsorted` + `bincount` per field and level, on
+ * storages that ARE numpy / cupy arrays) ------------------------------------------------------------------------------------------------
+ * Counts how the items of the box [origin, origin + extent) of each of `nfields` fields (1 .. GT4MI_HISTOGRAM_MAX_FIELDS) are distributed
+ * over `nbins` bins (1 .. GT4MI_HISTOGRAM_MAX_BINS) in ONE pass and ONE kernel launch, on `stream`, without synchronisation, allocation or
+ * workspace.  `elem_size` is 4 (float32) or 8 (float64) and is the item size of EVERY field.  No field is written; a field stride of 0 on an
+ * extent above 1 is GT4MI_ERR_INVALID_ARGUMENT.  `by` = GT4MI_HISTOGRAM_WHOLE: one row of counters per field for the whole box;
+ * GT4MI_HISTOGRAM_BY_K: one row per level k of the box (nrows = extent[2]).
+ * `edges` is a DEVICE pointer to float64 edges: nbins + 1 that every field shares, or with GT4MI_HISTOGRAM_EDGES_PER_FIELD nfields sets of
+ * nbins + 1.  `edges_host` points to the same values in HOST memory; the dry run, and only the dry run, reads it and checks the edges:
+ * finite and strictly increasing.  A call without the dry-run flag reads neither pointer on the host.
+ * `result` holds nfields x nrows x (nbins + 3) int64 counters, result[(k * nrows + row) * (nbins + 3) + slot]: the bins, then
+ * GT4MI_HISTOGRAM_BELOW, GT4MI_HISTOGRAM_ABOVE and GT4MI_HISTOGRAM_NAN at nbins + 0, 1, 2.  It is aligned to 8 bytes and meets no field and
+ * not the edges.  No byte outside it is written.  Without GT4MI_HISTOGRAM_ACCUMULATE it is zeroed first, in stream order, by a
+ * hipMemsetAsync on `stream`; with the flag the counts are ADDED to what it holds (a run-long PDF: one call per step into one result).
+ * THE CONTRACT (csrc/field_histogram.hip.h states it again, tests/histogram_ref.py restates it in plain Python and in numpy).  Every item x
+ * of a row's box is converted exactly to float64 and lands in exactly one counter of the row:
+ *   nan      if x != x
+ *   below    if x < e[0]          (-inf included)
+ *   above    if x > e[nbins]      (+inf included)
+ *   bin nbins - 1 if x == e[nbins]: the last bin is closed, as in numpy.histogram
+ *   else the bin b with e[b] <= x < e[b+1]; -0.0 == 0.0 as IEEE compares them
+ * For finite items in range the bins are numpy.histogram(x.astype(float64), bins=e)[0] bit for bit.  The counters of a row sum to the items
+ * of its box; items outside the box (pads, ghost cells) are never read.  The counters are integers, so the result is exact and the same bits
+ * for any layout, path, launch shape, device or decomposition: the sum of the histograms of the parts of a box IS the histogram of the box.
+ * The count depends on the edges alone: the kernel guesses the bin with one multiply, accepts the guess only if the comparisons against e[]
+ * hold and bisects otherwise; every search loop is bounded by a constant, so any content of the edges buffer terminates.
+ * *path (may be NULL) = GT4MI_HISTOGRAM_PATH_ROWS if every field has unit item stride along an axis of a row's box that is longer than 1 (it
+ * is walked in 16-byte lanes where the other strides allow), GT4MI_HISTOGRAM_PATH_ITEMS if any field goes item by item (per level a
+ * K-contiguous field does: a level holds no line of it).  The result does not depend on the path.
+ * GT4MI_HISTOGRAM_MAX_BINS is what the kernels' LDS plan carries: the float64 edges and one uint32 counter per slot of 4096 bins are 49 184
+ * bytes per workgroup (padded to 16), three workgroups per CU (csrc/field_histogram.hip.h).  A box holds at most 2^31 - 1 items, so that no on-chip
+ * counter can wrap.
+ * NOT OFFERED: weighted histograms (float sums would need a fixed order), rows along I or J, two-dimensional (joint) histograms, edges
+ * changed after the dry run has checked them.
+ * Refusals: null pointers, nfields outside 1 .. 8, nbins outside 1 .. GT4MI_HISTOGRAM_MAX_BINS, an invalid or empty extent, an invalid `by`,
+ * an unknown flag, edges that are not finite or not strictly increasing (the message names the first offending index), edges or a result
+ * that are misaligned, a result that meets a field or the edges (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a misaligned
+ * field, more than 2^31 - 1 items or 2^24 levels (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS).
+ * Every check runs before anything is enqueued.  With GT4MI_HISTOGRAM_DRY_RUN the checks run (those of the edges among them), *path and
+ * *launches are set and no device is touched; `edges` and `result` may then be NULL (what is passed is checked).  *launches (may be NULL) =
+ * the kernels the call enqueues: 1 (the zeroing is a memset, not a kernel). */
+enum { GT4MI_HISTOGRAM_MAX_FIELDS = 8, GT4MI_HISTOGRAM_MAX_BINS = 4096, GT4MI_HISTOGRAM_EXTRA = 3 };
+enum { GT4MI_HISTOGRAM_BELOW = 0, GT4MI_HISTOGRAM_ABOVE = 1, GT4MI_HISTOGRAM_NAN = 2 };
+enum { GT4MI_HISTOGRAM_WHOLE = 0, GT4MI_HISTOGRAM_BY_K = 1 };
+enum { GT4MI_HISTOGRAM_PATH_ROWS = 0, GT4MI_HISTOGRAM_PATH_ITEMS = 1 };
+enum { GT4MI_HISTOGRAM_ACCUMULATE = 1, GT4MI_HISTOGRAM_EDGES_PER_FIELD = 2, GT4MI_HISTOGRAM_DRY_RUN = 256 };
+int gt4mi_field_histogram(const gt4mi_field* fields, int nfields, const int64_t extent[3], int elem_size, int nbins, const double* edges,
+                          const double* edges_host, int by, int64_t* result, int flags, void* stream, int* path, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
