@@ -1,5 +1,5 @@
 """What the frozen utility calls (``boundary.HaloFill``, ``diagnostics.FieldStats`` / ``LevelStats``, ``transfer.FieldCopy``,
-``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``departure.DepartureInterp``, ``sampling.Sample``, ``linesolve.LineSolve``, ``linescan.LineScan``, ``linefind.LineFind``, ``histogram.Histogram``) share on the Python side: turning a refusal of the library into an
+``vertical.VerticalRemap`` / ``VerticalInterp``, ``horizontal.HorizontalInterp`` / ``HorizontalRemap``, ``departure.DepartureInterp``, ``sampling.Sample``, ``linesolve.LineSolve``, ``linescan.LineScan``, ``linefind.LineFind``, ``linefilter.LineFilter`` / ``LineSpectrum``, ``histogram.Histogram``) share on the Python side: turning a refusal of the library into an
 exception, normalising halo / origin / domain / field lists, the native field tables, the dry run, and binding a checked call to
 the caller's objects.
 

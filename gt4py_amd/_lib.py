@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "gt4mi_line_scan",
     "gt4mi_line_find",
     "gt4mi_field_histogram",
+    "gt4mi_line_filter",
     "gt4mi_comm_unique_id",
     "gt4mi_comm_create",
     "gt4mi_comm_create_local",
@@ -152,6 +153,8 @@ HISTOGRAM_BELOW, HISTOGRAM_ABOVE, HISTOGRAM_NAN = 0, 1, 2
 HISTOGRAM_WHOLE, HISTOGRAM_BY_K = 0, 1
 HISTOGRAM_PATH_ROWS, HISTOGRAM_PATH_ITEMS = 0, 1
 HISTOGRAM_ACCUMULATE, HISTOGRAM_EDGES_PER_FIELD, HISTOGRAM_DRY_RUN = 1, 2, 256
+# gt4mi_line_filter (paths: LINE_PATH_*): modes, the longest line, flags
+FILTER_APPLY, FILTER_SPECTRUM, FILTER_MAX_N, FILTER_DRY_RUN = 0, 1, 4096, 256
 # hdiff flags
 HDIFF_LIMITER, HDIFF_INTERNAL_F32, HDIFF_COEFF_F32 = 1, 2, 4
 
@@ -297,6 +300,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.gt4mi_field_histogram.restype = I
     lib.gt4mi_field_histogram.argtypes = [FP, I, DOM, I, I, P, ctypes.POINTER(D), I, P, I, P, ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int)]
+    lib.gt4mi_line_filter.restype = I
+    lib.gt4mi_line_filter.argtypes = [FP, FP, I, P, DOM, P, P, DOM, I, I, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.gt4mi_stream_copy.restype = I
     lib.gt4mi_stream_copy.argtypes = [P, P, ctypes.c_size_t, P]
     lib.gt4mi_memory_write_probe.restype = I

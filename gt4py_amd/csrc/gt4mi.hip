@@ -25,6 +25,7 @@
 #include "line_scan.hip.h"
 #include "line_find.hip.h"
 #include "field_histogram.hip.h"
+#include "line_filter.hip.h"
 #include "memprobe.hip.h"
 #include "hdiff.hip.h"
 #include "hdiff_ring.hip.h"
@@ -305,6 +306,13 @@ int gt4mi_field_histogram(const gt4mi_field* fields, int nfields, const int64_t 
                           const double* edges_host, int by, int64_t* result, int flags, void* stream, int* path, int* launches) {
     return gt4mi::field_histogram(fields, nfields, extent, elem_size, nbins, edges, edges_host, by, result, flags,
                                   static_cast<hipStream_t>(stream), path, launches);
+}
+
+int gt4mi_line_filter(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const double* response, const int64_t* response_extent,
+                      const double* twiddles, double* result, const int64_t extent[3], int axis, int elem_size, int mode, int flags,
+                      void* stream, int* path, int* launches) {
+    return gt4mi::line_filter(dst, src, nfields, response, response_extent, twiddles, result, extent, axis, elem_size, mode, flags,
+                              static_cast<hipStream_t>(stream), path, launches);
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

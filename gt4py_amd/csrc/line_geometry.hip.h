@@ -1,4 +1,4 @@
-// What the utilities that work along the lines of I, J or K (line_solve, line_stats, line_scan, line_find) share: the rule that picks one of
+// What the utilities that work along the lines of I, J or K (line_solve, line_stats, line_scan, line_find, line_filter) share: the rule that picks one of
 // their three paths (TILES, LANES, ITEMS: each entry's header says what its kernels do there) from the strides, which line a lane
 // owns, the tiles of the TILES path, and -- for the two pair entries -- the front of the host entry, the grid of lines and the
 // launch.  A further line utility states its kernels and its own checks and takes its geometry from here.

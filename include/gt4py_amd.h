@@ -826,6 +826,62 @@ enum { GT4MI_HISTOGRAM_ACCUMULATE = 1, GT4MI_HISTOGRAM_EDGES_PER_FIELD = 2, GT4M
 int gt4mi_field_histogram(const gt4mi_field* fields, int nfields, const int64_t extent[3], int elem_size, int nbins, const double* edges,
                           const double* edges_host, int by, int64_t* result, int flags, void* stream, int* path, int* launches);
 
+/* ---- Fourier filtering along periodic lines of I, J or K (NEW entry, additive: the ABI version stays 8; the reference has nothing in
+ * wavenumber space: a stencil reads its neighbours at compile-time offsets, a Fourier coefficient reads the whole line.  Its users leave
+ * for an FFT library: rfft, a multiply and irfft per field -- three launches and more, complex intermediates of the field's size, the
+ * order of the arithmetic whatever the library picks) ---------------------------------------------------------------------------------
+ * Every line along `axis` (0 = I, 1 = J, 2 = K) of the box [origin, origin + extent) is taken as periodic of length n = extent[axis], a
+ * power of two with 2 <= n <= 4096; nh = n / 2 + 1.  ONE kernel launch per 8 fields, on `stream`, without synchronisation, allocation
+ * or workspace.  `elem_size` is 4 (float32) or 8 (float64) and is the item size of EVERY field.  A, B are the two axes other than `axis`
+ * in IJK order, nA, nB the box's extents along them.
+ * `mode` = GT4MI_FILTER_APPLY: for each of `nfields` (dst, src) pairs the line of src is transformed, wavenumber m is multiplied by the real
+ * response[m] and the line is transformed back into dst.  `response` is a DEVICE pointer to response_extent[0] x response_extent[1] x nh
+ * float64, C-ordered; response_extent[0] is 1 or nA, response_extent[1] is 1 or nB: an extent of 1 broadcasts ({1, 1}: one response for
+ * every line; {nj, 1} on axis I: the polar filter, one response per latitude).  It is read when the kernel runs, never written, and its
+ * values are not checked.  dst[k] may BE src[k] -- the same first item and the same strides: in place.  Every other meeting of the
+ * bytes of a dst box with a src box, another dst box, the response or the twiddles is refused.  `result` is NULL.
+ * `mode` = GT4MI_FILTER_SPECTRUM: the forward transform of each of the `nfields` fields `src` alone.  `dst`, `response` and `response_extent`
+ * are NULL.  `result` holds nfields x 2 x nA x nB x nh float64, result[(((k * 2 + part) * nA + a) * nB + b) * nh + m], part 0 the real and
+ * part 1 the imaginary part of wavenumber m = 0 .. n/2: the same shape on every path.  It is aligned to 8 bytes and meets no field and
+ * not the twiddles.  No byte outside it is written.
+ * `twiddles` is a DEVICE pointer to n float64 that the CALLER has computed: wr[j] = cos(2 pi j / n) at [j] and wi[j] = -sin(2 pi j / n)
+ * at [n/2 + j] for j < n/2, with w[0] = (1, 0) and w[n/4] = (0, -1) set exactly.  The device never evaluates a sine or a cosine.
+ * THE ARITHMETIC IS PART OF THE CONTRACT (csrc/line_filter.hip.h states it again, tests/line_filter_ref.py restates it in plain Python and
+ * in numpy).  All of it is IEEE float64 on the items converted exactly, one rounding per operation, no FMA; one rounding to the fields'
+ * type on the store.  L = log2 n; x[p] = (item p of the line, +0.0).
+ *   FORWARD   radix-2 decimation in frequency, natural order in, bit-reversed order out.  For h = n/2, n/4, .. 1, for every block start
+ *             (a multiple of 2h) and j < h:  p = start + j, q = p + h, w = w[j * n / (2h)], a = x[p], b = x[q]:
+ *               u = a - b ;  a' = a + b ;  b'.re = wr * u.re - wi * u.im ;  b'.im = wr * u.im + wi * u.re
+ *   MULTIPLY  in place: the slot at p holds wavenumber m = bitrev_L(p); both parts are multiplied by response[min(m, n - m)].
+ *   INVERSE   radix-2 decimation in time, bit-reversed order in, natural order out, with conj(w).  For h = 1, 2, .. n/2, p, q, w, a, b
+ *             as above:  t.re = wr * b.re + wi * b.im ;  t.im = wr * b.im - wi * b.re ;  a' = a + t ;  b' = a - t
+ *             dst[p] = T(x[p].re * (1.0 / n)), the factor exact; the imaginary part is dropped.  No permutation is executed.
+ *   SPECTRUM  after FORWARD the slot at p is stored at m = bitrev_L(p) where m <= n/2.
+ * A kernel may fuse stages in registers only where every bit of the result stays the same, signed zeros included: the shipped one fuses
+ * up to three and leaves out nothing, no trivial twiddle and no zero imaginary part (1 * x - 0 * y is not x for every x and y).  A
+ * line's result depends on that line, its response row and n alone: not on layout, axis, path, the other fields and lines of the call or
+ * the device; a NaN or an infinity stays in its line.  Every loop bound and every address follows from n, the extents and the strides.
+ * *path (may be NULL) = which way the strides of the call select for the loads and stores, by the rule of gt4mi_line_solve with every
+ * field strict and the response loose (it counts as unit along `axis` and allows another axis only where it is broadcast along it):
+ * GT4MI_LINE_PATH_TILES (`axis` has unit stride in every field: lanes along the line, 16 bytes each where every line is aligned so),
+ * GT4MI_LINE_PATH_LANES (another axis has: a workgroup takes neighbouring lines along it, a load covers runs along that axis),
+ * GT4MI_LINE_PATH_ITEMS (anything else: item by item, correct and slow).  The bits do not depend on the path.
+ * NOT OFFERED: lengths that are not a power of two (mixed radix), lengths above 4096 (one line is all a workgroup's 64 KiB hold), a
+ * complex response, a line that is split over ranks.
+ * Refusals: null pointers, nfields < 1, an invalid extent, axis or mode, an unknown flag, a dst, response or result with the wrong mode,
+ * a response extent that is neither 1 nor the box's, a response, twiddles or result that is misaligned, a result that meets a field or
+ * the twiddles (GT4MI_ERR_INVALID_ARGUMENT); an item size other than 4 or 8, a line length that is not a power of two from 2 to 4096
+ * (the message names it), a misaligned field, a forbidden overlap, more lines than one launch counts (GT4MI_ERR_UNSUPPORTED); a box that
+ * does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS).  An extent with a zero entry along another axis is GT4MI_OK, nothing enqueued.  Every
+ * check runs before the first launch; a refused call enqueues nothing.  With GT4MI_FILTER_DRY_RUN the checks run, *path and *launches are
+ * set and no device is touched; `response`, `twiddles` and `result` may then be NULL (what is passed is checked).  *launches (may be
+ * NULL) = the kernels the call enqueues: ceil(nfields / 8). */
+enum { GT4MI_FILTER_APPLY = 0, GT4MI_FILTER_SPECTRUM = 1 };
+enum { GT4MI_FILTER_DRY_RUN = 256 };
+int gt4mi_line_filter(const gt4mi_field* dst, const gt4mi_field* src, int nfields, const double* response, const int64_t* response_extent,
+                      const double* twiddles, double* result, const int64_t extent[3], int axis, int elem_size, int mode, int flags,
+                      void* stream, int* path, int* launches);
+
 /* ---- multi-GPU: RCCL halo exchange driven from native code (NEW, no reference counterpart) --------
  * One process per GPU.  gt4mi_comm wraps an RCCL communicator created from a 128-byte unique id
  * (gt4mi_comm_unique_id on one rank, distributed by the host program, e.g. torch.distributed).
