@@ -3,17 +3,17 @@ every refusal (raised before any GPU work), and ``physical_sides``."""
 
 import ctypes
 import itertools
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
 import boundary_ref as R
+import entry_checks as E
+from entry_checks import INV, OOB, UNS, int64s
 from gt4py_amd import _lib, boundary
 from gt4py_amd.distributed.halo import Decomposition
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
+HOST = (8, 9, 3)  # the shape of a host field where a test states none
 SENTINEL = -12345.0
 
 
@@ -80,43 +80,24 @@ def test_sides_and_corner_rule_of_the_restatement():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_abi_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_halo_fill\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* fields", "int nfields", "const int64_t domain[3]", "const int64_t halo[4]", "int mode_i",
-                      "int mode_j", "int sides", "const void* value", "int elem_size", "void* stream", "int* launches"]
-    fn = _lib.load().gt4mi_halo_fill
-    i64p, c_int = ctypes.POINTER(ctypes.c_int64), ctypes.c_int
-    assert fn.restype is c_int
-    assert fn.argtypes == [ctypes.POINTER(_lib.Field), c_int, i64p, i64p, c_int, c_int, c_int, ctypes.c_void_p, c_int,
-                           ctypes.c_void_p, ctypes.POINTER(c_int)]
-    assert "gt4mi_halo_fill" in _lib.EXPORTED_SYMBOLS
     # the header says the entry has no reference counterpart, and the enums of header and binding agree
-    comment = text[: text.index("int gt4mi_halo_fill(")].rsplit("/* ----", 1)[1]
-    assert "no reference counterpart" in comment
-    for name in ("NONE", "PERIODIC", "ZERO_GRADIENT", "SYMMETRIC", "REFLECT", "CONSTANT", "I_LO", "I_HI", "J_LO", "J_HI",
-                 "ALL_SIDES", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_HALO_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"HALO_{name}") == value, name
+    E.check_binding("gt4mi_halo_fill",
+                    ["const gt4mi_field* fields", "int nfields", "const int64_t domain[3]", "const int64_t halo[4]", "int mode_i",
+                     "int mode_j", "int sides", "const void* value", "int elem_size", "void* stream", "int* launches"],
+                    prefix="HALO", constants=("NONE", "PERIODIC", "ZERO_GRADIENT", "SYMMETRIC", "REFLECT", "CONSTANT", "I_LO", "I_HI", "J_LO",
+                                              "J_HI", "ALL_SIDES", "DRY_RUN"),
+                    phrases=("no reference counterpart",))
     assert boundary.ALL == boundary.I_LO | boundary.I_HI | boundary.J_LO | boundary.J_HI == 15
 
 
 def _call(fields, nfields=1, domain=(4, 4, 2), halo=(1, 1, 1, 1), mode_i=_lib.HALO_PERIODIC, mode_j=_lib.HALO_PERIODIC,
           sides=_lib.HALO_ALL_SIDES, value=b"\0" * 8, elem_size=8):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
-    rc = lib.gt4mi_halo_fill(fields, nfields, _lib.domain3(domain) if domain is not None else None,
-                             (ctypes.c_int64 * 4)(*halo) if halo is not None else None, mode_i, mode_j, sides, value, elem_size, None,
-                             ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value
+    return E.call("gt4mi_halo_fill", fields, nfields, int64s(domain), int64s(halo), mode_i, mode_j, sides, value, elem_size, None, outs=(77,))
 
 
 def test_argument_errors_of_the_c_entry_without_a_gpu():
     """Every check runs before the first launch: these calls carry fake device addresses and never reach the GPU."""
     f = ctypes.byref(_lib.Field.make(0x10000, (6, 6, 2), (8, 48, 288), (1, 1, 0)))
-    INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
     rc, msg, launches = _call(None)
     assert rc == INV and b"null" in msg and launches == 0
     null_data = ctypes.byref(_lib.Field.make(0, (6, 6, 2), (8, 48, 288), (1, 1, 0)))
@@ -165,7 +146,7 @@ def test_argument_errors_of_the_c_entry_without_a_gpu():
     rc, msg, _ = _call(ctypes.byref(_lib.Field.make(0x10000, (6, 6, 2), (8, 52, 312), (1, 1, 0))))
     assert rc == UNS and b"multiple of the item size" in msg
     # the dry run counts launches: one per eight fields; nothing to do = none
-    many = (_lib.Field * 17)(*[_lib.Field.make(0x10000 * (n + 1), (6, 6, 2), (8, 48, 288), (1, 1, 0)) for n in range(17)])
+    many = E.table(_lib.Field.make(0x10000 * (n + 1), (6, 6, 2), (8, 48, 288), (1, 1, 0)) for n in range(17))
     dry = _lib.HALO_ALL_SIDES | _lib.HALO_DRY_RUN
     assert [_call(many, nfields=n, sides=dry)[2] for n in (1, 8, 9, 16, 17)] == [1, 1, 2, 2, 3]
     assert _call(many, nfields=8, sides=dry, mode_i=_lib.HALO_NONE, mode_j=_lib.HALO_NONE)[::2] == (0, 0)
@@ -181,25 +162,12 @@ def test_a_row_longer_than_an_int_is_refused_even_without_j_rows():
 
 
 def test_the_kernels_are_in_the_resource_log_and_use_no_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*halo_fill_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)",
-                         log.read_text(), re.S)
+    kernels = E.kernel_resources(r"halo_fill_kernel")
     assert len(kernels) == 4, kernels  # item sizes 1, 2, 4, 8
-    assert all(int(scratch) == 0 and int(lds) == 0 for _, scratch, lds in kernels), kernels
+    assert all(int(scratch) == 0 and int(lds) == 0 for _, scratch, _, lds in kernels), kernels
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 3), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 @pytest.mark.parametrize("kwargs, error, match", [
     (dict(halo=2, mode="bogus"), ValueError, "unknown boundary mode 'bogus'"),
     (dict(halo=2, mode=("periodic", "reflect", None)), ValueError, "mode_i, mode_j"),
@@ -223,9 +191,9 @@ def _host_field(shape=(8, 9, 3), dtype="float64"):
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
     with pytest.raises(error, match=match):
-        boundary.fill_halo(_host_field(), **kwargs)
+        boundary.fill_halo(E.host_field(HOST), **kwargs)
     with pytest.raises(error, match=match):
-        boundary.HaloFill([_host_field()], **kwargs)
+        boundary.HaloFill([E.host_field(HOST)], **kwargs)
 
 
 def test_python_refusals_about_the_fields_themselves():
@@ -238,21 +206,21 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         boundary.fill_halo(np.zeros((4, 4, 2)), halo=1, mode="periodic")
     with pytest.raises(ValueError, match="no I or no J axis"):
-        boundary.fill_halo(_host_field((8,)), halo=1, mode="periodic")
+        boundary.fill_halo(E.host_field((8,)), halo=1, mode="periodic")
     with pytest.raises(TypeError, match="share an item size"):
-        boundary.fill_halo(_host_field(), _host_field(dtype="float32"), halo=1, mode="periodic")
+        boundary.fill_halo(E.host_field(HOST), E.host_field(HOST, dtype="float32"), halo=1, mode="periodic")
     with pytest.raises(TypeError, match="share an item size"):
-        boundary.fill_halo(_host_field(dtype="int32"), _host_field(dtype="float32"), halo=1, mode="constant")
+        boundary.fill_halo(E.host_field(HOST, dtype="int32"), E.host_field(HOST, dtype="float32"), halo=1, mode="constant")
     with pytest.raises(ValueError, match="field 1: high width 1 along axis 0"):  # the second field is smaller
-        boundary.fill_halo(_host_field(), _host_field((7, 9, 3)), halo=1, mode="periodic")
+        boundary.fill_halo(E.host_field(HOST), E.host_field((7, 9, 3)), halo=1, mode="periodic")
 
 
 def test_defaults_of_origin_and_domain():
     with pytest.raises(TypeError, match="device fields"):
-        boundary.HaloFill([_host_field((8, 9))], halo=((1, 2), (0, 3)), mode=("reflect", "periodic"))  # Field[IJ]
+        boundary.HaloFill([E.host_field((8, 9))], halo=((1, 2), (0, 3)), mode=("reflect", "periodic"))  # Field[IJ]
     # (the object is not built for host memory; what it would have bound is checked through the library's messages)
     with pytest.raises(ValueError, match=r"high width 3 along axis J is larger than 2"):
-        boundary.HaloFill([_host_field((8, 5))], halo=((1, 2), (0, 3)), mode=("reflect", "periodic"))  # domain (5, 2, 1)
+        boundary.HaloFill([E.host_field((8, 5))], halo=((1, 2), (0, 3)), mode=("reflect", "periodic"))  # domain (5, 2, 1)
 
 
 # ---- physical_sides ----------------------------------------------------------------------------------------------------------

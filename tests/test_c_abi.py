@@ -10,6 +10,7 @@ import re
 
 import pytest
 
+import entry_checks as E
 from gt4py_amd import _lib
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -91,11 +92,7 @@ def test_no_shipped_hot_kernel_spills():
     The column kernels keep up to 104 levels of two fields in registers: one level too many, or the `#pragma unroll`ed
     level loop left rolled (LLVM's default unroll budget), and the register arrays silently become scratch memory --
     a 30 % slower kernel with identical results, which no parity test would notice."""
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    text = log.read_text()
-    kernels = re.findall(r"remark: Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)", text, re.S)
-    by_name = {name: (int(scratch), int(waves)) for name, scratch, waves in kernels}
+    by_name = {name: (scratch, waves) for name, scratch, waves, _ in E.kernel_resources(r"")}  # (every kernel)
     hot = {n: v for n, v in by_name.items() if any(k in n for k in ("lap5_strip_kernel", "hdiff_share_kernel", "hdiff_jmarch_kernel",
                                                                    "tridiag_pipe_kernel", "tridiag_kernel", "halo_copy_kernel",
                                                                    "lap5_step_kernel", "lap5_edge_kernel"))}

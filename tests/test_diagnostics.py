@@ -3,16 +3,16 @@ restatement of the documented order (tests/stats_ref.py) against exact arithmeti
 
 import ctypes
 import math
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import stats_ref as R
+from entry_checks import INV, OOB, UNS, int64s
 from gt4py_amd import _lib, diagnostics
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
+HOST = (8, 9, 3)  # the shape of a host field where a test states none
 U = 2.0 ** -53
 # domain -> (rows, rows per wave, tiles, tiles per finish leaf, finish leaves)
 SEVERAL_ROWS_PER_WAVE = {(5, 130, 130): (16900, 2, 2113, 17, 125), (3, 257, 129): (33153, 3, 2763, 22, 126)}
@@ -20,25 +20,15 @@ SEVERAL_ROWS_PER_WAVE = {(5, 130, 130): (16900, 2, 2113, 17, 125), (3, 257, 129)
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_abi_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_field_stats\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* fields", "const gt4mi_field* others", "int nfields", "const int64_t domain[3]",
-                      "int elem_size", "void* workspace", "int64_t workspace_bytes", "double* result", "int flags", "void* stream",
-                      "int64_t* workspace_needed", "int* launches"]
-    fn = _lib.load().gt4mi_field_stats
     FP, c_int, vp = ctypes.POINTER(_lib.Field), ctypes.c_int, ctypes.c_void_p
-    assert fn.restype is c_int
-    assert fn.argtypes == [FP, FP, c_int, ctypes.POINTER(ctypes.c_int64), c_int, vp, ctypes.c_int64, vp, c_int, vp,
-                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)]
-    assert "gt4mi_field_stats" in _lib.EXPORTED_SYMBOLS
-    comment = text[: text.index("int gt4mi_field_stats(")].rsplit("/* ----", 1)[1]
-    assert "no reference counterpart" in comment
-    for name in ("COUNT", "NONFINITE", "SUM", "SUM_ABS", "SUM_SQ", "MIN", "MAX", "DOT", "SLOTS", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_STATS_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"STATS_{name}") == value, name
+    E.check_binding("gt4mi_field_stats",
+                    ["const gt4mi_field* fields", "const gt4mi_field* others", "int nfields", "const int64_t domain[3]",
+                     "int elem_size", "void* workspace", "int64_t workspace_bytes", "double* result", "int flags", "void* stream",
+                     "int64_t* workspace_needed", "int* launches"],
+                    argtypes=[FP, FP, c_int, ctypes.POINTER(ctypes.c_int64), c_int, vp, ctypes.c_int64, vp, c_int, vp,
+                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)],
+                    prefix="STATS", constants=("COUNT", "NONFINITE", "SUM", "SUM_ABS", "SUM_SQ", "MIN", "MAX", "DOT", "SLOTS", "DRY_RUN"),
+                    phrases=("no reference counterpart",))
     assert diagnostics.Stats._fields == ("count", "nonfinite", "sum", "sum_abs", "sum_sq", "min", "max", "dot")
     assert (R.COUNT, R.NONFINITE, R.SUM, R.SUM_ABS, R.SUM_SQ, R.MIN, R.MAX, R.DOT) == tuple(range(8))
 
@@ -48,23 +38,20 @@ WORK, RESULT = 0x900000, 0xA00000
 NEEDED = 2 * 8 * 8  # domain (4, 4, 2): 8 rows, one per wave, 4 waves per tile: 2 tiles of 8 doubles
 
 
-def _field(ptr=FIELD[0], shape=FIELD[1], strides=FIELD[2], origin=FIELD[3]):
-    return _lib.Field.make(ptr, shape, strides, origin)
+def _field(ptr=FIELD[0], shape=FIELD[1], strides=FIELD[2], origin=FIELD[3]):  # (everything defaults to FIELD)
+    return E.field(ptr, shape, strides, origin)
 
 
 def _call(fields, others=None, nfields=1, domain=(4, 4, 2), elem_size=8, workspace=WORK, workspace_bytes=1 << 20, result=RESULT,
           flags=_lib.STATS_DRY_RUN):
     """Refusals are provoked WITHOUT the dry-run flag where they can be (a refused call enqueues nothing); a call that would
     pass every check carries the flag."""
-    lib = _lib.load()
-    needed, launches = ctypes.c_int64(-5), ctypes.c_int(77)
-    rc = lib.gt4mi_field_stats(fields, others, nfields, _lib.domain3(domain) if domain is not None else None, elem_size,
-                               workspace, workspace_bytes, result, flags, None, ctypes.byref(needed), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, needed.value
+    rc, msg, needed, launches = E.call("gt4mi_field_stats", fields, others, nfields, int64s(domain), elem_size, workspace, workspace_bytes, result,
+                                       flags, None, outs=(ctypes.c_int64(-5), 77))
+    return rc, msg, launches, needed
 
 
 def test_argument_errors_of_the_c_entry_without_a_gpu():
-    INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
     f = ctypes.byref(_field())
 
     def refused(status, needle, *args, **kwargs):
@@ -115,7 +102,7 @@ def test_argument_errors_of_the_c_entry_without_a_gpu():
 
 
 def test_dry_run_reports_workspace_and_launches():
-    many = (_lib.Field * 17)(*[_field(ptr=0x10000 * (n + 1)) for n in range(17)])
+    many = E.table(_field(ptr=0x10000 * (n + 1)) for n in range(17))
     for n, want in ((1, 2), (8, 2), (9, 3), (16, 3), (17, 4)):
         rc, msg, launches, needed = _call(many, nfields=n, workspace=None, result=None)  # asking for the size
         assert rc == 0 and launches == want and needed == n * NEEDED, (n, msg)
@@ -131,13 +118,10 @@ def test_dry_run_reports_workspace_and_launches():
 
 
 def test_the_kernels_are_in_the_resource_log_and_use_no_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*field_stats\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)",
-                         log.read_text(), re.S)
+    kernels = E.kernel_resources(r"field_stats")
     assert len(kernels) == 3, kernels  # float, double, finish
-    assert all(int(scratch) == 0 for _, scratch, _ in kernels), kernels
-    lds = {("finish" if "finish" in name else "main"): int(size) for name, _, size in kernels}
+    assert all(int(scratch) == 0 for _, scratch, _, _ in kernels), kernels
+    lds = {("finish" if "finish" in name else "main"): int(size) for name, _, _, size in kernels}
     assert lds == {"main": 4 * 8 * 8, "finish": 128 * 8 * 8}  # the per-workgroup combines only
 
 
@@ -260,15 +244,6 @@ def test_derived_values_of_a_record():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 3), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check; a call that passed them all is refused last."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def test_python_refusals_need_no_gpu():
     import torch
 
@@ -280,32 +255,32 @@ def test_python_refusals_need_no_gpu():
     with pytest.raises(TypeError):
         D.field_stats(np.zeros((4, 4, 2)))
     with pytest.raises(TypeError, match="float32 or float64 fields, not int32"):
-        D.field_stats(_host_field(dtype="int32"))
+        D.field_stats(E.host_field(HOST, dtype="int32"))
     with pytest.raises(TypeError, match="float32 or float64 fields, not bool"):
-        D.FieldStats([_host_field(dtype="bool")])
+        D.FieldStats([E.host_field(HOST, dtype="bool")])
     with pytest.raises(TypeError, match="share a dtype"):
-        D.field_stats(_host_field(), _host_field(dtype="float32"))
+        D.field_stats(E.host_field(HOST), E.host_field(HOST, dtype="float32"))
     with pytest.raises(TypeError, match="share a dtype"):
-        D.field_stats(_host_field(), other=_host_field(dtype="float32"))
+        D.field_stats(E.host_field(HOST), other=E.host_field(HOST, dtype="float32"))
     with pytest.raises(ValueError, match="one entry .* per field: 1 for 2 fields"):
-        D.FieldStats([_host_field(), _host_field()], others=[_host_field()])
+        D.FieldStats([E.host_field(HOST), E.host_field(HOST)], others=[E.host_field(HOST)])
     with pytest.raises(ValueError, match="IJ or IJK fields"):
-        D.field_stats(_host_field((8,)))
+        D.field_stats(E.host_field((8,)))
     with pytest.raises(ValueError, match="leave no domain"):
-        D.field_stats(_host_field(), halo=4)
+        D.field_stats(E.host_field(HOST), halo=4)
     with pytest.raises(TypeError, match="halo widths must be ints"):
-        D.field_stats(_host_field(), halo=((1, 1.5), (1, 1)))
+        D.field_stats(E.host_field(HOST), halo=((1, 1.5), (1, 1)))
     with pytest.raises(ValueError, match="field 0: origin 2 \\+ domain 7 along axis 0 is outside the array"):
-        D.field_stats(_host_field(), origin=(2, 0, 0), domain=(7, 9, 3))
+        D.field_stats(E.host_field(HOST), origin=(2, 0, 0), domain=(7, 9, 3))
     with pytest.raises(ValueError, match="field 1: origin 1 \\+ domain 6 along axis 0"):  # the second field is smaller
-        D.field_stats(_host_field(), _host_field((6, 9, 3)), halo=1)
+        D.field_stats(E.host_field(HOST), E.host_field((6, 9, 3)), halo=1)
     with pytest.raises(ValueError, match="other 0: origin 1 \\+ domain 7 along axis 1"):
-        D.field_stats(_host_field(), other=_host_field((8, 7, 3)), halo=1)
+        D.field_stats(E.host_field(HOST), other=E.host_field((8, 7, 3)), halo=1)
     with pytest.raises(ValueError, match="empty domain"):
-        D.field_stats(_host_field(), domain=(0, 3, 3))
+        D.field_stats(E.host_field(HOST), domain=(0, 3, 3))
     # all checks passed (an IJ weight against an IJK field among them): refused for being host memory
-    for kwargs in (dict(), dict(halo=2), dict(other=_host_field()), dict(other=_host_field((8, 9))), dict(origin=(1, 1), domain=(2, 2, 3))):
+    for kwargs in (dict(), dict(halo=2), dict(other=E.host_field(HOST)), dict(other=E.host_field((8, 9))), dict(origin=(1, 1), domain=(2, 2, 3))):
         with pytest.raises(TypeError, match="device fields"):
-            D.field_stats(_host_field(), **kwargs)
+            D.field_stats(E.host_field(HOST), **kwargs)
     with pytest.raises(TypeError, match="device fields"):
-        D.FieldStats([_host_field((8, 9), "float32")], halo=((1, 2), (0, 3)))  # Field[IJ]
+        D.FieldStats([E.host_field((8, 9), "float32")], halo=((1, 2), (0, 3)))  # Field[IJ]

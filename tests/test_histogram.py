@@ -4,18 +4,17 @@ search on adversarial edges, every refusal of the C entry through the dry run (m
 declaration, the kernels' resources, the arithmetic of ``Hist`` and the Python interface's argument checks."""
 
 import ctypes
-import gc
-import pathlib
 import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import histogram_ref as R
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, histogram
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 
 
 def _edge_sets():
@@ -106,31 +105,20 @@ def test_the_guess_and_correct_search_equals_the_plain_search_on_adversarial_edg
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_field_histogram\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* fields", "int nfields", "const int64_t extent[3]", "int elem_size", "int nbins", "const double* edges",
-                      "const double* edges_host", "int by", "int64_t* result", "int flags", "void* stream", "int* path", "int* launches"]
-    fn = _lib.load().gt4mi_field_histogram
     fp, i64p, c_int, ip = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_int)
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, c_int, i64p, c_int, c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_void_p, c_int,
-                           ctypes.c_void_p, ip, ip]
-    assert "gt4mi_field_histogram" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_field_histogram")
-    comment = text[: text.index("int gt4mi_field_histogram(")].rsplit("/* ----", 1)[1]
-    source = (ROOT / "gt4py_amd" / "csrc" / "field_histogram.hip.h").read_text()
-    for phrase in ("x != x", "x < e[0]", "-inf included", "+inf included", "the last bin is closed", "numpy.histogram", "-0.0 == 0.0",
-                   "weighted histograms", "rows along I or J", "joint"):
-        assert phrase in comment and phrase in source, phrase
-    for phrase in ("x > e[nbins]", "e[b] <= x < e[b+1]", "bounded by a constant", "hipMemsetAsync", "2^31 - 1 items", "49 184"):
-        assert phrase in comment, phrase
-    for name in ("MAX_FIELDS", "MAX_BINS", "EXTRA", "BELOW", "ABOVE", "NAN", "WHOLE", "BY_K", "PATH_ROWS", "PATH_ITEMS", "ACCUMULATE",
-                 "EDGES_PER_FIELD", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_HISTOGRAM_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"HISTOGRAM_{name}") == value, name
+    shared = ("x != x", "x < e[0]", "-inf included", "+inf included", "the last bin is closed", "numpy.histogram", "-0.0 == 0.0",
+              "weighted histograms", "rows along I or J", "joint")
+    E.check_binding("gt4mi_field_histogram",
+                    ["const gt4mi_field* fields", "int nfields", "const int64_t extent[3]", "int elem_size", "int nbins", "const double* edges",
+                     "const double* edges_host", "int by", "int64_t* result", "int flags", "void* stream", "int* path", "int* launches"],
+                    argtypes=[fp, c_int, i64p, c_int, c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_void_p, c_int,
+                              ctypes.c_void_p, ip, ip],
+                    prefix="HISTOGRAM", constants=("MAX_FIELDS", "MAX_BINS", "EXTRA", "BELOW", "ABOVE", "NAN", "WHOLE", "BY_K", "PATH_ROWS",
+                                                   "PATH_ITEMS", "ACCUMULATE", "EDGES_PER_FIELD", "DRY_RUN"),
+                    phrases=shared + ("x > e[nbins]", "e[b] <= x < e[b+1]", "bounded by a constant", "hipMemsetAsync", "2^31 - 1 items", "49 184"))
+    source = (E.ROOT / "gt4py_amd" / "csrc" / "field_histogram.hip.h").read_text()
+    for phrase in shared:
+        assert phrase in source, phrase
     assert (R.BELOW, R.ABOVE, R.NAN, R.EXTRA) == (_lib.HISTOGRAM_BELOW, _lib.HISTOGRAM_ABOVE, _lib.HISTOGRAM_NAN, _lib.HISTOGRAM_EXTRA)
     assert int(re.search(r"HIST_NUDGE = (\d+)", source).group(1)) == R.NUDGE and int(re.search(r"HIST_BISECT = (\d+)", source).group(1)) == R.BISECT
 
@@ -140,25 +128,19 @@ SHAPE = (6, 7, 5)
 EDGES = object()
 
 
-def _field(ptr, shape=SHAPE, strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj, nk = shape
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, shape, strides, origin)
+def _field(ptr, shape=SHAPE, *rest, **kwargs):  # (this file's shape)
+    return E.field(ptr, shape, *rest, **kwargs)
 
 
 def _call(fields, nfields=1, extent=(4, 5, 5), size=8, nbins=4, edges=EDG, host=EDGES, by=0, result=RES, flags=0, dry=True):
-    lib = _lib.load()
-    path, launches = ctypes.c_int(77), ctypes.c_int(77)
     if host is EDGES:
         sets = max(nfields, 1) if flags & _lib.HISTOGRAM_EDGES_PER_FIELD else 1
         host = np.tile(np.linspace(0.0, 1.0, max(nbins, 1) + 1), sets)
     keep = None if host is None else np.ascontiguousarray(host, dtype=np.float64)
-    rc = lib.gt4mi_field_histogram(ctypes.byref(fields) if isinstance(fields, _lib.Field) else fields, nfields,
-                                   (ctypes.c_int64 * 3)(*extent) if extent is not None else None, size, nbins, edges,
-                                   None if keep is None else keep.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), by, result,
-                                   flags | (_lib.HISTOGRAM_DRY_RUN if dry else 0), None, ctypes.byref(path), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, path.value
+    rc, msg, path, launches = E.call("gt4mi_field_histogram", as_arg(fields), nfields, int64s(extent), size, nbins, edges,
+                                     None if keep is None else keep.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), by, result,
+                                     flags | (_lib.HISTOGRAM_DRY_RUN if dry else 0), None, outs=(77, 77))
+    return rc, msg, launches, path
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -171,7 +153,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
                 assert rc == 0 and launches == 1 and path == ROWS, msg
     assert _call(_field(FLD, itemsize=4), size=4)[0] == 0
     assert _call(_field(FLD), nbins=_lib.HISTOGRAM_MAX_BINS)[0] == 0 and _call(_field(FLD), nbins=1)[0] == 0
-    eight = (_lib.Field * 9)(*[_field(FLD + n * 0x10000) for n in range(9)])
+    eight = E.table(_field(FLD + n * 0x10000) for n in range(9))
     assert _call(eight, nfields=8)[:1] == (0,) and _call(eight, nfields=8, flags=_lib.HISTOGRAM_EDGES_PER_FIELD)[0] == 0
     # the paths: ROWS where every field has a unit-stride axis inside a row's box, whichever it is
     kfirst, jfirst = (280, 40, 8), (56, 8, 336)
@@ -179,7 +161,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert _call(_field(FLD, strides=kfirst), by=1)[3] == ITEMS and _call(_field(FLD, strides=jfirst), by=1)[3] == ROWS
     assert _call(_field(FLD, strides=(16, 96, 672)))[3] == ITEMS
     assert _call(_field(FLD), extent=(1, 5, 5))[3] == ITEMS and _call(_field(FLD, strides=kfirst), extent=(4, 5, 1))[3] == ITEMS
-    pair = (_lib.Field * 2)(_field(FLD), _field(FLD + 0x10000, strides=(16, 96, 672)))
+    pair = E.table((_field(FLD), _field(FLD + 0x10000, strides=(16, 96, 672))))
     assert _call(pair, nfields=2)[3] == ITEMS
     # null pointers
     rc, msg, launches, path = _call(None)
@@ -237,7 +219,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
         assert rc == OOB and b"field 0" in msg and b"axis %d is outside the array" % axis in msg and launches == 0, msg
     rc, msg, *_ = _call(_field(FLD, origin=(1, -1, 0)))
     assert rc == OOB and b"field 0: negative origin -1 along axis 1" in msg
-    rc, msg, *_ = _call((_lib.Field * 2)(_field(FLD), _field(FLD + 0x10000, origin=(3, 1, 0))), nfields=2)
+    rc, msg, *_ = _call(E.table((_field(FLD), _field(FLD + 0x10000, origin=(3, 1, 0)))), nfields=2)
     assert rc == OOB and b"field 1: origin 3 + extent 4 along axis 0 is outside the array (shape 6)" in msg
     rc, msg, *_ = _call(_field(FLD, strides=(8, 52, 336)))
     assert rc == UNS and b"multiple of the item size" in msg
@@ -259,7 +241,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert _call(_field(FLD), result=first - 5 * 7 * 8)[0] == 0
     rc, msg, *_ = _call(_field(FLD), result=first - 5 * 7 * 8, by=1)  # five rows per level reach into the box
     assert rc == 0 and _call(_field(FLD), result=first - 5 * 7 * 8 + 8, by=1)[0] == INV
-    rc, msg, *_ = _call((_lib.Field * 2)(_field(FLD), _field(RES)), nfields=2)
+    rc, msg, *_ = _call(E.table((_field(FLD), _field(RES))), nfields=2)
     assert rc == INV and b"result overlaps field 1" in msg
     rc, msg, *_ = _call(_field(FLD), edges=RES + 8)
     assert rc == INV and b"result overlaps edges" in msg
@@ -271,13 +253,10 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*field_histogram\S*kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"field_histogram\S*kernel")
     # (float, float64) x (a counter copy per wave up to 1024 bins, one copy up to 4096)
     assert len(kernels) == 4 and len({name for name, *_ in kernels}) == 4, kernels
-    source = (ROOT / "gt4py_amd" / "csrc" / "field_histogram.hip.h").read_text()
+    source = (E.ROOT / "gt4py_amd" / "csrc" / "field_histogram.hip.h").read_text()
     stated = [int(v.replace(" ", "")) for v in re.findall(r"= (\d\d \d\d\d) bytes", source)]
     assert stated == [24640, 49184]
     for name, scratch, waves, lds in kernels:
@@ -346,16 +325,6 @@ def test_merge_histograms_is_the_histogram_of_the_concatenation():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 E5 = [0.0, 1.0, 2.0, 3.0, 4.0]
 
 
@@ -380,7 +349,7 @@ E5 = [0.0, 1.0, 2.0, 3.0, 4.0]
     (dict(edges=[E5], domain=(2, 3, 1), origin=(3, 3, 2)), TypeError, "device fields"),
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
-    field = _host_field()
+    field = E.host_field(HOST)
     with pytest.raises(error, match=match):
         histogram.histogram(field, **kwargs)
     with pytest.raises(error, match=match):
@@ -391,7 +360,7 @@ def test_python_refusals_about_the_fields_themselves():
     import torch
 
     F = histogram.histogram
-    field = _host_field()
+    field = E.host_field(HOST)
     with pytest.raises(ValueError, match="at least one field"):
         F(edges=E5)
     with pytest.raises(ValueError, match="at least one field"):
@@ -399,17 +368,17 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError, match="host"):
         F(torch.zeros(8, 9, 5, dtype=torch.float64), edges=E5)  # as_device_array's own refusal
     with pytest.raises(ValueError, match="takes IJ or IJK fields, not a field of 1 dimension"):
-        F(_host_field((8,)), edges=E5)
+        F(E.host_field((8,)), edges=E5)
     with pytest.raises(TypeError, match="share a dtype: float64 and float32 differ"):
-        F(field, _host_field(dtype="float32"), edges=E5)
+        F(field, E.host_field(HOST, dtype="float32"), edges=E5)
     with pytest.raises(TypeError, match="float32 or float64 fields, not int64"):
-        F(_host_field(dtype="int64"), edges=E5)
+        F(E.host_field(HOST, dtype="int64"), edges=E5)
     with pytest.raises(ValueError, match="nfields = 9 is outside 1 .. 8"):
-        F(*[_host_field() for _ in range(9)], edges=E5)
+        F(*[E.host_field(HOST) for _ in range(9)], edges=E5)
     with pytest.raises(ValueError, match="field 1: origin 0 \\+ extent 9 along axis 1 is outside the array \\(shape 8\\)"):
-        F(field, _host_field((8, 8, 5)), edges=E5)  # the first field sets the box
+        F(field, E.host_field((8, 8, 5)), edges=E5)  # the first field sets the box
     with pytest.raises(TypeError, match="device fields"):
-        F(_host_field((8, 9)), edges=E5, by="K")  # IJ: one level
+        F(E.host_field((8, 9)), edges=E5, by="K")  # IJ: one level
     with pytest.raises(ValueError, match="bins must be a positive int"):
         histogram.Histogram.uniform([field], 0.0, 1.0, 0)
     with pytest.raises(ValueError, match="not strictly increasing"):
@@ -423,7 +392,7 @@ def test_a_frozen_histogram_knows_its_box_its_edges_and_its_views(monkeypatch):
     import torch
 
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    fields = [_host_field((10, 9, 5), "float32") for _ in range(3)]
+    fields = [E.host_field((10, 9, 5), "float32") for _ in range(3)]
     h = histogram.Histogram.uniform(fields, -1.0, 1.0, 8, by="K", accumulate=True, halo=((1, 2), (0, 1)))
     assert (h.bins, h.by, h.accumulate, h.rows, h.origin, h.domain, h.launches, h.path) == (8, "K", True, 5, (1, 0, 0), (7, 8, 5), 1, "items")
     assert np.array_equal(h.edges, np.linspace(-1.0, 1.0, 9)) and h.edges.dtype == np.float64
@@ -442,6 +411,4 @@ def test_a_frozen_histogram_knows_its_box_its_edges_and_its_views(monkeypatch):
     # torch's C order is K-contiguous: whole-box calls walk K, per-level calls go item by item
     assert histogram.Histogram(fields[0], edges=E5).path == "rows" and histogram.Histogram(fields[0], edges=E5, by="K").path == "items"
     del fields[1]
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        h()
+    E.refuses_a_dead_array(h)

@@ -3,19 +3,16 @@ tests/horizontal_interp_ref.py, whose plain-Python and numpy forms are held agai
 entry through the dry run (made-up addresses that are never dereferenced), the declaration, the kernels' resources and the Python
 interface's argument checks."""
 
-import ctypes
-import gc
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import horizontal_interp_ref as H
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, horizontal
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (10, 9, 5)  # the shape of a host field where a test states none
 REACHES = [(0, 0, 0, 0), (1, 1, 1, 1), (2, 2, 2, 2), (3, 1, 0, 2)]
 
 
@@ -187,28 +184,14 @@ def test_documented_consequences():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_horizontal_interp\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* pos_i",
-                      "const gt4mi_field* pos_j", "const int64_t extent[3]", "const int64_t reach[4]", "int elem_size",
-                      "int pos_elem_size", "int method", "int flags", "void* stream", "int* launches"]
-    fn = _lib.load().gt4mi_horizontal_interp
-    fp, i64p, c_int = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, fp, fp, i64p, i64p, c_int, c_int, c_int, c_int, ctypes.c_void_p, ctypes.POINTER(c_int)]
-    assert "gt4mi_horizontal_interp" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_horizontal_interp")
     # the header states the contract and that the reference has no counterpart; the enums of header and binding agree
-    comment = text[: text.index("int gt4mi_horizontal_interp(")].rsplit("/* ----", 1)[1]
-    for phrase in ("no reference counterpart", "fancy indexing", "floor(x + 0.5)", "w0j*r0 + w1j*r1", "((a*t)*c) / 6.0", "edge replication",
-                   "0 * inf = NaN"):
-        assert phrase in comment, phrase
-    for name in ("NEAREST", "LINEAR", "CUBIC", "CUBIC_MONOTONE", "RELATIVE", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_INTERP_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"INTERP_{name}") == value, name
+    E.check_binding("gt4mi_horizontal_interp",
+                    ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* pos_i",
+                     "const gt4mi_field* pos_j", "const int64_t extent[3]", "const int64_t reach[4]", "int elem_size",
+                     "int pos_elem_size", "int method", "int flags", "void* stream", "int* launches"],
+                    prefix="INTERP", constants=("NEAREST", "LINEAR", "CUBIC", "CUBIC_MONOTONE", "RELATIVE", "DRY_RUN"),
+                    phrases=("no reference counterpart", "fancy indexing", "floor(x + 0.5)", "w0j*r0 + w1j*r1", "((a*t)*c) / 6.0", "edge replication",
+                             "0 * inf = NaN"))
     assert horizontal.METHODS == {"nearest": 0, "linear": 1, "cubic": 2, "cubic_monotone": 3}
 
 
@@ -216,28 +199,17 @@ DST, SRC, PI, PJ = 0x10_0000, 0x4000_0000, 0x8000_0000, 0xC000_0000  # made-up d
 NK = 3
 
 
-def _field(ptr, nk=NK, shape_ij=(8, 8), strides=None, origin=(2, 2, 0), itemsize=8):
-    ni, nj = shape_ij
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, (ni, nj, nk), strides, origin)
+def _field(ptr, nk=NK, shape_ij=(8, 8), strides=None, origin=(2, 2, 0), itemsize=8):  # (nk first; this file's plane and origin)
+    return E.field(ptr, (*shape_ij, nk), strides, origin, itemsize)
 
 
-def _plane(ptr, shape_ij=(8, 8), origin=(2, 2, 0), itemsize=8):
-    """A Field[IJ] of positions: K stride 0."""
-    ni, nj = shape_ij
-    return _lib.Field.make(ptr, (ni, nj, 1), (itemsize, ni * itemsize, 0), origin)
+def _plane(ptr, shape_ij=(8, 8), origin=(2, 2, 0), itemsize=8):  # (positions; this file's plane and origin)
+    return E.plane(ptr, shape_ij, origin, itemsize)
 
 
 def _call(dst, src, pi, pj, nfields=1, extent=(4, 4, NK), reach=(1, 1, 1, 1), size=8, pos_size=8, method=1, flags=0):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_horizontal_interp(as_arg(dst), as_arg(src), nfields, as_arg(pi), as_arg(pj),
-                                     (ctypes.c_int64 * 3)(*extent) if extent is not None else None,
-                                     (ctypes.c_int64 * 4)(*reach) if reach is not None else None, size, pos_size, method,
-                                     flags | _lib.INTERP_DRY_RUN, None, ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value
+    return E.call("gt4mi_horizontal_interp", as_arg(dst), as_arg(src), nfields, as_arg(pi), as_arg(pj), int64s(extent), int64s(reach),
+                  size, pos_size, method, flags | _lib.INTERP_DRY_RUN, None, outs=(77,))
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -342,7 +314,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == UNS and b"dst 0 and pos_i overlap in memory" in msg
     rc, msg, _ = _call(d, s, pi, _plane(DST + 8 * 20))
     assert rc == UNS and b"dst 0 and pos_j overlap in memory" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, _ = _call(two(d, _field(DST + 0x1000)), two(s, _field(DST + 64)), pi, pj, nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, _ = _call(two(d, _field(DST + 128)), two(s, _field(SRC + 0x1000)), pi, pj, nfields=2)
@@ -358,17 +330,14 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
 
 
 def test_launches_are_one_per_eight_pairs():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x1000) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x1000) for n in range(9)])
+    d = E.table(_field(DST + n * 0x1000) for n in range(9))
+    s = E.table(_field(SRC + n * 0x1000) for n in range(9))
     pi, pj = _plane(PI), _plane(PJ)
     assert [_call(d, s, pi, pj, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*horizontal_interp_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"horizontal_interp_kernel")
     # 2 field types x 2 position types x 4 methods x the instantiations for 1, 4 and 8 entries
     assert len(kernels) == 48 and len({name for name, *_ in kernels}) == 48, kernels
     for name, scratch, waves, lds in kernels:
@@ -376,18 +345,8 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(10, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def _good(**over):
-    args = dict(dst=_host_field(), src=_host_field(), pos_i=_host_field(), pos_j=_host_field((10, 9)))
+    args = dict(dst=E.host_field(HOST), src=E.host_field(HOST), pos_i=E.host_field(HOST), pos_j=E.host_field((10, 9)))
     args.update(over)
     return args.pop("dst"), args.pop("src"), args
 
@@ -420,7 +379,7 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(ValueError, match="at least one"):
         R([], [], **pos)
     with pytest.raises(ValueError, match="2 destination.s. and 1 source"):
-        R([dst, _host_field()], [src], **pos)
+        R([dst, E.host_field(HOST)], [src], **pos)
     with pytest.raises(TypeError, match="host"):
         R(torch.zeros(10, 9, 5, dtype=torch.float64), src, **pos)  # as_device_array's own refusal
     with pytest.raises(TypeError):
@@ -428,22 +387,22 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         R(dst, src, pos_i=np.zeros((10, 9)), pos_j=pos["pos_j"])
     with pytest.raises(ValueError, match="takes IJK fields"):
-        R(_host_field((10, 9)), src, **pos)
+        R(E.host_field((10, 9)), src, **pos)
     with pytest.raises(ValueError, match="pos_j must be an IJK field or a Field.IJ."):
-        R(dst, src, pos_i=pos["pos_i"], pos_j=_host_field((9,)))
+        R(dst, src, pos_i=pos["pos_i"], pos_j=E.host_field((9,)))
     # dtypes: the fields share one, the position fields share one (not necessarily the same), all float32 or float64
     with pytest.raises(TypeError, match="share a dtype"):
-        R(_host_field(dtype="float32"), src, **pos)
+        R(E.host_field(HOST, dtype="float32"), src, **pos)
     with pytest.raises(TypeError, match="float32 or float64 fields"):
-        R(_host_field(dtype="int64"), _host_field(dtype="int64"), **pos)
+        R(E.host_field(HOST, dtype="int64"), E.host_field(HOST, dtype="int64"), **pos)
     with pytest.raises(TypeError, match="pos_i and pos_j share a dtype"):
-        R(dst, src, pos_i=pos["pos_i"], pos_j=_host_field((10, 9), "float32"))
+        R(dst, src, pos_i=pos["pos_i"], pos_j=E.host_field((10, 9), "float32"))
     with pytest.raises(TypeError, match="position fields are float32 or float64"):
-        R(dst, src, pos_i=_host_field(dtype="int32"), pos_j=_host_field(dtype="int32"))
+        R(dst, src, pos_i=E.host_field(HOST, dtype="int32"), pos_j=E.host_field(HOST, dtype="int32"))
     with pytest.raises(TypeError, match="device fields"):  # float32 fields against float64 positions is a combination of its own
-        R(_host_field(dtype="float32"), _host_field(dtype="float32"), **pos)
+        R(E.host_field(HOST, dtype="float32"), E.host_field(HOST, dtype="float32"), **pos)
     # a field onto itself; a dst that is also a position field
-    x = _host_field()
+    x = E.host_field(HOST)
     with pytest.raises(TypeError, match="dst 0 and src 0 overlap in memory"):
         R(x, x, **pos)
     with pytest.raises(TypeError, match="dst 0 and pos_i overlap in memory"):
@@ -453,15 +412,10 @@ def test_python_refusals_about_the_fields_themselves():
 def test_a_frozen_interpolation_knows_its_box_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a HorizontalInterp whose device
     check is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    dsts, srcs = [_host_field((10, 9, 5)) for _ in range(9)], [_host_field((12, 9, 6)) for _ in range(9)]
-    pi, pj = _host_field((10, 9), "float32"), _host_field((10, 9, 5), "float32")
+    E.on_device(monkeypatch)
+    dsts, srcs = [E.host_field((10, 9, 5)) for _ in range(9)], [E.host_field((12, 9, 6)) for _ in range(9)]
+    pi, pj = E.host_field((10, 9), "float32"), E.host_field((10, 9, 5), "float32")
     hi = horizontal.HorizontalInterp(dsts, srcs, pos_i=pi, pos_j=pj, method="cubic", relative=True, halo=((2, 1), (1, 3)))
     assert (hi.launches, hi.domain, hi.origin, hi.method, hi.relative) == (2, (7, 5, 5), (2, 1, 0), "cubic", True)
     del pi
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        hi()
+    E.refuses_a_dead_array(hi)

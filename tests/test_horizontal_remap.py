@@ -4,19 +4,17 @@ dry run, with made-up addresses that are never dereferenced), the declarations, 
 argument checks and the properties of the restated arithmetic (conservation, linear fields)."""
 
 import ctypes
-import gc
 import math
-import pathlib
 import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import horizontal_remap_ref as R
+from entry_checks import INV, OOB, UNS, as_arg
 from gt4py_amd import _lib, horizontal
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
 EPS = 2.0 ** -52
 METHODS = [R.PCM, R.PLM]
 SIZES = [(1, 1), (1, 5), (5, 1), (2, 3), (17, 9), (9, 17), (130, 1)]
@@ -165,35 +163,26 @@ def test_every_refusal_of_the_table_entry():
 
 # ---- the declarations ------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signatures_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    params = lambda name: [" ".join(p.split()) for p in re.search(rf"int {name}\((.*?)\);", text, re.S).group(1).split(",")]  # noqa: E731
-    assert params("gt4mi_overlap_table") == ["const double* src_edges", "int ns", "const double* dst_edges", "int nd", "int32_t* ptr", "int32_t* cell",
-                                             "double* w", "double* h", "double* c", "double* den", "int capacity", "int* nnz"]
-    assert params("gt4mi_horizontal_remap") == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_overlap_axis* axis_i",
-                                                "const gt4mi_overlap_axis* axis_j", "int64_t nk", "int elem_size", "int method", "int flags",
-                                                "void* stream", "int* launches"]
+    P, I = ctypes.c_void_p, ctypes.c_int
+    E.check_binding("gt4mi_overlap_table",
+                    ["const double* src_edges", "int ns", "const double* dst_edges", "int nd", "int32_t* ptr", "int32_t* cell",
+                     "double* w", "double* h", "double* c", "double* den", "int capacity", "int* nnz"],
+                    argtypes=[P, I, P, I, P, P, P, P, P, P, I, ctypes.POINTER(I)])
+    E.check_binding("gt4mi_horizontal_remap",
+                    ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_overlap_axis* axis_i",
+                     "const gt4mi_overlap_axis* axis_j", "int64_t nk", "int elem_size", "int method", "int flags",
+                     "void* stream", "int* launches"],
+                    prefix="HREMAP", constants=("PCM", "PLM", "DRY_RUN"),
+                    phrases=("conservative horizontal remapping", "no reference", "(r - l) / d", "xs[k+1] >= hi", "0.5 * (xl + xr) - 0.5",
+                             "edge replication", "row_b = sum_a wi_a * q[a, b]", "(q[a, b] + si * ci_a) + sj * cj_b",
+                             "not strictly monotone in 2-d", "clamps each ptr value to [0, nnz]"))
+    text = (E.ROOT / "include" / "gt4py_amd.h").read_text()
     struct = re.search(r"typedef struct gt4mi_overlap_axis \{(.*?)\} gt4mi_overlap_axis;", text, re.S).group(1)
     members = [" ".join(m.split()) for m in re.sub(r"/\*.*?\*/", "", struct, flags=re.S).split(";") if m.strip()]
     assert members == ["int32_t ns, nd, nnz", "const int32_t* ptr", "const int32_t* cell", "const double* w", "const double* h", "const double* c",
                        "const double* den"]
     assert [n for n, _ in _lib.OverlapAxis._fields_] == ["ns", "nd", "nnz", "ptr", "cell", "w", "h", "c", "den"]
     assert ctypes.sizeof(_lib.OverlapAxis) == 64 and _lib.OverlapAxis.ptr.offset == 16
-    lib = _lib.load()
-    P, I = ctypes.c_void_p, ctypes.c_int
-    fp, ap = ctypes.POINTER(_lib.Field), ctypes.POINTER(_lib.OverlapAxis)
-    assert lib.gt4mi_overlap_table.restype is I and lib.gt4mi_overlap_table.argtypes == [P, I, P, I, P, P, P, P, P, P, I, ctypes.POINTER(I)]
-    assert lib.gt4mi_horizontal_remap.restype is I
-    assert lib.gt4mi_horizontal_remap.argtypes == [fp, fp, I, ap, ap, ctypes.c_int64, I, I, I, P, ctypes.POINTER(I)]
-    for name in ("gt4mi_overlap_table", "gt4mi_horizontal_remap"):
-        assert name in _lib.EXPORTED_SYMBOLS and hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), name)
-    comment = text[: text.index("int gt4mi_horizontal_remap(")].split("conservative horizontal remapping", 1)[1]
-    for phrase in ("no reference", "(r - l) / d", "xs[k+1] >= hi", "0.5 * (xl + xr) - 0.5", "edge replication", "row_b = sum_a wi_a * q[a, b]",
-                   "(q[a, b] + si * ci_a) + sj * cj_b", "not strictly monotone in 2-d", "clamps each ptr value to [0, nnz]"):
-        assert phrase in comment, phrase
-    for name in ("PCM", "PLM", "DRY_RUN"):
-        assert getattr(_lib, f"HREMAP_{name}") == int(re.search(rf"GT4MI_HREMAP_{name} = (\d+)", text).group(1)), name
     assert horizontal.REMAP_METHODS == {"pcm": _lib.HREMAP_PCM, "plm": _lib.HREMAP_PLM}
 
 
@@ -202,11 +191,8 @@ DST, SRC, TAB = 0x10_0000, 0x4000_0000, 0x8000_0000  # made-up device addresses,
 NS_I, NS_J, ND_I, ND_J, NK = 6, 5, 4, 3, 3
 
 
-def _field(ptr, shape_ij, nk=NK, strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj = shape_ij
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, (ni, nj, nk), strides, origin)
+def _field(ptr, shape_ij, nk=NK, strides=None, origin=(1, 1, 0), itemsize=8):  # (the plane, then this file's nk)
+    return E.field(ptr, (*shape_ij, nk), strides, origin, itemsize)
 
 
 def _axis(base, ns, nd, nnz=None, **over):
@@ -218,12 +204,8 @@ def _axis(base, ns, nd, nnz=None, **over):
 
 
 def _call(dst, src, axis_i, axis_j, nfields=1, nk=NK, size=8, method=0, flags=0):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, (_lib.Field, _lib.OverlapAxis)) else f  # noqa: E731
-    rc = lib.gt4mi_horizontal_remap(as_arg(dst), as_arg(src), nfields, as_arg(axis_i), as_arg(axis_j), nk, size, method,
-                                    flags | _lib.HREMAP_DRY_RUN, None, ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value
+    return E.call("gt4mi_horizontal_remap", as_arg(dst), as_arg(src), nfields, as_arg(axis_i), as_arg(axis_j), nk, size, method,
+                  flags | _lib.HREMAP_DRY_RUN, None, outs=(77,))
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -322,7 +304,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == UNS and b"overlap in memory" in msg
     rc, msg, _ = _call(d, _field(DST + last - s_first + 8, (NS_I + 2, NS_J + 2)), ai, aj)  # the byte ranges of the BOXES do not meet
     assert rc == 0, msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, _ = _call(two(d, _field(DST + 0x1000, (ND_I + 2, ND_J + 2))), two(s, _field(DST + 64, (NS_I + 2, NS_J + 2))), ai, aj, nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, _ = _call(two(d, _field(DST + 128, (ND_I + 2, ND_J + 2))), two(s, _field(SRC + 0x1000, (NS_I + 2, NS_J + 2))), ai, aj, nfields=2)
@@ -344,17 +326,14 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
 
 
 def test_launches_are_one_per_eight_pairs():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x1000, (ND_I + 2, ND_J + 2)) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x1000, (NS_I + 2, NS_J + 2)) for n in range(9)])
+    d = E.table(_field(DST + n * 0x1000, (ND_I + 2, ND_J + 2)) for n in range(9))
+    s = E.table(_field(SRC + n * 0x1000, (NS_I + 2, NS_J + 2)) for n in range(9))
     ai, aj = _axis(TAB, NS_I, ND_I), _axis(TAB + 0x10000, NS_J, ND_J)
     assert [_call(d, s, ai, aj, nfields=n)[2] for n in (1, 4, 8, 9)] == [1, 1, 1, 2]
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*horizontal_remap_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"horizontal_remap_kernel")
     # 2 field types x 2 methods x the instantiations for 1, 4 and 8 entries
     assert len(kernels) == 12 and len({name for name, *_ in kernels}) == 12, kernels
     for name, scratch, waves, lds in kernels:
@@ -362,21 +341,11 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work -------------------------------------------------------------------
-def _host_field(shape, dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 XI, XJ, YI, YJ = np.linspace(0, 1, 9), np.linspace(0, 2, 7), np.linspace(0, 1, 5), np.linspace(-0.5, 2.5, 4)
 
 
 def _good(**over):
-    args = dict(dst=_host_field((4, 3, 5)), src=_host_field((8, 6, 5)), src_edges=(XI, XJ), dst_edges=(YI, YJ))
+    args = dict(dst=E.host_field((4, 3, 5)), src=E.host_field((8, 6, 5)), src_edges=(XI, XJ), dst_edges=(YI, YJ))
     args.update(over)
     return args.pop("dst"), args.pop("src"), args
 
@@ -417,29 +386,29 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(ValueError, match="at least one"):
         F([], [], **edges)
     with pytest.raises(ValueError, match="2 destination.s. and 1 source"):
-        F([dst, _host_field((4, 3, 5))], [src], **edges)
+        F([dst, E.host_field((4, 3, 5))], [src], **edges)
     with pytest.raises(TypeError, match="host"):
         F(torch.zeros(4, 3, 5, dtype=torch.float64), src, **edges)  # as_device_array's own refusal
     with pytest.raises(TypeError):
         F(dst, np.zeros((8, 6, 5)), **edges)
     with pytest.raises(ValueError, match="takes IJK fields"):
-        F(_host_field((4, 3)), src, **edges)
+        F(E.host_field((4, 3)), src, **edges)
     with pytest.raises(TypeError, match="share a dtype: float64 and float32 differ"):
-        F(dst, _host_field((8, 6, 5), "float32"), **edges)
+        F(dst, E.host_field((8, 6, 5), "float32"), **edges)
     with pytest.raises(TypeError, match="share a dtype"):
-        F([dst, _host_field((4, 3, 5), "float32")], [src, src], **edges)
+        F([dst, E.host_field((4, 3, 5), "float32")], [src, src], **edges)
     with pytest.raises(TypeError, match="float32 or float64 fields"):
-        F(_host_field((4, 3, 5), "int64"), _host_field((8, 6, 5), "int64"), **edges)
+        F(E.host_field((4, 3, 5), "int64"), E.host_field((8, 6, 5), "int64"), **edges)
     with pytest.raises(ValueError, match=r"levels behind the origin: \[4, 5\] differ"):
-        F([dst, _host_field((4, 3, 4))], [src, src], **edges)
+        F([dst, E.host_field((4, 3, 4))], [src, src], **edges)
     with pytest.raises(ValueError, match="do not match dst 1 of shape"):
-        F([dst, _host_field((3, 3, 5))], [src, src], **edges)
+        F([dst, E.host_field((3, 3, 5))], [src, src], **edges)
     with pytest.raises(TypeError, match="device fields"):
-        F(_host_field((4, 3, 5), "float32"), _host_field((8, 6, 5), "float32"), **edges)
+        F(E.host_field((4, 3, 5), "float32"), E.host_field((8, 6, 5), "float32"), **edges)
     with pytest.raises(TypeError, match="device fields"):  # fields larger than the boxes, with origins
-        F(_host_field((6, 5, 5)), _host_field((9, 9, 6)), **edges, dst_origin=(2, 1, 0), src_origin=(1, 3, 1))
+        F(E.host_field((6, 5, 5)), E.host_field((9, 9, 6)), **edges, dst_origin=(2, 1, 0), src_origin=(1, 3, 1))
     # a field onto itself (identical grids): the library's refusal, as a TypeError
-    x = _host_field((8, 6, 5))
+    x = E.host_field((8, 6, 5))
     with pytest.raises(TypeError, match="dst 0 and src 0 overlap in memory"):
         F(x, x, src_edges=(XI, XJ), dst_edges=(XI, XJ))
 
@@ -447,11 +416,8 @@ def test_python_refusals_about_the_fields_themselves():
 def test_a_frozen_remap_knows_its_boxes_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a HorizontalRemap whose device
     check is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    dsts, srcs = [_host_field((5, 3, 5)) for _ in range(9)], [_host_field((8, 7, 6)) for _ in range(9)]
+    E.on_device(monkeypatch)
+    dsts, srcs = [E.host_field((5, 3, 5)) for _ in range(9)], [E.host_field((8, 7, 6)) for _ in range(9)]
     hr = horizontal.HorizontalRemap(dsts, srcs, src_edges=(XI, XJ), dst_edges=(YI, YJ), method="plm", src_origin=(0, 1, 1))
     assert (hr.src_extent, hr.dst_extent, hr.nk, hr.launches, hr.method) == ((8, 6), (4, 3), 5, 2, "plm")
     assert hr.terms == (8, 6 + 3 - 1) and (hr.src_origin, hr.dst_origin) == ((0, 1, 1), (0, 0, 0))
@@ -461,9 +427,7 @@ def test_a_frozen_remap_knows_its_boxes_and_refuses_to_run_after_an_array_died(m
         assert np.array_equal(hr._tables[2 * axis].numpy(), np.concatenate([ptr, cell]))
         assert np.array_equal(hr._tables[2 * axis + 1].numpy(), np.concatenate([w, h, c, den]))
     del srcs[4]
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        hr()
+    E.refuses_a_dead_array(hr)
 
 
 # ---- properties of the restated arithmetic ----------------------------------------------------------------------------------------

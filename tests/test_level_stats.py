@@ -4,16 +4,17 @@ every refusal (before any GPU work), the dry run's workspace and launch counts, 
 
 import ctypes
 import math
-import pathlib
 import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import level_stats_ref as R
+from entry_checks import INV, OOB, UNS, int64s
 from gt4py_amd import _lib, diagnostics
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
+HOST = (8, 9, 3)  # the shape of a host field where a test states none
 U = 2.0 ** -53
 PARAMS = ["const gt4mi_field* fields", "const gt4mi_field* others", "int nfields", "const int64_t domain[3]", "int elem_size",
           "void* workspace", "int64_t workspace_bytes", "double* result", "int flags", "void* stream", "int64_t* workspace_needed",
@@ -22,27 +23,16 @@ PARAMS = ["const gt4mi_field* fields", "const gt4mi_field* others", "int nfields
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_abi_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_level_stats\((.*?)\);", text, re.S).group(1)
-    assert [" ".join(p.split()) for p in decl.split(",")] == PARAMS
-    same = re.search(r"int gt4mi_field_stats\((.*?)\);", text, re.S).group(1)
-    assert [" ".join(p.split()) for p in same.split(",")] == PARAMS  # the signature of gt4mi_field_stats
-    fn = _lib.load().gt4mi_level_stats
     FP, c_int, vp = ctypes.POINTER(_lib.Field), ctypes.c_int, ctypes.c_void_p
-    assert fn.restype is c_int
-    assert fn.argtypes == [FP, FP, c_int, ctypes.POINTER(ctypes.c_int64), c_int, vp, ctypes.c_int64, vp, c_int, vp,
-                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)]
-    assert "gt4mi_level_stats" in _lib.EXPORTED_SYMBOLS
-    comment = text[: text.index("int gt4mi_level_stats(")].rsplit("/* ----", 1)[1]
-    for needle in ("no reference counterpart", "function of (ni, nj) alone", "partial[((entry * nk + k) * TL + t) * 8 + slot]",
-                   "result[(entry * 9 + row) * nk + k]", "ceil(nfields / 8) + 1"):
-        assert needle in comment, needle
+    types = [FP, FP, c_int, ctypes.POINTER(ctypes.c_int64), c_int, vp, ctypes.c_int64, vp, c_int, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)]
+    E.check_binding("gt4mi_level_stats", PARAMS, argtypes=types,
+                    phrases=("no reference counterpart", "function of (ni, nj) alone", "partial[((entry * nk + k) * TL + t) * 8 + slot]",
+                             "result[(entry * 9 + row) * nk + k]", "ceil(nfields / 8) + 1"))
+    E.check_binding("gt4mi_field_stats", PARAMS, argtypes=types)  # the signature of gt4mi_field_stats
 
 
 def test_constants_of_the_header_the_binding_and_the_restatement_agree():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
+    text = (E.ROOT / "include" / "gt4py_amd.h").read_text()
     header = {name: int(re.search(rf"GT4MI_LEVEL_STATS_{name}\s*=?\s*(\d+)", text).group(1)) for name in ("MEAN", "ROWS", "MAX_TILES")}
     assert header == {"MEAN": 8, "ROWS": 9, "MAX_TILES": _lib.LEVEL_STATS_MAX_TILES}
     assert (_lib.LEVEL_STATS_MEAN, _lib.LEVEL_STATS_ROWS) == (8, 9) == (R.MEAN, R.ROWS)
@@ -63,23 +53,20 @@ WORK, RESULT = 0x900000, 0xA00000
 NEEDED = 2 * 1 * 64  # domain (4, 4, 2): 2 levels of 4 rows, one per wave: one tile of 8 doubles each
 
 
-def _field(ptr=FIELD[0], shape=FIELD[1], strides=FIELD[2], origin=FIELD[3]):
-    return _lib.Field.make(ptr, shape, strides, origin)
+def _field(ptr=FIELD[0], shape=FIELD[1], strides=FIELD[2], origin=FIELD[3]):  # (everything defaults to FIELD)
+    return E.field(ptr, shape, strides, origin)
 
 
 def _call(fields, others=None, nfields=1, domain=(4, 4, 2), elem_size=8, workspace=WORK, workspace_bytes=1 << 20, result=RESULT,
           flags=_lib.STATS_DRY_RUN):
     """Refusals are provoked WITHOUT the dry-run flag (a refused call enqueues nothing); a call that would pass every check
     carries the flag."""
-    lib = _lib.load()
-    needed, launches = ctypes.c_int64(-5), ctypes.c_int(77)
-    rc = lib.gt4mi_level_stats(fields, others, nfields, _lib.domain3(domain) if domain is not None else None, elem_size,
-                               workspace, workspace_bytes, result, flags, None, ctypes.byref(needed), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, needed.value
+    rc, msg, needed, launches = E.call("gt4mi_level_stats", fields, others, nfields, int64s(domain), elem_size, workspace, workspace_bytes, result,
+                                       flags, None, outs=(ctypes.c_int64(-5), 77))
+    return rc, msg, launches, needed
 
 
 def test_argument_errors_of_the_c_entry_without_a_gpu():
-    INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
     f = ctypes.byref(_field())
 
     def refused(status, needle, *args, **kwargs):
@@ -144,7 +131,7 @@ def test_argument_errors_of_the_c_entry_without_a_gpu():
 
 
 def test_dry_run_reports_workspace_and_launches():
-    many = (_lib.Field * 17)(*[_field(ptr=0x10000 * (n + 1)) for n in range(17)])
+    many = E.table(_field(ptr=0x10000 * (n + 1)) for n in range(17))
     for n, want in ((1, 2), (8, 2), (9, 3), (16, 3), (17, 4)):
         rc, msg, launches, needed = _call(many, nfields=n, workspace=None, result=None)  # asking for the size
         assert rc == 0 and launches == want and needed == n * NEEDED, (n, msg)
@@ -159,10 +146,7 @@ def test_dry_run_reports_workspace_and_launches():
 def test_the_kernels_are_in_the_resource_log_and_use_no_scratch():
     """No scratch, LDS only for the per-workgroup combine, and no fewer waves per SIMD than the field_stats kernel of the same
     item type in the same log."""
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    found = re.findall(r"remark: Function Name: (\S*(?:field|level)_stats\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                       r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    found = E.kernel_resources(r"(?:field|level)_stats")
     kernels = {}
     for name, scratch, waves, lds in found:
         family = "level" if "level_stats" in name else "field"
@@ -332,38 +316,29 @@ def test_merge_profiles_joins_level_by_level_in_the_order_given():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 3), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check; a call that passed them all is refused last."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def test_python_refusals_need_no_gpu():
     D = diagnostics
     with pytest.raises(ValueError, match="at least one field"):
         D.level_stats()
     with pytest.raises(TypeError, match="float32 or float64 fields, not int32"):
-        D.level_stats(_host_field(dtype="int32"))
+        D.level_stats(E.host_field(HOST, dtype="int32"))
     with pytest.raises(TypeError, match="share a dtype"):
-        D.level_stats(_host_field(), other=_host_field(dtype="float32"))
+        D.level_stats(E.host_field(HOST), other=E.host_field(HOST, dtype="float32"))
     with pytest.raises(ValueError, match="one entry .* per field: 1 for 2 fields"):
-        D.LevelStats([_host_field(), _host_field()], others=[_host_field()])
+        D.LevelStats([E.host_field(HOST), E.host_field(HOST)], others=[E.host_field(HOST)])
     with pytest.raises(ValueError, match="IJ or IJK fields"):
-        D.level_stats(_host_field((8,)))
+        D.level_stats(E.host_field((8,)))
     with pytest.raises(ValueError, match="leave no domain"):
-        D.level_stats(_host_field(), halo=4)
+        D.level_stats(E.host_field(HOST), halo=4)
     with pytest.raises(ValueError, match="level_stats: field 0: origin 0 \\+ domain 4 along axis 2 is outside the array"):
-        D.level_stats(_host_field(), origin=(0, 0, 0), domain=(8, 9, 4))
+        D.level_stats(E.host_field(HOST), origin=(0, 0, 0), domain=(8, 9, 4))
     with pytest.raises(ValueError, match="level_stats: other 0: origin 1 \\+ domain 7 along axis 1"):
-        D.level_stats(_host_field(), other=_host_field((8, 7, 3)), halo=1)
+        D.level_stats(E.host_field(HOST), other=E.host_field((8, 7, 3)), halo=1)
     with pytest.raises(ValueError, match="level_stats: empty domain"):
-        D.level_stats(_host_field(), domain=(3, 3, 0))
+        D.level_stats(E.host_field(HOST), domain=(3, 3, 0))
     # all checks passed (an IJ weight against an IJK field, levels 1-2 only, an IJ field): refused for being host memory
-    for kwargs in (dict(), dict(halo=2), dict(other=_host_field((8, 9))), dict(origin=(1, 1, 1), domain=(2, 2, 2))):
+    for kwargs in (dict(), dict(halo=2), dict(other=E.host_field((8, 9))), dict(origin=(1, 1, 1), domain=(2, 2, 2))):
         with pytest.raises(TypeError, match="device fields"):
-            D.level_stats(_host_field(), **kwargs)
+            D.level_stats(E.host_field(HOST), **kwargs)
     with pytest.raises(TypeError, match="device fields"):
-        D.LevelStats([_host_field((8, 9), "float32")], halo=((1, 2), (0, 3)))  # Field[IJ]: nk = 1
+        D.LevelStats([E.host_field((8, 9), "float32")], halo=((1, 2), (0, 3)))  # Field[IJ]: nk = 1

@@ -4,19 +4,18 @@ addresses that are never dereferenced), the declaration, the path rule, the kern
 checks."""
 
 import ctypes
-import gc
-import pathlib
 import re
 
 import numpy as np
 import pytest
 
 import device_layouts as DL
+import entry_checks as E
 import line_filter_ref as R
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, linefilter
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 EPS = 2.0 ** -52
 LENGTHS = [2 ** k for k in range(1, 13)]
 #: The largest deviation of the restatement from numpy.fft over `_lines` for n = 2 .. 4096, in units of EPS times the scale of the
@@ -153,24 +152,12 @@ PARAMS = ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "co
 
 
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_line_filter\((.*?)\);", text, re.S).group(1)
-    assert [" ".join(p.split()) for p in decl.split(",")] == PARAMS
-    fn = _lib.load().gt4mi_line_filter
     fp, i64p, c_int, ip, vp = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, vp, i64p, vp, vp, i64p, c_int, c_int, c_int, c_int, vp, ip, ip]
-    assert "gt4mi_line_filter" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_line_filter")
-    comment = text[: text.index("int gt4mi_line_filter(")].rsplit("/* ----", 1)[1]
-    for phrase in ("u = a - b", "a' = a + b", "b'.re = wr * u.re - wi * u.im", "b'.im = wr * u.im + wi * u.re", "t.re = wr * b.re + wi * b.im",
-                   "t.im = wr * b.im - wi * b.re", "response[min(m, n - m)]", "no FMA", "bitrev_L(p)", "w[n/4] = (0, -1)", "1.0 / n",
-                   "never evaluates a sine", "mixed radix"):
-        assert phrase in comment, phrase
-    for name in ("APPLY", "SPECTRUM", "DRY_RUN"):
-        assert getattr(_lib, f"FILTER_{name}") == int(re.search(rf"GT4MI_FILTER_{name} = (\d+)", text).group(1)), name
+    E.check_binding("gt4mi_line_filter", PARAMS, argtypes=[fp, fp, c_int, vp, i64p, vp, vp, i64p, c_int, c_int, c_int, c_int, vp, ip, ip],
+                    prefix="FILTER", constants=("APPLY", "SPECTRUM", "DRY_RUN"),
+                    phrases=("u = a - b", "a' = a + b", "b'.re = wr * u.re - wi * u.im", "b'.im = wr * u.im + wi * u.re",
+                             "t.re = wr * b.re + wi * b.im", "t.im = wr * b.im - wi * b.re", "response[min(m, n - m)]", "no FMA", "bitrev_L(p)",
+                             "w[n/4] = (0, -1)", "1.0 / n", "never evaluates a sine", "mixed radix"))
 
 
 DST, SRC, RSP, TWD, RES = 0x10_0000, 0x4000_0000, 0x8000_0000, 0x9000_0000, 0xA000_0000  # made-up addresses, far apart
@@ -179,25 +166,14 @@ EXTENT = (8, 5, 5)
 APPLY, SPECTRUM = _lib.FILTER_APPLY, _lib.FILTER_SPECTRUM
 
 
-def _field(ptr, shape=SHAPE, strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj, nk = shape
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, shape, strides, origin)
-
-
-def _c_order(ptr, shape=SHAPE, itemsize=8):
-    return _field(ptr, shape, (shape[1] * shape[2] * itemsize, shape[2] * itemsize, itemsize), itemsize=itemsize)
+def _field(ptr, shape=SHAPE, *rest, **kwargs):  # (this file's shape)
+    return E.field(ptr, shape, *rest, **kwargs)
 
 
 def _call(dst, src, nfields=1, extent=EXTENT, axis=0, size=8, mode=APPLY, flags=0, response=RSP, rext=(1, 1), twiddles=TWD, result=None):
-    lib = _lib.load()
-    path, launches = ctypes.c_int(77), ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_line_filter(as_arg(dst), as_arg(src), nfields, response, None if rext is None else (ctypes.c_int64 * 2)(*rext), twiddles, result,
-                               (ctypes.c_int64 * 3)(*extent) if extent is not None else None, axis, size, mode, flags | _lib.FILTER_DRY_RUN,
-                               None, ctypes.byref(path), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, path.value
+    rc, msg, path, launches = E.call("gt4mi_line_filter", as_arg(dst), as_arg(src), nfields, response, int64s(rext), twiddles, result,
+                                     int64s(extent), axis, size, mode, flags | _lib.FILTER_DRY_RUN, None, outs=(77, 77))
+    return rc, msg, launches, path
 
 
 def _spectrum(src, **kwargs):
@@ -305,7 +281,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == 0, msg
     rc, msg, *_ = _call(_field(DST), _field(SRC), twiddles=DST + 160)
     assert rc == UNS and b"dst 0 and twiddles overlap in memory" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, *_ = _call(two(_field(DST), _field(DST + 0x10000)), two(_field(SRC), _field(DST)), nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, *_ = _call(two(_field(DST), _field(DST + 64)), two(_field(SRC), _field(SRC + 0x10000)), nfields=2)
@@ -340,8 +316,8 @@ def _restated_path(strides, response_extent, extent, axis, itemsize=8):
 
 
 def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x10000) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x10000) for n in range(9)])
+    d = E.table(_field(DST + n * 0x10000) for n in range(9))
+    s = E.table(_field(SRC + n * 0x10000) for n in range(9))
     assert [_call(d, s, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
     assert [_spectrum(s, nfields=n)[2] for n in (1, 8, 9)] == [1, 1, 2]
     seen = set()
@@ -368,18 +344,15 @@ def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
     for axis, want in ((0, T), (1, LN), (2, LN)):
         assert _call(_field(DST, shape), _field(SRC, shape), extent=(8, 8, 8), axis=axis)[3] == want
     for axis, want in ((0, LN), (1, LN), (2, T)):
-        assert _call(_c_order(DST, shape), _c_order(SRC, shape), extent=(8, 8, 8), axis=axis)[3] == want
-        assert _call(_field(DST, shape), _c_order(SRC, shape), extent=(8, 8, 8), axis=axis)[3] == IT
-    assert _call(_c_order(DST, shape), _c_order(SRC, shape), extent=(8, 8, 8), axis=0, rext=(8, 1))[3] == LN  # lanes along K, one row per j
-    assert _call(_c_order(DST, shape), _c_order(SRC, shape), extent=(8, 8, 8), axis=0, rext=(8, 8))[3] == IT
-    assert _call(_c_order(DST, shape), _c_order(SRC, shape), extent=(8, 8, 8), axis=2, rext=(8, 8))[3] == T
+        assert _call(_field(DST, shape, layout="kfirst"), _field(SRC, shape, layout="kfirst"), extent=(8, 8, 8), axis=axis)[3] == want
+        assert _call(_field(DST, shape), _field(SRC, shape, layout="kfirst"), extent=(8, 8, 8), axis=axis)[3] == IT
+    assert _call(_field(DST, shape, layout="kfirst"), _field(SRC, shape, layout="kfirst"), extent=(8, 8, 8), axis=0, rext=(8, 1))[3] == LN  # lanes along K, one row per j
+    assert _call(_field(DST, shape, layout="kfirst"), _field(SRC, shape, layout="kfirst"), extent=(8, 8, 8), axis=0, rext=(8, 8))[3] == IT
+    assert _call(_field(DST, shape, layout="kfirst"), _field(SRC, shape, layout="kfirst"), extent=(8, 8, 8), axis=2, rext=(8, 8))[3] == T
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*line_filter_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"line_filter_kernel")
     # (float, double) x (a tile of 2048 points beside the twiddles, one line of 4096)
     assert len(kernels) == 4 and len({name for name, *_ in kernels}) == 4, kernels
     assert sorted(int(lds) for *_, lds in kernels) == [48 * 1024, 48 * 1024, 64 * 1024, 64 * 1024]
@@ -388,16 +361,6 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 @pytest.mark.parametrize("kwargs, error, match", [
     (dict(halo=2.0), ValueError, "halo must be"),
     (dict(halo=-1), ValueError, "must not be negative"),
@@ -410,12 +373,12 @@ def _host(shape=(8, 9, 5), dtype="float64"):
     (dict(), TypeError, "device fields"),  # all checks passed: refused for being host memory
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
-    dst, src = _host((8, 9, 5)), _host((8, 9, 5))
+    dst, src = E.host_field((8, 9, 5)), E.host_field((8, 9, 5))
     n = {"J": 9, "K": 5}.get(kwargs.get("axis"), 6 if "origin" in kwargs else 8)
     with pytest.raises(error, match=match):
-        linefilter.filter_lines(dst, src, response=_host((n // 2 + 1,)), **kwargs)
+        linefilter.filter_lines(dst, src, response=E.host_field((n // 2 + 1,)), **kwargs)
     with pytest.raises(error, match=match):
-        linefilter.LineFilter([dst], [src], response=_host((n // 2 + 1,)), **kwargs)
+        linefilter.LineFilter([dst], [src], response=E.host_field((n // 2 + 1,)), **kwargs)
     with pytest.raises(error, match=match):
         linefilter.LineSpectrum([src], **kwargs)
     with pytest.raises(error, match=match):
@@ -424,45 +387,45 @@ def test_python_refusals_need_no_gpu(kwargs, error, match):
 
 def test_python_refusals_about_the_fields_and_the_response():
     F = linefilter.filter_lines
-    dst, src, r = _host(), _host(), _host((5,))
+    dst, src, r = E.host_field(HOST), E.host_field(HOST), E.host_field((5,))
     with pytest.raises(ValueError, match="at least one"):
         F([], [], response=r)
     with pytest.raises(ValueError, match="at least one"):
         linefilter.spectrum_lines([])
     with pytest.raises(ValueError, match="2 destination.s. and 1 source.s. were passed"):
-        F([dst, _host()], [src], response=r)
+        F([dst, E.host_field(HOST)], [src], response=r)
     with pytest.raises(ValueError, match="takes IJK fields"):
-        F(_host((8, 9)), src, response=r)
+        F(E.host_field((8, 9)), src, response=r)
     # one dtype for the fields, float32 or float64
     with pytest.raises(TypeError, match="the fields of one call share a dtype: float64 and float32 differ"):
-        F(dst, _host(dtype="float32"), response=r)
+        F(dst, E.host_field(HOST, dtype="float32"), response=r)
     with pytest.raises(TypeError, match="float32 or float64 fields, not int64"):
-        F(_host(dtype="int64"), _host(dtype="int64"), response=r)
+        F(E.host_field(HOST, dtype="int64"), E.host_field(HOST, dtype="int64"), response=r)
     # the response: float64, (nh,) or (ea, eb, nh) C-ordered, nh = n // 2 + 1, an extent 1 or the box's
     with pytest.raises(TypeError, match="response must be float64, not float32"):
-        F(dst, src, response=_host((5,), "float32"))
+        F(dst, src, response=E.host_field((5,), "float32"))
     with pytest.raises(TypeError, match="response must be float64, not float32"):
-        F(_host(dtype="float32"), _host(dtype="float32"), response=_host((5,), "float32"))
+        F(E.host_field(HOST, dtype="float32"), E.host_field(HOST, dtype="float32"), response=E.host_field((5,), "float32"))
     with pytest.raises(ValueError, match=r"response must have shape \(nh,\) or \(ea, eb, nh\), not \(9, 5\)"):
-        F(dst, src, response=_host((9, 5)))
+        F(dst, src, response=E.host_field((9, 5)))
     for shape in ((4,), (8,), (9, 5, 4)):
         with pytest.raises(ValueError, match=f"response holds {shape[-1]} wavenumbers, a line of 8 points along I needs n // 2 \\+ 1 = 5"):
-            F(dst, src, response=_host(shape))
+            F(dst, src, response=E.host_field(shape))
     with pytest.raises(ValueError, match="response must be C-ordered and dense"):
-        F(dst, src, response=_host((9, 5, 10))[:, :, ::2])
+        F(dst, src, response=E.host_field((9, 5, 10))[:, :, ::2])
     with pytest.raises(ValueError, match="line_filter: response extent 4 along axis 1 is neither 1 nor the box's 9"):
-        F(dst, src, response=_host((4, 5, 5)))
+        F(dst, src, response=E.host_field((4, 5, 5)))
     with pytest.raises(ValueError, match="line_filter: response extent 9 along axis 2 is neither 1 nor the box's 5"):
-        F(dst, src, response=_host((9, 9, 5)))
+        F(dst, src, response=E.host_field((9, 9, 5)))
     for shape in ((5,), (1, 1, 5), (9, 1, 5), (1, 5, 5), (9, 5, 5)):
         with pytest.raises(TypeError, match="device fields"):
-            F(dst, src, response=_host(shape))
+            F(dst, src, response=E.host_field(shape))
     with pytest.raises(ValueError, match="share their length along I: 8 and 16 differ"):
-        F(dst, _host((16, 9, 5)), response=r)
+        F(dst, E.host_field((16, 9, 5)), response=r)
     # overlaps come from the library; in place is fine up to the device check
     with pytest.raises(TypeError, match="line_filter: dst 0 and src 1 overlap in memory"):
-        F([dst, _host()], [src, dst], response=r)
-    other = _host()
+        F([dst, E.host_field(HOST)], [src, dst], response=r)
+    other = E.host_field(HOST)
     with pytest.raises(TypeError, match="line_filter: dst 0 and dst 1 overlap in memory"):
         F([dst, dst], [src, other], response=r)
     with pytest.raises(TypeError, match="line_filter: dst 0 and response overlap in memory"):
@@ -476,13 +439,10 @@ def test_python_refusals_about_the_fields_and_the_response():
 def test_frozen_objects_know_their_box_and_refuse_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on objects whose device check is made
     to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
+    E.on_device(monkeypatch)
     for count, launches in ((1, 1), (8, 1), (9, 2)):
-        dsts, srcs = [_host((10, 16, 5), "float32") for _ in range(count)], [_host((12, 16, 5), "float32") for _ in range(count)]
-        r = _host((10, 1, 9))
+        dsts, srcs = [E.host_field((10, 16, 5), "float32") for _ in range(count)], [E.host_field((12, 16, 5), "float32") for _ in range(count)]
+        r = E.host_field((10, 1, 9))
         lf = linefilter.LineFilter(dsts, srcs, axis="J", response=r, halo=((1, 1), (0, 0)))
         assert (lf.n, lf.lines, lf.launches, lf.extent, lf.domain, lf.origin, lf.axis, lf.path) == \
             (16, 50, launches, (10, 16, 5), (8, 16, 5), (1, 0, 0), "J", "lanes")
@@ -491,11 +451,9 @@ def test_frozen_objects_know_their_box_and_refuse_to_run_after_an_array_died(mon
         assert sp.result.shape == (count, 2, 12, 5, 9) and sp.coefficients() is sp.result
         with pytest.raises(RuntimeError, match="has not been called yet"):
             sp.get()
-    a = _host((8, 18, 5))
-    assert linefilter.LineFilter(a, a, axis="I", response=_host((18, 1, 5))).path == "lanes"  # torch's C order: K is contiguous
-    assert linefilter.LineFilter(a, a, axis="I", response=_host((18, 5, 5))).path == "items"  # (one response row per line: no lanes across lines)
-    assert linefilter.LineFilter(a, a, axis="K", response=_host((8, 18, 3)), origin=(0, 0, 1)).path == "tiles"
+    a = E.host_field((8, 18, 5))
+    assert linefilter.LineFilter(a, a, axis="I", response=E.host_field((18, 1, 5))).path == "lanes"  # torch's C order: K is contiguous
+    assert linefilter.LineFilter(a, a, axis="I", response=E.host_field((18, 5, 5))).path == "items"  # (one response row per line: no lanes across lines)
+    assert linefilter.LineFilter(a, a, axis="K", response=E.host_field((8, 18, 3)), origin=(0, 0, 1)).path == "tiles"
     del r
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        lf()
+    E.refuses_a_dead_array(lf)

@@ -4,18 +4,16 @@ and both against ``numpy.argmax`` / ``numpy.argmin``, directed crossing cases, e
 checks."""
 
 import ctypes
-import gc
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import line_find_ref as R
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, linefind
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 NAN = float("nan")
 
 
@@ -143,28 +141,17 @@ def test_directed_crossing_cases():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_line_find\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* fields", "int nfields", "const gt4mi_field* coord", "const int64_t extent[3]", "int axis",
-                      "int elem_size", "int what", "int direction", "const double* level", "double missing", "double* result", "int flags",
-                      "void* stream", "int* path", "int* launches"]
-    fn = _lib.load().gt4mi_line_find
     fp, i64p, c_int, ip = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_int)
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, c_int, fp, i64p, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p,
-                           c_int, ctypes.c_void_p, ip, ip]
-    assert "gt4mi_line_find" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_line_find")
-    comment = text[: text.index("int gt4mi_line_find(")].rsplit("/* ----", 1)[1]
-    for phrase in ("y[q] < L && y[q+1] >= L", "y[q] > L && y[q+1] <= L", "t = (L - y[q]) / (y[q+1] - y[q])", "double(n-1-q) - t",
-                   "zc[q] + t * (zc[q+1] - zc[q])", "no FMA", "numpy.argmax", "the first NaN met wins", "no early exit", "cupy"):
-        assert phrase in comment, phrase
-    for name in ("CROSSING", "ARGMAX", "ARGMIN", "ANY", "RISING", "FALLING", "POSITION", "COORD", "EXTRA", "ROWS", "REVERSE", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_FIND_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"FIND_{name}") == value, name
+    E.check_binding("gt4mi_line_find",
+                    ["const gt4mi_field* fields", "int nfields", "const gt4mi_field* coord", "const int64_t extent[3]", "int axis",
+                     "int elem_size", "int what", "int direction", "const double* level", "double missing", "double* result", "int flags",
+                     "void* stream", "int* path", "int* launches"],
+                    argtypes=[fp, c_int, fp, i64p, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p,
+                              c_int, ctypes.c_void_p, ip, ip],
+                    prefix="FIND", constants=("CROSSING", "ARGMAX", "ARGMIN", "ANY", "RISING", "FALLING", "POSITION", "COORD", "EXTRA", "ROWS",
+                                              "REVERSE", "DRY_RUN"),
+                    phrases=("y[q] < L && y[q+1] >= L", "y[q] > L && y[q+1] <= L", "t = (L - y[q]) / (y[q+1] - y[q])", "double(n-1-q) - t",
+                             "zc[q] + t * (zc[q+1] - zc[q])", "no FMA", "numpy.argmax", "the first NaN met wins", "no early exit", "cupy"))
 
 
 FLD, CRD, RES = 0x10_0000, 0x4000_0000, 0x8000_0000  # made-up addresses, far apart
@@ -173,32 +160,16 @@ CROSSING, ARGMAX, ARGMIN = _lib.FIND_CROSSING, _lib.FIND_ARGMAX, _lib.FIND_ARGMI
 LEVEL = object()
 
 
-def _field(ptr, shape=SHAPE, strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj, nk = shape
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, shape, strides, origin)
-
-
-def _c_order(ptr, itemsize=8):
-    return _field(ptr, strides=(7 * 5 * itemsize, 5 * itemsize, itemsize), itemsize=itemsize)
-
-
-def _line(ptr, n, axis, itemsize=8):
-    shape, strides = [1, 1, 1], [0, 0, 0]
-    shape[axis], strides[axis] = n, itemsize
-    return _lib.Field.make(ptr, shape, strides, (0, 0, 0))
+def _field(ptr, shape=SHAPE, *rest, **kwargs):  # (this file's shape)
+    return E.field(ptr, shape, *rest, **kwargs)
 
 
 def _call(fields, coord=None, nfields=1, extent=(4, 5, 5), axis=0, size=8, what=CROSSING, direction=0, level=LEVEL, result=RES, flags=0):
-    lib = _lib.load()
-    path, launches = ctypes.c_int(77), ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
     if level is LEVEL:
         level = (ctypes.c_double * max(nfields, 1))(*([273.15] * max(nfields, 1))) if what == CROSSING else None
-    rc = lib.gt4mi_line_find(as_arg(fields), nfields, as_arg(coord), (ctypes.c_int64 * 3)(*extent) if extent is not None else None, axis, size,
-                             what, direction, level, NAN, result, flags | _lib.FIND_DRY_RUN, None, ctypes.byref(path), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, path.value
+    rc, msg, path, launches = E.call("gt4mi_line_find", as_arg(fields), nfields, as_arg(coord), int64s(extent), axis, size, what, direction,
+                                     level, NAN, result, flags | _lib.FIND_DRY_RUN, None, outs=(77, 77))
+    return rc, msg, launches, path
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -270,7 +241,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == OOB and b"field 0: negative origin -1 along axis 1" in msg
     rc, msg, *_ = _call(_field(FLD, origin=(3, 1, 0)))
     assert rc == OOB and b"field 0: origin 3 + extent 4 along axis 0 is outside the array (shape 6)" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, *_ = _call(two(_field(FLD), _field(FLD + 0x10000, origin=(3, 1, 0))), nfields=2)
     assert rc == OOB and b"field 1: origin 3" in msg
     # strides and alignment
@@ -283,11 +254,11 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     # a 1-d coord along the line axis: broadcast, exempt from the shape check on the other axes, n items needed
     for axis in range(3):
         n = (4, 5, 5)[axis]
-        rc, msg, launches, _ = _call(_field(FLD), _line(CRD, n, axis), axis=axis)
+        rc, msg, launches, _ = _call(_field(FLD), E.line(CRD, n, axis), axis=axis)
         assert rc == 0 and launches == 1, msg
-        rc, msg, *_ = _call(_field(FLD), _line(CRD, n - 1, axis), axis=axis)
+        rc, msg, *_ = _call(_field(FLD), E.line(CRD, n - 1, axis), axis=axis)
         assert rc == OOB and b"coord 0" in msg and b"axis %d" % axis in msg, msg
-    rc, msg, *_ = _call(_field(FLD), _line(CRD, 5, 1), axis=0)  # 1-d along the wrong axis
+    rc, msg, *_ = _call(_field(FLD), E.line(CRD, 5, 1), axis=0)  # 1-d along the wrong axis
     assert rc == OOB and b"coord 0" in msg
     # the result: aligned to 8 bytes, clear of every field and of the coord (a 4 x 5 x 5 box along I: 25 lines, 3 doubles each per field)
     rc, msg, launches, _ = _call(_field(FLD), result=RES + 4)
@@ -303,7 +274,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == INV and b"result overlaps field 1" in msg
     rc, msg, *_ = _call(_field(FLD), _field(RES))
     assert rc == INV and b"result overlaps coord" in msg
-    rc, msg, *_ = _call(_field(FLD), _line(RES + 64, 4, 0))
+    rc, msg, *_ = _call(_field(FLD), E.line(RES + 64, 4, 0))
     assert rc == INV and b"result overlaps coord" in msg
     rc, msg, *_ = _call(_field(FLD), _field(FLD))  # a field as its own coord is fine: nothing is written
     assert rc == 0, msg
@@ -332,7 +303,7 @@ def _restated_path(strides, coord_strides, extent, axis, itemsize=8):
 
 
 def test_launches_are_one_per_eight_fields_and_the_path_follows_the_strides():
-    f = (_lib.Field * 9)(*[_field(FLD + n * 0x10000) for n in range(9)])
+    f = E.table(_field(FLD + n * 0x10000) for n in range(9))
     assert [_call(f, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
     L, T, IT = _lib.LINE_PATH_LANES, _lib.LINE_PATH_TILES, _lib.LINE_PATH_ITEMS
     ifirst, kfirst, jfirst = (8, 48, 336), (280, 40, 8), (56, 8, 336)
@@ -344,8 +315,8 @@ def test_launches_are_one_per_eight_fields_and_the_path_follows_the_strides():
                     line = [0, 0, 0]
                     line[axis] = 8
                     for sz in (None, ifirst, kfirst, tuple(line)):
-                        z = None if sz is None else _line(CRD, extent[axis], axis) if sz == tuple(line) else _field(CRD, strides=sz)
-                        pair = (_lib.Field * 2)(_field(FLD, strides=s0), _field(FLD + 0x10000, strides=s1))
+                        z = None if sz is None else E.line(CRD, extent[axis], axis) if sz == tuple(line) else _field(CRD, strides=sz)
+                        pair = E.table((_field(FLD, strides=s0), _field(FLD + 0x10000, strides=s1)))
                         rc, msg, launches, path = _call(pair, z, nfields=2, extent=extent, axis=axis, what=ARGMIN)
                         assert rc == 0 and path == _restated_path([s0, s1], sz, extent, axis), (extent, axis, s0, s1, sz, path, msg)
                         seen.add((axis, path))
@@ -354,17 +325,14 @@ def test_launches_are_one_per_eight_fields_and_the_path_follows_the_strides():
     for axis, want in ((0, T), (1, L), (2, L)):
         assert _call(_field(FLD), axis=axis)[3] == want
     for axis, want in ((0, L), (1, L), (2, T)):
-        assert _call(_c_order(FLD), _c_order(CRD), axis=axis)[3] == want
+        assert _call(_field(FLD, layout="kfirst"), _field(CRD, layout="kfirst"), axis=axis)[3] == want
     for axis in range(3):  # a coord of another layout than the fields: item by item
-        assert _call(_field(FLD), _c_order(CRD), axis=axis)[3] == IT
+        assert _call(_field(FLD), _field(CRD, layout="kfirst"), axis=axis)[3] == IT
     assert _call(_field(FLD), extent=(1, 5, 5), axis=0)[3] == IT  # a line of one point has no run to tile
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*line_find\S*kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"line_find\S*kernel")
     # (float, float64) x the register budgets for 1, 4 and 8 entries x (lanes, items, tiles)
     assert len(kernels) == 18 and len({name for name, *_ in kernels}) == 18, kernels
     for name, scratch, waves, lds in kernels:
@@ -373,16 +341,6 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 @pytest.mark.parametrize("kwargs, error, match", [
     (dict(level=1.0, halo=2.0), ValueError, "halo must be"),
     (dict(level=1.0, halo=-1), ValueError, "must not be negative"),
@@ -402,7 +360,7 @@ def _host_field(shape=(8, 9, 5), dtype="float64"):
     (dict(level=273.15, axis="I", direction="falling"), TypeError, "device fields"),  # all checks passed: refused for being host memory
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
-    field = _host_field()
+    field = E.host_field(HOST)
     with pytest.raises(error, match=match):
         linefind.find_lines(field, **kwargs)
     with pytest.raises(error, match=match):
@@ -413,7 +371,7 @@ def test_python_refusals_about_the_fields_themselves():
     import torch
 
     F = linefind.find_lines
-    field, z = _host_field(), _host_field()
+    field, z = E.host_field(HOST), E.host_field(HOST)
     with pytest.raises(ValueError, match="at least one field"):
         F(level=1.0)
     with pytest.raises(ValueError, match="at least one field"):
@@ -423,34 +381,31 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         F(field, level=1.0, coord=np.zeros(5))
     with pytest.raises(ValueError, match="takes IJK fields"):
-        F(_host_field((8, 9)), level=1.0)
+        F(E.host_field((8, 9)), level=1.0)
     with pytest.raises(ValueError, match="coord must be an IJK field or a 1-d array along J"):
-        F(field, level=1.0, coord=_host_field((8, 9)), axis="J")
+        F(field, level=1.0, coord=E.host_field((8, 9)), axis="J")
     with pytest.raises(TypeError, match="share a dtype: float64 and float32 differ"):
-        F(field, _host_field(dtype="float32"), level=1.0)
+        F(field, E.host_field(HOST, dtype="float32"), level=1.0)
     with pytest.raises(TypeError, match="share a dtype: float64 and float32 differ"):
-        F(field, level=1.0, coord=_host_field((5,), "float32"))
+        F(field, level=1.0, coord=E.host_field((5,), "float32"))
     with pytest.raises(TypeError, match="float32 or float64 fields, not int64"):
-        F(_host_field(dtype="int64"), what="argmax")
+        F(E.host_field(HOST, dtype="int64"), what="argmax")
     with pytest.raises(ValueError, match="coord has 8 items, a line of 5 points along K needs 5"):
-        F(field, level=1.0, coord=_host_field((8,)))
+        F(field, level=1.0, coord=E.host_field((8,)))
     with pytest.raises(ValueError, match="share their length along K: 5 and 6 differ"):
-        F(field, _host_field((8, 9, 6)), level=1.0)
+        F(field, E.host_field((8, 9, 6)), level=1.0)
     with pytest.raises(TypeError, match="device fields"):
-        F(field, _host_field((9, 11, 5)), what="argmin", coord=_host_field((5,)))  # along I and J the smaller array sets the domain
+        F(field, E.host_field((9, 11, 5)), what="argmin", coord=E.host_field((5,)))  # along I and J the smaller array sets the domain
     with pytest.raises(TypeError, match="device fields"):
         F(field, level=1.0, coord=field)  # a field as its own coord
 
 
 def test_a_frozen_search_knows_its_box_its_sections_and_its_levels(monkeypatch):
     """The device check is made to pass for host memory: the call itself is never reached."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
+    E.on_device(monkeypatch)
     for count, launches in ((1, 1), (8, 1), (9, 2)):
-        fields = [_host_field((10, 9, 5), "float32") for _ in range(count)]
-        z = _host_field((9,), "float32")
+        fields = [E.host_field((10, 9, 5), "float32") for _ in range(count)]
+        z = E.host_field((9,), "float32")
         lf = linefind.LineFind(fields, axis="J", level=[float(k) for k in range(count)], direction="rising", reverse=True, coord=z, missing=-1.0,
                                halo=((1, 1), (0, 0)))
         assert (lf.n, lf.lines, lf.launches, lf.extent, lf.domain, lf.origin, lf.axis, lf.what, lf.path) == \
@@ -493,6 +448,4 @@ def test_a_frozen_search_knows_its_box_its_sections_and_its_levels(monkeypatch):
     with pytest.raises(ValueError, match=r"\(3, nB, nA\)"):
         linefind.Found.from_rows(block[:2], "argmin")
     del z
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        lf()
+    E.refuses_a_dead_array(lf)

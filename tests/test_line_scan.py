@@ -4,19 +4,15 @@ between signed zeros is not relied on, the contract's own is pinned by directed 
 run (made-up addresses that are never dereferenced), the declaration, the kernels' resources and the Python interface's argument
 checks."""
 
-import ctypes
-import gc
-import pathlib
-import re
-
 import numpy as np
 import pytest
 
+import entry_checks as E
 import line_scan_ref as R
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, linescan
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 FLAG_SETS = [(False, False), (True, False), (False, True), (True, True)]  # (exclusive, reverse)
 
 
@@ -130,25 +126,11 @@ def test_max_and_min_agree_with_numpy_by_value_and_the_tie_rule_is_the_contracts
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_line_scan\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* weight", "const int64_t extent[3]",
-                      "int axis", "int elem_size", "int op", "int flags", "void* stream", "int* path", "int* launches"]
-    fn = _lib.load().gt4mi_line_scan
-    fp, i64p, c_int, ip = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_int)
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, fp, i64p, c_int, c_int, c_int, c_int, ctypes.c_void_p, ip, ip]
-    assert "gt4mi_line_scan" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_line_scan")
-    comment = text[: text.index("int gt4mi_line_scan(")].rsplit("/* ----", 1)[1]
-    for phrase in ("s[0] = t[0]", "s[m] = s[m-1] + t[m]", "s[m-1] != s[m-1] or s[m-1] > x[m]", "no FMA", "numpy.cumsum", "in-place", "cupy"):
-        assert phrase in comment, phrase
-    for name in ("SUM", "MAX", "MIN", "EXCLUSIVE", "REVERSE", "WIDE", "DRY_RUN", "PATH_LANES", "PATH_TILES", "PATH_ITEMS"):
-        value = int(re.search(rf"GT4MI_SCAN_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"SCAN_{name}") == value, name
+    E.check_binding("gt4mi_line_scan",
+                  ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* weight", "const int64_t extent[3]",
+                   "int axis", "int elem_size", "int op", "int flags", "void* stream", "int* path", "int* launches"],
+                  prefix="SCAN", constants=("SUM", "MAX", "MIN", "EXCLUSIVE", "REVERSE", "WIDE", "DRY_RUN", "PATH_LANES", "PATH_TILES", "PATH_ITEMS"),
+                  phrases=("s[0] = t[0]", "s[m] = s[m-1] + t[m]", "s[m-1] != s[m-1] or s[m-1] > x[m]", "no FMA", "numpy.cumsum", "in-place", "cupy"))
 
 
 DST, SRC, WGT = 0x10_0000, 0x4000_0000, 0x8000_0000  # made-up addresses, far apart
@@ -156,30 +138,14 @@ SHAPE = (6, 7, 5)
 SUM, MAX, MIN = _lib.SCAN_SUM, _lib.SCAN_MAX, _lib.SCAN_MIN
 
 
-def _field(ptr, shape=SHAPE, strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj, nk = shape
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, shape, strides, origin)
-
-
-def _c_order(ptr, itemsize=8):
-    return _field(ptr, strides=(7 * 5 * itemsize, 5 * itemsize, itemsize), itemsize=itemsize)
-
-
-def _line(ptr, n, axis, itemsize=8):
-    shape, strides = [1, 1, 1], [0, 0, 0]
-    shape[axis], strides[axis] = n, itemsize
-    return _lib.Field.make(ptr, shape, strides, (0, 0, 0))
+def _field(ptr, shape=SHAPE, *rest, **kwargs):  # (this file's shape)
+    return E.field(ptr, shape, *rest, **kwargs)
 
 
 def _call(dst, src, weight=None, nfields=1, extent=(4, 5, 5), axis=0, size=8, op=SUM, flags=0):
-    lib = _lib.load()
-    path, launches = ctypes.c_int(77), ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_line_scan(as_arg(dst), as_arg(src), nfields, as_arg(weight), (ctypes.c_int64 * 3)(*extent) if extent is not None else None,
-                             axis, size, op, flags | _lib.SCAN_DRY_RUN, None, ctypes.byref(path), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, path.value
+    rc, msg, path, launches = E.call("gt4mi_line_scan", as_arg(dst), as_arg(src), nfields, as_arg(weight), int64s(extent), axis, size, op,
+                                   flags | _lib.SCAN_DRY_RUN, None, outs=(77, 77))
+    return rc, msg, launches, path
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -251,11 +217,11 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     # a 1-d weight along the line axis: broadcast, exempt from the shape check on the other axes, n items needed
     for axis in range(3):
         n = (4, 5, 5)[axis]
-        rc, msg, launches, _ = _call(_field(DST), _field(SRC), _line(WGT, n, axis), axis=axis)
+        rc, msg, launches, _ = _call(_field(DST), _field(SRC), E.line(WGT, n, axis), axis=axis)
         assert rc == 0 and launches == 1, msg
-        rc, msg, *_ = _call(_field(DST), _field(SRC), _line(WGT, n - 1, axis), axis=axis)
+        rc, msg, *_ = _call(_field(DST), _field(SRC), E.line(WGT, n - 1, axis), axis=axis)
         assert rc == OOB and b"weight 0" in msg and b"axis %d" % axis in msg, msg
-    rc, msg, *_ = _call(_field(DST), _field(SRC), _line(WGT, 5, 1), axis=0)  # 1-d along the wrong axis
+    rc, msg, *_ = _call(_field(DST), _field(SRC), E.line(WGT, 5, 1), axis=0)  # 1-d along the wrong axis
     assert rc == OOB and b"weight 0" in msg
     # overlap in memory: a dst against a shifted src, another pair's src, the weight, another dst
     rc, msg, launches, _ = _call(_field(DST), _field(DST + 8))
@@ -264,9 +230,9 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == UNS and b"dst 0 and src 0 overlap in memory" in msg
     rc, msg, *_ = _call(_field(DST), _field(SRC), _field(DST))
     assert rc == UNS and b"dst 0 and weight overlap in memory" in msg
-    rc, msg, *_ = _call(_field(DST), _field(SRC), _line(DST + 80, 4, 0))
+    rc, msg, *_ = _call(_field(DST), _field(SRC), E.line(DST + 80, 4, 0))
     assert rc == UNS and b"dst 0 and weight overlap in memory" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, *_ = _call(two(_field(DST), _field(DST + 0x10000)), two(_field(SRC), _field(DST)), nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, *_ = _call(two(_field(DST), _field(DST + 64)), two(_field(SRC), _field(SRC + 0x10000)), nfields=2)
@@ -303,8 +269,8 @@ def _restated_path(strides, weight_strides, extent, axis, itemsize=8):
 
 
 def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x10000) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x10000) for n in range(9)])
+    d = E.table(_field(DST + n * 0x10000) for n in range(9))
+    s = E.table(_field(SRC + n * 0x10000) for n in range(9))
     assert [_call(d, s, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
     L, T, IT = _lib.SCAN_PATH_LANES, _lib.SCAN_PATH_TILES, _lib.SCAN_PATH_ITEMS
     ifirst, kfirst, jfirst = (8, 48, 336), (280, 40, 8), (56, 8, 336)
@@ -316,7 +282,7 @@ def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
                     line = [0, 0, 0]
                     line[axis] = 8
                     for sw in (None, ifirst, kfirst, tuple(line)):
-                        w = None if sw is None else _line(WGT, extent[axis], axis) if sw == tuple(line) else _field(WGT, strides=sw)
+                        w = None if sw is None else E.line(WGT, extent[axis], axis) if sw == tuple(line) else _field(WGT, strides=sw)
                         rc, msg, launches, path = _call(_field(DST, strides=sd), _field(SRC, strides=ss), w, extent=extent, axis=axis)
                         assert rc == 0 and path == _restated_path([sd, ss], sw, extent, axis), (extent, axis, sd, ss, sw, path, msg)
                         seen.add((axis, path))
@@ -325,18 +291,15 @@ def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
     for axis, want in ((0, T), (1, L), (2, L)):
         assert _call(_field(DST), _field(SRC), axis=axis)[3] == want
     for axis, want in ((0, L), (1, L), (2, T)):
-        assert _call(_c_order(DST), _c_order(SRC), _c_order(WGT), axis=axis)[3] == want
+        assert _call(_field(DST, layout="kfirst"), _field(SRC, layout="kfirst"), _field(WGT, layout="kfirst"), axis=axis)[3] == want
     for axis in range(3):  # fields that disagree: item by item
-        assert _call(_field(DST), _c_order(SRC), axis=axis)[3] == IT
-        assert _call(_field(DST), _field(SRC), _c_order(WGT), axis=axis)[3] == IT
+        assert _call(_field(DST), _field(SRC, layout="kfirst"), axis=axis)[3] == IT
+        assert _call(_field(DST), _field(SRC), _field(WGT, layout="kfirst"), axis=axis)[3] == IT
     assert _call(_field(DST), _field(SRC), extent=(1, 5, 5), axis=0)[3] == IT  # a line of one point has no run to tile
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*line_scan\S*kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"line_scan\S*kernel")
     # (float, float64, float accumulated in float64) x the register budgets for 1, 4 and 8 entries x (lanes, items, tiles)
     assert len(kernels) == 27 and len({name for name, *_ in kernels}) == 27, kernels
     for name, scratch, waves, lds in kernels:
@@ -345,16 +308,6 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 @pytest.mark.parametrize("kwargs, error, match", [
     (dict(halo=2.0), ValueError, "halo must be"),
     (dict(halo=-1), ValueError, "must not be negative"),
@@ -370,7 +323,7 @@ def _host_field(shape=(8, 9, 5), dtype="float64"):
     (dict(), TypeError, "device fields"),  # all checks passed: refused for being host memory
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
-    dst, src = _host_field(), _host_field()
+    dst, src = E.host_field(HOST), E.host_field(HOST)
     with pytest.raises(error, match=match):
         linescan.scan_lines(dst, src, **kwargs)
     with pytest.raises(error, match=match):
@@ -381,11 +334,11 @@ def test_python_refusals_about_the_fields_themselves():
     import torch
 
     S = linescan.scan_lines
-    dst, src, w = _host_field(), _host_field(), _host_field()
+    dst, src, w = E.host_field(HOST), E.host_field(HOST), E.host_field(HOST)
     with pytest.raises(ValueError, match="at least one"):
         S([], [])
     with pytest.raises(ValueError, match="2 destination.s. and 1 source.s. were passed"):
-        S([dst, _host_field()], [src])
+        S([dst, E.host_field(HOST)], [src])
     with pytest.raises(TypeError, match="host"):
         S(torch.zeros(8, 9, 5, dtype=torch.float64), src)  # as_device_array's own refusal
     with pytest.raises(TypeError):
@@ -393,31 +346,31 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         S(dst, src, weight=np.zeros(8))
     with pytest.raises(ValueError, match="takes IJK fields"):
-        S(_host_field((8, 9)), src)
+        S(E.host_field((8, 9)), src)
     with pytest.raises(ValueError, match="weight must be an IJK field or a 1-d array along J"):
-        S(dst, src, weight=_host_field((8, 9)), axis="J")
+        S(dst, src, weight=E.host_field((8, 9)), axis="J")
     # a weight goes with the sum
     for op in ("max", "min"):
         with pytest.raises(ValueError, match=f"a weight goes with op='sum' only, not with op='{op}'"):
             S(dst, src, weight=w, op=op)
     # one dtype for everything, float32 or float64
     with pytest.raises(TypeError, match="share a dtype: float64 and float32 differ"):
-        S(dst, _host_field(dtype="float32"))
+        S(dst, E.host_field(HOST, dtype="float32"))
     with pytest.raises(TypeError, match="share a dtype: float64 and float32 differ"):
-        S(dst, src, weight=_host_field((8,), "float32"))
+        S(dst, src, weight=E.host_field((8,), "float32"))
     with pytest.raises(TypeError, match="float32 or float64 fields, not int64"):
-        S(_host_field(dtype="int64"), _host_field(dtype="int64"))
+        S(E.host_field(HOST, dtype="int64"), E.host_field(HOST, dtype="int64"))
     # the weight's shape: a 1-d array holds exactly n items along the line axis; IJK arrays agree along it
     with pytest.raises(TypeError, match="device fields"):
-        S(dst, src, weight=_host_field((8,)))
+        S(dst, src, weight=E.host_field((8,)))
     with pytest.raises(ValueError, match="weight has 8 items, a line of 9 points along J needs 9"):
-        S(dst, src, weight=_host_field((8,)), axis="J")
+        S(dst, src, weight=E.host_field((8,)), axis="J")
     with pytest.raises(ValueError, match="weight has 8 items, a line of 10 points along I needs 10"):
-        S(_host_field((10, 9, 5)), _host_field((10, 9, 5)), weight=_host_field((8,)), halo=1)
+        S(E.host_field((10, 9, 5)), E.host_field((10, 9, 5)), weight=E.host_field((8,)), halo=1)
     with pytest.raises(ValueError, match="share their length along I: 8 and 10 differ"):
-        S(dst, _host_field((10, 9, 5)))
+        S(dst, E.host_field((10, 9, 5)))
     with pytest.raises(TypeError, match="device fields"):  # along J and K the smaller array sets the domain
-        S(dst, _host_field((8, 11, 6)))
+        S(dst, E.host_field((8, 11, 6)))
     # an origin or a box outside a shape (the library's words)
     with pytest.raises(ValueError, match="leave no domain"):
         S(dst, src, origin=(9, 0, 0))
@@ -427,8 +380,8 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError, match="line_scan: dst 0 and weight overlap in memory"):
         S(dst, src, weight=dst)
     with pytest.raises(TypeError, match="line_scan: dst 0 and src 1 overlap in memory"):
-        S([dst, _host_field()], [src, dst])
-    other = _host_field()
+        S([dst, E.host_field(HOST)], [src, dst])
+    other = E.host_field(HOST)
     with pytest.raises(TypeError, match="line_scan: dst 0 and dst 1 overlap in memory"):
         S([dst, dst], [src, other])
     with pytest.raises(TypeError, match="device fields"):
@@ -440,19 +393,14 @@ def test_python_refusals_about_the_fields_themselves():
 def test_a_frozen_scan_knows_its_box_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a LineScan whose device check
     is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
+    E.on_device(monkeypatch)
     for count, launches in ((1, 1), (8, 1), (9, 2)):
-        dsts, srcs = [_host_field((10, 9, 5), "float32") for _ in range(count)], [_host_field((12, 9, 5), "float32") for _ in range(count)]
-        w = _host_field((9,), "float32")
+        dsts, srcs = [E.host_field((10, 9, 5), "float32") for _ in range(count)], [E.host_field((12, 9, 5), "float32") for _ in range(count)]
+        w = E.host_field((9,), "float32")
         sc = linescan.LineScan(dsts, srcs, axis="J", weight=w, wide=True, exclusive=True, halo=1)
         assert (sc.n, sc.lines, sc.launches, sc.extent, sc.domain, sc.origin, sc.axis, sc.op, sc.path) == \
             (9, 50, launches, (10, 9, 5), (8, 7, 5), (1, 1, 0), "J", "sum", "lanes")
         assert (sc.exclusive, sc.reverse, sc.wide) == (True, False, True) and not hasattr(sc, "workspace")
     assert linescan.LineScan(dsts[0], dsts[0], axis="K", op="min", reverse=True).path == "tiles"  # torch's C order: K is contiguous
     del w
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        sc()
+    E.refuses_a_dead_array(sc)

@@ -7,18 +7,16 @@ relative error max|x - x_numpy| / max|x_numpy| of a line is 4.452e-16 (MEASURED_
 test asserts 16 times that, which only absorbs another LAPACK build)."""
 
 import ctypes
-import gc
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import line_solve_ref as R
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, linesolve
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 MEASURED_WORST = 4.452e-16
 
 
@@ -98,53 +96,27 @@ def test_solve_along_moves_the_line_axis_and_broadcasts_1d_coefficients():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_line_solve\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* out", "const gt4mi_field* rhs", "int nfields", "const gt4mi_field* lower", "const gt4mi_field* diag",
-                      "const gt4mi_field* upper", "const int64_t extent[3]", "int axis", "int elem_size", "int flags", "void* workspace",
-                      "int64_t workspace_bytes", "void* stream", "int64_t* workspace_needed", "int* path", "int* launches"]
-    fn = _lib.load().gt4mi_line_solve
-    fp, i64p, c_int, i64, ip = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, fp, fp, fp, i64p, c_int, c_int, c_int, ctypes.c_void_p, i64, ctypes.c_void_p, i64p, ip, ip]
-    assert "gt4mi_line_solve" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_line_solve")
-    comment = text[: text.index("int gt4mi_line_solve(")].rsplit("/* ----", 1)[1]
-    for phrase in ("den = b[m] - a[m] * cp[m-1]", "gamma = -b[0]", "(alpha * beta) / gamma", "no reciprocal", "No pivoting", "in-place"):
-        assert phrase in comment, phrase
-    for name in ("PERIODIC", "DRY_RUN", "PATH_LANES", "PATH_TILES", "PATH_ITEMS"):
-        value = int(re.search(rf"GT4MI_LINE_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"LINE_{name}") == value, name
+    E.check_binding("gt4mi_line_solve",
+                    ["const gt4mi_field* out", "const gt4mi_field* rhs", "int nfields", "const gt4mi_field* lower", "const gt4mi_field* diag",
+                     "const gt4mi_field* upper", "const int64_t extent[3]", "int axis", "int elem_size", "int flags", "void* workspace",
+                     "int64_t workspace_bytes", "void* stream", "int64_t* workspace_needed", "int* path", "int* launches"],
+                    prefix="LINE", constants=("PERIODIC", "DRY_RUN", "PATH_LANES", "PATH_TILES", "PATH_ITEMS"),
+                    phrases=("den = b[m] - a[m] * cp[m-1]", "gamma = -b[0]", "(alpha * beta) / gamma", "no reciprocal", "No pivoting", "in-place"))
 
 
 OUT, RHS, LO, DI, UP, WS = 0x10_0000, 0x4000_0000, 0x8000_0000, 0xA000_0000, 0xC000_0000, 0xE000_0000  # made-up addresses, far apart
 SHAPE = (6, 7, 5)
 
 
-def _field(ptr, shape=SHAPE, strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj, nk = shape
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, shape, strides, origin)
-
-
-def _line(ptr, n, axis, itemsize=8):
-    shape, strides = [1, 1, 1], [0, 0, 0]
-    shape[axis], strides[axis] = n, itemsize
-    return _lib.Field.make(ptr, shape, strides, (0, 0, 0))
+def _field(ptr, shape=SHAPE, *rest, **kwargs):  # (this file's shape)
+    return E.field(ptr, shape, *rest, **kwargs)
 
 
 def _call(out, rhs, lo, di, up, nfields=1, extent=(4, 5, 5), axis=0, size=8, flags=0, ws=None, ws_bytes=0):
-    lib = _lib.load()
-    needed, path, launches = ctypes.c_int64(-7), ctypes.c_int(77), ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_line_solve(as_arg(out), as_arg(rhs), nfields, as_arg(lo), as_arg(di), as_arg(up),
-                              (ctypes.c_int64 * 3)(*extent) if extent is not None else None, axis, size, flags | _lib.LINE_DRY_RUN, ws, ws_bytes,
-                              None, ctypes.byref(needed), ctypes.byref(path), ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, needed.value, path.value
+    rc, msg, needed, path, launches = E.call("gt4mi_line_solve", as_arg(out), as_arg(rhs), nfields, as_arg(lo), as_arg(di), as_arg(up),
+                                             int64s(extent), axis, size, flags | _lib.LINE_DRY_RUN, ws, ws_bytes, None,
+                                             outs=(ctypes.c_int64(-7), 77, 77))
+    return rc, msg, launches, needed, path
 
 
 def _good():
@@ -223,11 +195,11 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     # 1-d coefficients along the line axis: broadcast, exempt from the shape check on the other axes, n items needed
     for axis in range(3):
         n = (4, 5, 5)[axis]
-        rc, msg, launches, *_ = _call(_field(OUT), _field(RHS), _line(LO, n, axis), _line(DI, n, axis), _line(UP, n, axis), axis=axis)
+        rc, msg, launches, *_ = _call(_field(OUT), _field(RHS), E.line(LO, n, axis), E.line(DI, n, axis), E.line(UP, n, axis), axis=axis)
         assert rc == 0 and launches == 1, msg
-        rc, msg, *_ = _call(_field(OUT), _field(RHS), _line(LO, n, axis), _line(DI, n - 1, axis), _line(UP, n, axis), axis=axis)
+        rc, msg, *_ = _call(_field(OUT), _field(RHS), E.line(LO, n, axis), E.line(DI, n - 1, axis), E.line(UP, n, axis), axis=axis)
         assert rc == OOB and b"diag 0" in msg and b"axis %d" % axis in msg, msg
-    rc, msg, *_ = _call(_field(OUT), _field(RHS), _line(LO, 5, 1), _field(DI), _field(UP), axis=0)  # 1-d along the wrong axis
+    rc, msg, *_ = _call(_field(OUT), _field(RHS), E.line(LO, 5, 1), _field(DI), _field(UP), axis=0)  # 1-d along the wrong axis
     assert rc == OOB and b"lower 0" in msg
     # the workspace: too small, misaligned, over a field; absent is fine in a dry run
     _, _, _, needed, _ = _call(*_good())
@@ -255,9 +227,9 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
         args[n] = _field(OUT)
         rc, msg, *_ = _call(*args)
         assert rc == UNS and what in msg, msg
-    rc, msg, *_ = _call(_field(OUT), _field(RHS), _line(LO, 4, 0), _line(OUT + 80, 4, 0), _line(UP, 4, 0))
+    rc, msg, *_ = _call(_field(OUT), _field(RHS), E.line(LO, 4, 0), E.line(OUT + 80, 4, 0), E.line(UP, 4, 0))
     assert rc == UNS and b"out 0 and diag overlap in memory" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, *_ = _call(two(_field(OUT), _field(OUT + 0x10000)), two(_field(RHS), _field(OUT)), _field(LO), _field(DI), _field(UP), nfields=2)
     assert rc == UNS and b"out 0 and rhs 1 overlap in memory" in msg
     rc, msg, *_ = _call(two(_field(OUT), _field(OUT + 64)), two(_field(RHS), _field(RHS + 0x10000)), _field(LO), _field(DI), _field(UP), nfields=2)
@@ -289,8 +261,8 @@ def test_a_call_without_a_workspace_is_refused_before_any_launch():
 
 
 def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
-    o = (_lib.Field * 9)(*[_field(OUT + n * 0x10000) for n in range(9)])
-    r = (_lib.Field * 9)(*[_field(RHS + n * 0x10000) for n in range(9)])
+    o = E.table(_field(OUT + n * 0x10000) for n in range(9))
+    r = E.table(_field(RHS + n * 0x10000) for n in range(9))
     assert [_call(o, r, _field(LO), _field(DI), _field(UP), nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
     c_order = lambda p: _field(p, strides=(7 * 5 * 8, 5 * 8, 8))  # noqa: E731
     L, T, IT = _lib.LINE_PATH_LANES, _lib.LINE_PATH_TILES, _lib.LINE_PATH_ITEMS
@@ -300,16 +272,13 @@ def test_launches_are_one_per_eight_pairs_and_the_path_follows_the_strides():
         assert _call(_field(OUT), c_order(RHS), _field(LO), _field(DI), _field(UP), axis=axis)[4] == IT
         assert _call(_field(OUT), _field(RHS), _field(LO), c_order(DI), _field(UP), axis=axis)[4] == IT
     # 1-d coefficients keep the path of the fields; a line of one point has no run to tile
-    assert _call(_field(OUT), _field(RHS), _line(LO, 4, 0), _line(DI, 4, 0), _line(UP, 4, 0), axis=0)[4] == T
-    assert _call(_field(OUT), _field(RHS), _line(LO, 5, 1), _line(DI, 5, 1), _line(UP, 5, 1), axis=1)[4] == L
+    assert _call(_field(OUT), _field(RHS), E.line(LO, 4, 0), E.line(DI, 4, 0), E.line(UP, 4, 0), axis=0)[4] == T
+    assert _call(_field(OUT), _field(RHS), E.line(LO, 5, 1), E.line(DI, 5, 1), E.line(UP, 5, 1), axis=1)[4] == L
     assert _call(*_good(), extent=(1, 5, 5), axis=0)[4] == IT
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*line_solve\S*kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"line_solve\S*kernel")
     # 2 dtypes x the register budgets for 1, 4 and 8 entries x (lanes, items, tiles)
     assert len(kernels) == 18 and len({name for name, *_ in kernels}) == 18, kernels
     for name, scratch, waves, lds in kernels:
@@ -318,18 +287,8 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def _args(**over):
-    args = dict(out=_host_field(), rhs=_host_field(), lower=_host_field(), diag=_host_field(), upper=_host_field())
+    args = dict(out=E.host_field(HOST), rhs=E.host_field(HOST), lower=E.host_field(HOST), diag=E.host_field(HOST), upper=E.host_field(HOST))
     args.update(over)
     return args.pop("out"), args.pop("rhs"), args
 
@@ -343,7 +302,7 @@ def _args(**over):
     (dict(origin=(0, 0, 5)), ValueError, "leave no domain"),
     (dict(axis="X"), ValueError, "axis must be one of"),
     (dict(axis=0), ValueError, "axis must be one of"),
-    (dict(periodic=True, upper=_host_field((2,)), origin=(6, 0, 0)), ValueError, "at least 3 points"),
+    (dict(periodic=True, upper=E.host_field((2,)), origin=(6, 0, 0)), ValueError, "at least 3 points"),
     (dict(periodic=True), TypeError, "device fields"),  # all checks passed: refused for being host memory
     (dict(), TypeError, "device fields"),
 ])
@@ -364,7 +323,7 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(ValueError, match="at least one"):
         S([], [], **rest)
     with pytest.raises(ValueError, match="2 out field.s. and 1 rhs field.s. were passed"):
-        S([out, _host_field()], [rhs], **rest)
+        S([out, E.host_field(HOST)], [rhs], **rest)
     with pytest.raises(TypeError, match="host"):
         S(torch.zeros(8, 9, 5, dtype=torch.float64), rhs, **rest)  # as_device_array's own refusal
     with pytest.raises(TypeError):
@@ -372,34 +331,34 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         S(out, rhs, lower=np.zeros(8), diag=rest["diag"], upper=rest["upper"])
     with pytest.raises(ValueError, match="takes IJK fields"):
-        S(_host_field((8, 9)), rhs, **rest)
+        S(E.host_field((8, 9)), rhs, **rest)
     with pytest.raises(ValueError, match="diag must be an IJK field or a 1-d array along I"):
-        S(out, rhs, lower=rest["lower"], diag=_host_field((8, 9)), upper=rest["upper"])
+        S(out, rhs, lower=rest["lower"], diag=E.host_field((8, 9)), upper=rest["upper"])
     # one dtype for everything, float32 or float64
     with pytest.raises(TypeError, match="share a dtype"):
-        S(out, _host_field(dtype="float32"), **rest)
+        S(out, E.host_field(HOST, dtype="float32"), **rest)
     with pytest.raises(TypeError, match="share a dtype"):
-        S(out, rhs, lower=rest["lower"], diag=rest["diag"], upper=_host_field((8,), "float32"))
-    ints = {k: _host_field(v.shape, "int64") for k, v in rest.items()}
+        S(out, rhs, lower=rest["lower"], diag=rest["diag"], upper=E.host_field((8,), "float32"))
+    ints = {k: E.host_field(v.shape, "int64") for k, v in rest.items()}
     with pytest.raises(TypeError, match="float32 or float64 fields"):
-        S(_host_field(dtype="int64"), _host_field(dtype="int64"), **ints)
+        S(E.host_field(HOST, dtype="int64"), E.host_field(HOST, dtype="int64"), **ints)
     # coefficient shapes: a 1-d array holds exactly n items along the line axis; IJK arrays agree along it
-    rest = dict(rest, upper=_host_field((8,)))
+    rest = dict(rest, upper=E.host_field((8,)))
     with pytest.raises(TypeError, match="device fields"):
         S(out, rhs, **rest)
     with pytest.raises(ValueError, match="upper has 8 items, a line of 9 points along J needs 9"):
         S(out, rhs, axis="J", **rest)
     with pytest.raises(ValueError, match="upper has 8 items, a line of 10 points along I needs 10"):
-        S(_host_field((10, 9, 5)), _host_field((10, 9, 5)), lower=_host_field((10, 9, 5)), diag=_host_field((10, 9, 5)), upper=rest["upper"], halo=1)
+        S(E.host_field((10, 9, 5)), E.host_field((10, 9, 5)), lower=E.host_field((10, 9, 5)), diag=E.host_field((10, 9, 5)), upper=rest["upper"], halo=1)
     with pytest.raises(ValueError, match="share their length along I: 8 and 10 differ"):
-        S(out, _host_field((10, 9, 5)), **rest)
+        S(out, E.host_field((10, 9, 5)), **rest)
     with pytest.raises(TypeError, match="device fields"):  # along J and K the smaller array sets the domain
-        S(out, _host_field((8, 11, 6)), **rest)
+        S(out, E.host_field((8, 11, 6)), **rest)
     # overlaps come from the library: a field as its own coefficient; in place is fine up to the device check
     with pytest.raises(TypeError, match="out 0 and diag overlap in memory"):
         S(out, rhs, lower=rest["lower"], diag=out, upper=rest["upper"])
     with pytest.raises(TypeError, match="out 0 and rhs 1 overlap in memory"):
-        S([out, _host_field()], [rhs, out], **rest)
+        S([out, E.host_field(HOST)], [rhs, out], **rest)
     with pytest.raises(TypeError, match="device fields"):
         S(out, out, **rest)
 
@@ -407,17 +366,12 @@ def test_python_refusals_about_the_fields_themselves():
 def test_a_frozen_solve_knows_its_box_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a LineSolve whose device check
     is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    outs, rhss = [_host_field((10, 9, 5), "float32") for _ in range(9)], [_host_field((12, 9, 5), "float32") for _ in range(9)]
-    a, b, c = _host_field((10, 9, 5), "float32"), _host_field((9,), "float32"), _host_field((9,), "float32")
+    E.on_device(monkeypatch)
+    outs, rhss = [E.host_field((10, 9, 5), "float32") for _ in range(9)], [E.host_field((12, 9, 5), "float32") for _ in range(9)]
+    a, b, c = E.host_field((10, 9, 5), "float32"), E.host_field((9,), "float32"), E.host_field((9,), "float32")
     ls = linesolve.LineSolve(outs, rhss, lower=a, diag=b, upper=c, axis="J", periodic=True, halo=1)
     assert (ls.n, ls.lines, ls.launches, ls.extent, ls.domain, ls.origin, ls.axis, ls.periodic, ls.path) == \
         (9, 50, 2, (10, 9, 5), (8, 7, 5), (1, 1, 0), "J", True, "lanes")
     assert ls.workspace.shape == (2 * 64 * 9,) and ls.workspace.dtype == np.float32  # cp and q: rows of 64 items for 50 lines
     del c
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        ls()
+    E.refuses_a_dead_array(ls)

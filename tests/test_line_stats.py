@@ -4,16 +4,17 @@ dry run and paths, ``Lines`` / ``merge_lines``, the Python refusals, and the ker
 
 import ctypes
 import math
-import pathlib
 import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import line_stats_ref as R
+from entry_checks import INV, OOB, UNS, int64s
 from gt4py_amd import _lib, diagnostics
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
+HOST = (8, 9, 3)  # the shape of a host field where a test states none
 G = _lib.LINE_STATS_SEGMENT
 U = 2.0 ** -53
 LENGTHS = [1, 2, 3, 4, 5, G - 1, G, G + 1, 2 * G + 3, 3 * G, 5 * G + 1]
@@ -100,26 +101,17 @@ def test_the_order_free_slots_equal_numpys(dtype):
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_header_and_constants_agree():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_line_stats\((.*?)\);", text, re.S).group(1)
-    assert [" ".join(p.split()) for p in decl.split(",")] == PARAMS
-    fn = _lib.load().gt4mi_line_stats
     FP, c_int, vp, i64 = ctypes.POINTER(_lib.Field), ctypes.c_int, ctypes.c_void_p, ctypes.c_int64
-    assert fn.restype is c_int
-    assert fn.argtypes == [FP, FP, c_int, ctypes.POINTER(i64), c_int, c_int, vp, i64, vp, c_int, vp, ctypes.POINTER(i64), ctypes.POINTER(c_int),
-                           ctypes.POINTER(c_int)]
-    assert "gt4mi_line_stats" in _lib.EXPORTED_SYMBOLS
+    E.check_binding("gt4mi_line_stats", PARAMS,
+                    argtypes=[FP, FP, c_int, ctypes.POINTER(i64), c_int, c_int, vp, i64, vp, c_int, vp, ctypes.POINTER(i64), ctypes.POINTER(c_int),
+                              ctypes.POINTER(c_int)],
+                    prefix="LINE_STATS", constants=("MEAN", "ROWS", "PATH_LANES", "PATH_TILES", "PATH_ITEMS"),
+                    phrases=("no reference counterpart", "function of n alone", "(A0 (+) A1) (+) (A2 (+) A3)", "new[i] = old[2i] (+) old[2i + 1]",
+                             "result[((entry * 9 + row) * nB + b) * nA + a]", "nfields * lines * S * 8 * 8", "2^30 (line, segment) pairs"))
+    text = (E.ROOT / "include" / "gt4py_amd.h").read_text()
     define = re.search(r"#ifndef GT4MI_LINE_STATS_SEGMENT\n#define GT4MI_LINE_STATS_SEGMENT (\d+)", text)
     assert define and int(define.group(1)) == G and G % 4 == 0
-    header = {name: int(re.search(rf"GT4MI_LINE_STATS_{name} = (\d+)", text).group(1)) for name in ("MEAN", "ROWS", "PATH_LANES", "PATH_TILES", "PATH_ITEMS")}
-    assert header == {"MEAN": _lib.LINE_STATS_MEAN, "ROWS": _lib.LINE_STATS_ROWS, "PATH_LANES": _lib.LINE_STATS_PATH_LANES,
-                      "PATH_TILES": _lib.LINE_STATS_PATH_TILES, "PATH_ITEMS": _lib.LINE_STATS_PATH_ITEMS}
     assert (_lib.LINE_STATS_MEAN, _lib.LINE_STATS_ROWS) == (8, 9) == (R.MEAN, R.ROWS) and diagnostics.LINE_ROWS[R.MEAN] == "mean"
-    comment = text[: text.index("int gt4mi_line_stats(")].rsplit("/* ----", 1)[1]
-    for needle in ("no reference counterpart", "function of n alone", "(A0 (+) A1) (+) (A2 (+) A3)", "new[i] = old[2i] (+) old[2i + 1]",
-                   "result[((entry * 9 + row) * nB + b) * nA + a]", "nfields * lines * S * 8 * 8", "2^30 (line, segment) pairs"):
-        assert needle in comment, needle
     # the library was built with the same G: G items are one segment, one more makes two
     for n, segments in ((G, 1), (G + 1, 2)):
         f = ctypes.byref(_lib.Field.make(0x10000, (n, 3, 2), (8, 8 * n, 24 * n), (0, 0, 0)))
@@ -132,21 +124,18 @@ WORK, RESULT = 0x900000, 0xA00000
 NEEDED = 1 * 8 * 1 * 64  # domain (4, 4, 2) along I: 8 lines of one segment
 
 
-def _field(ptr=FIELD[0], shape=FIELD[1], strides=FIELD[2], origin=FIELD[3]):
-    return _lib.Field.make(ptr, shape, strides, origin)
+def _field(ptr=FIELD[0], shape=FIELD[1], strides=FIELD[2], origin=FIELD[3]):  # (everything defaults to FIELD)
+    return E.field(ptr, shape, strides, origin)
 
 
 def _call(fields, others=None, nfields=1, domain=(4, 4, 2), axis=0, elem_size=8, workspace=WORK, workspace_bytes=1 << 20, result=RESULT,
           flags=_lib.STATS_DRY_RUN):
-    lib = _lib.load()
-    needed, launches, path = ctypes.c_int64(-5), ctypes.c_int(77), ctypes.c_int(55)
-    rc = lib.gt4mi_line_stats(fields, others, nfields, _lib.domain3(domain) if domain is not None else None, axis, elem_size, workspace,
-                              workspace_bytes, result, flags, None, ctypes.byref(needed), ctypes.byref(launches), ctypes.byref(path))
-    return rc, lib.gt4mi_last_error(), launches.value, needed.value, path.value
+    rc, msg, needed, launches, path = E.call("gt4mi_line_stats", fields, others, nfields, int64s(domain), axis, elem_size, workspace,
+                                             workspace_bytes, result, flags, None, outs=(ctypes.c_int64(-5), 77, 55))
+    return rc, msg, launches, needed, path
 
 
 def test_argument_errors_of_the_c_entry_without_a_gpu():
-    INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
     f = ctypes.byref(_field())
 
     def refused(status, needle, *args, **kwargs):
@@ -206,7 +195,7 @@ def test_argument_errors_of_the_c_entry_without_a_gpu():
 
 
 def test_dry_run_reports_workspace_and_launches():
-    many = (_lib.Field * 17)(*[_field(ptr=0x10000 * (n + 1)) for n in range(17)])
+    many = E.table(_field(ptr=0x10000 * (n + 1)) for n in range(17))
     for n, want in ((1, 1), (8, 1), (9, 2), (16, 2), (17, 3)):
         rc, msg, launches, needed, _ = _call(many, nfields=n, workspace=None, result=None)  # asking for the size
         assert rc == 0 and launches == want and needed == n * NEEDED, (n, msg)
@@ -214,8 +203,8 @@ def test_dry_run_reports_workspace_and_launches():
         big = ctypes.byref(_field(shape=domain, strides=(8, 8 * domain[0], 8 * domain[0] * domain[1]), origin=(0, 0, 0)))
         for axis in range(3):
             for nfields, passes in ((1, 1), (9, 2)):
-                fields = (_lib.Field * nfields)(*[_field(0x10000 + 0x1000000000 * n, domain, (8, 8 * domain[0], 8 * domain[0] * domain[1]), (0, 0, 0))
-                                                  for n in range(nfields)])
+                fields = E.table(_field(0x10000 + 0x1000000000 * n, domain, (8, 8 * domain[0], 8 * domain[0] * domain[1]), (0, 0, 0))
+                                 for n in range(nfields))
                 rc, msg, launches, needed, _ = _call(fields, nfields=nfields, domain=domain, axis=axis, workspace=None, result=None)
                 lines, segments = math.prod(domain) // domain[axis], R.segments(domain[axis], G)
                 assert rc == 0 and needed == nfields * lines * segments * 8 * 8 and launches == passes + (segments > 1), (domain, axis, msg)
@@ -237,7 +226,7 @@ def test_the_path_follows_the_strides():
                 rc, msg, _, _, path = _call(f, domain=domain, axis=axis, elem_size=size, workspace=None, result=None)
                 assert rc == 0 and path == want[name][axis] == R.expected_path([strides], [], domain, axis, size), (name, axis, msg, path)
         # mixed: an I-contiguous and a K-contiguous field share no unit-stride axis
-        mixed = (_lib.Field * 2)(_field(0x10000, shape, layouts["I-contiguous"], (0, 0, 0)), _field(0x4000000, shape, layouts["K-contiguous"], (0, 0, 0)))
+        mixed = E.table((_field(0x10000, shape, layouts["I-contiguous"], (0, 0, 0)), _field(0x4000000, shape, layouts["K-contiguous"], (0, 0, 0))))
         for axis in range(3):
             assert _call(mixed, nfields=2, domain=domain, axis=axis, elem_size=size, workspace=None, result=None)[::4] == (0, X)
         # an IJ weight (K stride 0) beside an I-contiguous field: along K it is broadcast along the line, lanes still run along I
@@ -249,7 +238,7 @@ def test_the_path_follows_the_strides():
             assert got[::4] == (0, path) and path == R.expected_path([layouts["I-contiguous"]], [weight], domain, axis, size), (axis, got)
         # nine entries are two launches: only the NINTH has a second field, and that alone breaks unit stride -- the rule looks at
         # every entry of the call, not at the eight of the first launch
-        nine = (_lib.Field * 9)(*[_field(0x10000 + 0x1000000 * n, shape, layouts["I-contiguous"], (0, 0, 0)) for n in range(9)])
+        nine = E.table(_field(0x10000 + 0x1000000 * n, shape, layouts["I-contiguous"], (0, 0, 0)) for n in range(9))
         others = (_lib.Field * 9)()  # (data == NULL: no second field)
         others[8] = _field(0x40000000, shape, layouts["every other item"], (0, 0, 0))
         for axis, alone in enumerate((T, L, L)):
@@ -266,11 +255,7 @@ def test_the_path_follows_the_strides():
 def test_the_kernels_are_in_the_resource_log_and_use_no_scratch():
     """As test_no_shipped_hot_kernel_spills reads the log: every line_stats kernel -- the march kernel and the tile kernels of both
     item types, the finish kernel -- has ScratchSize 0; only the tile kernels use LDS."""
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    found = re.findall(r"remark: Function Name: (\S*line_stats\S*kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)",
-                       log.read_text(), re.S)
-    kernels = {name: (int(scratch), int(lds)) for name, scratch, lds in found}
+    kernels = {name: (scratch, lds) for name, scratch, _, lds in E.kernel_resources(r"line_stats\S*kernel")}
     kinds = sorted(re.search(r"line_stats_(march|tile|finish)_kernel", name).group(1) for name in kernels)
     assert kinds == ["finish"] + ["march"] * 2 + ["tile"] * 4, sorted(kernels)
     assert all(scratch == 0 for scratch, _ in kernels.values()), kernels
@@ -338,44 +323,35 @@ def test_merge_lines_joins_line_by_line_in_the_order_given():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 3), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check; a call that passed them all is refused last."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def test_python_refusals_need_no_gpu():
     D = diagnostics
     with pytest.raises(TypeError, match="axis"):
-        D.line_stats(_host_field())  # axis has no default
+        D.line_stats(E.host_field(HOST))  # axis has no default
     for axis in ("L", 3, -1, None, True, 1.0):
         with pytest.raises(ValueError, match="axis must be 'I', 'J', 'K' or 0, 1, 2"):
-            D.line_stats(_host_field(), axis=axis)
+            D.line_stats(E.host_field(HOST), axis=axis)
     with pytest.raises(ValueError, match="at least one field"):
         D.line_stats(axis="I")
     with pytest.raises(TypeError, match="float32 or float64 fields, not int32"):
-        D.line_stats(_host_field(dtype="int32"), axis="I")
+        D.line_stats(E.host_field(HOST, dtype="int32"), axis="I")
     with pytest.raises(TypeError, match="share a dtype"):
-        D.line_stats(_host_field(), axis="J", other=_host_field(dtype="float32"))
+        D.line_stats(E.host_field(HOST), axis="J", other=E.host_field(HOST, dtype="float32"))
     with pytest.raises(ValueError, match="one entry .* per field: 1 for 2 fields"):
-        D.LineStats([_host_field(), _host_field()], axis=0, others=[_host_field()])
+        D.LineStats([E.host_field(HOST), E.host_field(HOST)], axis=0, others=[E.host_field(HOST)])
     with pytest.raises(ValueError, match="IJ or IJK fields"):
-        D.line_stats(_host_field((8,)), axis="I")
+        D.line_stats(E.host_field((8,)), axis="I")
     with pytest.raises(ValueError, match="leave no domain"):
-        D.line_stats(_host_field(), axis="K", halo=4)
+        D.line_stats(E.host_field(HOST), axis="K", halo=4)
     with pytest.raises(ValueError, match="line_stats: field 0: origin 0 \\+ domain 4 along axis 2 is outside the array"):
-        D.line_stats(_host_field(), axis="I", origin=(0, 0, 0), domain=(8, 9, 4))
+        D.line_stats(E.host_field(HOST), axis="I", origin=(0, 0, 0), domain=(8, 9, 4))
     with pytest.raises(ValueError, match="line_stats: empty domain"):
-        D.line_stats(_host_field(), axis=2, domain=(3, 3, 0))
+        D.line_stats(E.host_field(HOST), axis=2, domain=(3, 3, 0))
     # all checks passed (an IJ weight against an IJK field, a sub-box, every spelling of the axis): refused for being host memory
-    for kwargs in (dict(axis="I"), dict(axis="j", halo=2), dict(axis="K", other=_host_field((8, 9))), dict(axis=np.int64(1), origin=(1, 1, 1), domain=(2, 2, 2))):
+    for kwargs in (dict(axis="I"), dict(axis="j", halo=2), dict(axis="K", other=E.host_field((8, 9))), dict(axis=np.int64(1), origin=(1, 1, 1), domain=(2, 2, 2))):
         with pytest.raises(TypeError, match="device fields"):
-            D.line_stats(_host_field(), **kwargs)
+            D.line_stats(E.host_field(HOST), **kwargs)
     with pytest.raises(TypeError, match="device fields"):
-        D.LineStats([_host_field((8, 9), "float32")], axis="I", halo=((1, 2), (0, 3)))  # Field[IJ]: nk = 1
+        D.LineStats([E.host_field((8, 9), "float32")], axis="I", halo=((1, 2), (0, 3)))  # Field[IJ]: nk = 1
 
 
 # ---- what consumes a section: a stencil with a two-dimensional field of each kind ------------------------------------------------

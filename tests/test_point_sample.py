@@ -4,20 +4,17 @@ readable box, NaN and infinite positions, the one rounding of the fill value), e
 (made-up addresses that are never dereferenced), the declaration, the kernels' resources and the Python interface's argument
 checks."""
 
-import ctypes
-import gc
 import math
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import point_sample_ref as S
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, sampling
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (10, 9, 5)  # the shape of a host field where a test states none
 REACHES = [(0, 0, 0, 0), (1, 1, 1, 1), (3, 1, 0, 2)]
 
 
@@ -144,39 +141,24 @@ def test_the_fill_value_is_rounded_once_to_the_item_type():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    decl = re.search(r"int gt4mi_point_sample\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* pos_i",
-                      "const gt4mi_field* pos_j", "const gt4mi_field* pos_k", "int64_t npoints", "const int64_t extent[3]",
-                      "const int64_t reach[4]", "int elem_size", "int pos_elem_size", "int method", "int flags", "double fill_value",
-                      "void* stream", "int* launches"]
-    fn = _lib.load().gt4mi_point_sample
-    fp, i64p, c_int = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, fp, fp, fp, ctypes.c_int64, i64p, i64p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_void_p,
-                           ctypes.POINTER(c_int)]
-    assert "gt4mi_point_sample" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_point_sample")
-    assert re.search(r"enum \{ GT4MI_SAMPLE_FILL = 2, GT4MI_SAMPLE_DRY_RUN = 256 \};", text)
+    E.check_binding("gt4mi_point_sample",
+                    ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* pos_i",
+                     "const gt4mi_field* pos_j", "const gt4mi_field* pos_k", "int64_t npoints", "const int64_t extent[3]",
+                     "const int64_t reach[4]", "int elem_size", "int pos_elem_size", "int method", "int flags", "double fill_value",
+                     "void* stream", "int* launches"],
+                    phrases=("no reference counterpart", "gt4mi_horizontal_interp in absolute mode", "gt4mi_departure_interp in absolute mode",
+                             "K has no ghost levels", "p < xmin, p > xmax or p != p", "rounded once", "LAUNCH time",
+                             "number or order of the points", "ceil(nfields / 8)"))
+    assert "enum { GT4MI_SAMPLE_FILL = 2, GT4MI_SAMPLE_DRY_RUN = 256 };" in (E.ROOT / "include" / "gt4py_amd.h").read_text()
     assert (_lib.SAMPLE_FILL, _lib.SAMPLE_DRY_RUN) == (2, 256)
-    comment = text[: text.index("int gt4mi_point_sample(")].rsplit("/* ----", 1)[1]
-    for phrase in ("no reference counterpart", "gt4mi_horizontal_interp in absolute mode", "gt4mi_departure_interp in absolute mode",
-                   "K has no ghost levels", "p < xmin, p > xmax or p != p", "rounded once", "LAUNCH time", "number or order of the points",
-                   "ceil(nfields / 8)"):
-        assert phrase in comment, phrase
 
 
 DST, SRC, PI, PJ, PK = 0x10_0000, 0x4000_0000, 0x8000_0000, 0xC000_0000, 0x1_0000_0000  # made-up device addresses, far apart
 NP, NK = 10, 3
 
 
-def _field(ptr, nk=NK, shape_ij=(8, 8), strides=None, origin=(2, 2, 0), itemsize=8):
-    ni, nj = shape_ij
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, (ni, nj, nk), strides, origin)
+def _field(ptr, nk=NK, shape_ij=(8, 8), strides=None, origin=(2, 2, 0), itemsize=8):  # (nk first; this file's plane and origin)
+    return E.field(ptr, (*shape_ij, nk), strides, origin, itemsize)
 
 
 def _result(ptr, npoints=NP, nk=NK, strides=None, itemsize=8, origin=(0, 0, 0)):
@@ -192,14 +174,8 @@ def _list(ptr, npoints=NP, itemsize=8, stride=None):
 
 def _call(dst, src, pi, pj, pk=None, nfields=1, npoints=NP, extent=(4, 4, NK), reach=(1, 1, 1, 1), size=8, pos_size=8, method=1, flags=0,
           fill_value=0.0):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_point_sample(as_arg(dst), as_arg(src), nfields, as_arg(pi), as_arg(pj), as_arg(pk), npoints,
-                                (ctypes.c_int64 * 3)(*extent) if extent is not None else None,
-                                (ctypes.c_int64 * 4)(*reach) if reach is not None else None, size, pos_size, method,
-                                flags | _lib.SAMPLE_DRY_RUN, fill_value, None, ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value
+    return E.call("gt4mi_point_sample", as_arg(dst), as_arg(src), nfields, as_arg(pi), as_arg(pj), as_arg(pk), npoints, int64s(extent),
+                  int64s(reach), size, pos_size, method, flags | _lib.SAMPLE_DRY_RUN, fill_value, None, outs=(77,))
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -317,7 +293,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == 0, msg
     rc, msg, _ = _call(d1, s, pi, pj, _list(DST + 8))
     assert rc == UNS and b"dst 0 and pos_k overlap in memory" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, _ = _call(two(d, _result(DST + 0x1000)), two(s, _field(DST + 64)), pi, pj, nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, _ = _call(two(d, _result(DST + last)), two(s, _field(SRC + 0x1000)), pi, pj, nfields=2)
@@ -335,18 +311,15 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
 
 
 def test_launches_are_one_per_eight_fields():
-    d = (_lib.Field * 9)(*[_result(DST + n * 8 * NP * NK) for n in range(9)])  # the blocks of a C-ordered (9, NP, NK) result
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x1000) for n in range(9)])
+    d = E.table(_result(DST + n * 8 * NP * NK) for n in range(9))  # the blocks of a C-ordered (9, NP, NK) result
+    s = E.table(_field(SRC + n * 0x1000) for n in range(9))
     pi, pj, pk = _list(PI), _list(PJ), _list(PK)
     assert [_call(d, s, pi, pj, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
     assert [_call(d, s, pi, pj, pk, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*point_sample_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"point_sample_kernel")
     # 2 field types x 2 position types x 4 methods x the instantiations for 1, 4 and 8 entries x 2 modes
     assert len(kernels) == 96 and len({name for name, *_ in kernels}) == 96, kernels
     for name, scratch, waves, lds in kernels:
@@ -354,20 +327,10 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host(shape=(10, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def _good(**over):
-    args = dict(pos_i=_host((7,)), pos_j=_host((7,)))
+    args = dict(pos_i=E.host_field((7,)), pos_j=E.host_field((7,)))
     args.update(over)
-    return _host(), args
+    return E.host_field(HOST), args
 
 
 @pytest.mark.parametrize("kwargs, error, match", [
@@ -379,11 +342,11 @@ def _good(**over):
     (dict(method="quintic"), ValueError, "method must be one of"),
     (dict(outside="wrap"), ValueError, "outside must be one of"),
     (dict(fill_value="zero"), TypeError, "fill_value must be a number"),
-    (dict(out=_host((1, 7, 4))), ValueError, r"out must have shape \(1, 7, 5\) and dtype float64"),
-    (dict(out=_host((1, 7, 5), "float32")), ValueError, "out must have shape"),
-    (dict(pos_k=_host((7,)), out=_host((1, 7, 5))), ValueError, r"out must have shape \(1, 7\)"),
+    (dict(out=E.host_field((1, 7, 4))), ValueError, r"out must have shape \(1, 7, 5\) and dtype float64"),
+    (dict(out=E.host_field((1, 7, 5), "float32")), ValueError, "out must have shape"),
+    (dict(pos_k=E.host_field((7,)), out=E.host_field((1, 7, 5))), ValueError, r"out must have shape \(1, 7\)"),
     (dict(halo=((1, 2), (0, 3)), method="cubic_monotone", outside="fill", fill_value=-1), TypeError, "sample works on device fields"),
-    (dict(pos_k=_host((7,)), out=_host((1, 7))), TypeError, "sample works on device fields"),
+    (dict(pos_k=E.host_field((7,)), out=E.host_field((1, 7))), TypeError, "sample works on device fields"),
     (dict(), TypeError, "sample works on device fields"),  # all checks passed: host arrays are refused last
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
@@ -413,51 +376,48 @@ def test_python_refusals_about_the_arrays_themselves(monkeypatch):
     with pytest.raises(TypeError):
         R(field, **dict(pos, pos_j=np.zeros(7)))
     with pytest.raises(ValueError, match="takes IJK fields"):
-        R(_host((10, 9)), **pos)
+        R(E.host_field((10, 9)), **pos)
     with pytest.raises(ValueError, match="pos_j must be a 1-d array of positions, not an array of 2"):
-        R(field, **dict(pos, pos_j=_host((7, 1))))
+        R(field, **dict(pos, pos_j=E.host_field((7, 1))))
     with pytest.raises(ValueError, match="pos_k must be a 1-d array of positions, not an array of 3"):
-        R(field, **dict(pos, pos_k=_host((10, 9, 5))))
+        R(field, **dict(pos, pos_k=E.host_field((10, 9, 5))))
     with pytest.raises(ValueError, match="pos_i and pos_j share a length: 7 and 8 differ"):
-        R(field, **dict(pos, pos_j=_host((8,))))
+        R(field, **dict(pos, pos_j=E.host_field((8,))))
     with pytest.raises(ValueError, match="pos_i and pos_k share a length: 7 and 6 differ"):
-        R(field, **dict(pos, pos_k=_host((6,))))
+        R(field, **dict(pos, pos_k=E.host_field((6,))))
     with pytest.raises(ValueError, match="at least one point"):
-        R(field, pos_i=_host((0,)), pos_j=_host((0,)))
+        R(field, pos_i=E.host_field((0,)), pos_j=E.host_field((0,)))
     with pytest.raises(TypeError, match="the fields of one call share a dtype"):
-        R([field, _host(dtype="float32")], **pos)
+        R([field, E.host_field(HOST, dtype="float32")], **pos)
     with pytest.raises(TypeError, match="float32 or float64 fields"):
-        R(_host(dtype="int64"), **pos)
+        R(E.host_field(HOST, dtype="int64"), **pos)
     with pytest.raises(TypeError, match="pos_i and pos_j share a dtype: float64 and float32 differ"):
-        R(field, **dict(pos, pos_j=_host((7,), "float32")))
+        R(field, **dict(pos, pos_j=E.host_field((7,), "float32")))
     with pytest.raises(TypeError, match="pos_i and pos_k share a dtype"):
-        R(field, **dict(pos, pos_k=_host((7,), "float32")))
+        R(field, **dict(pos, pos_k=E.host_field((7,), "float32")))
     with pytest.raises(TypeError, match="position arrays are float32 or float64"):
-        R(field, pos_i=_host((7,), "int32"), pos_j=_host((7,), "int32"))
+        R(field, pos_i=E.host_field((7,), "int32"), pos_j=E.host_field((7,), "int32"))
     assert not calls
     with pytest.raises(TypeError, match="device fields"):  # float32 fields against float64 positions is a combination of its own
-        R(_host(dtype="float32"), **pos)
+        R(E.host_field(HOST, dtype="float32"), **pos)
     assert len(calls) == 1  # (the dry run)
     # the caller's result on top of a field, of a position array
-    flat = _host((7 * 5 + 7,))
+    flat = E.host_field((7 * 5 + 7,))
     with pytest.raises(TypeError, match="dst 0 and pos_i overlap in memory"):
         R(field, pos_i=flat[:7], pos_j=pos["pos_j"], out=DeviceArray(flat.tensor[6:41].view(1, 7, 5)))
-    big = _host((10, 9, 5))
+    big = E.host_field((10, 9, 5))
     with pytest.raises(TypeError, match="dst 0 and src 0 overlap in memory"):
         R(big, **pos, out=DeviceArray(big.tensor.view(-1)[:35].view(1, 7, 5)))
     with pytest.raises(TypeError, match="dst 0 and dst 1 overlap in memory"):
-        R([field, _host()], **pos, out=DeviceArray(flat.tensor[:35].view(1, 7, 5).expand(2, 7, 5)))
+        R([field, E.host_field(HOST)], **pos, out=DeviceArray(flat.tensor[:35].view(1, 7, 5).expand(2, 7, 5)))
 
 
 def test_a_frozen_call_knows_its_shapes_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a Sample whose device check is made
     to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    fields = [_host((12, 9, 5), "float32") for _ in range(9)]
-    pi, pj, pk = (_host((11,), "float64") for _ in range(3))
+    E.on_device(monkeypatch)
+    fields = [E.host_field((12, 9, 5), "float32") for _ in range(9)]
+    pi, pj, pk = (E.host_field((11,), "float64") for _ in range(3))
     column = sampling.Sample(fields, pos_i=pi, pos_j=pj, method="cubic", halo=((2, 1), (1, 3)))
     assert (column.launches, column.domain, column.origin, column.npoints, column.method, column.outside) == (2, (9, 5, 5), (2, 1, 0), 11, "cubic", "clamp")
     assert column.result.shape == (9, 11, 5) and column.result.dtype == np.float32 and column.result.tensor.is_contiguous()
@@ -466,11 +426,9 @@ def test_a_frozen_call_knows_its_shapes_and_refuses_to_run_after_an_array_died(m
         column.column(9)
     with pytest.raises(RuntimeError, match="has not been called yet"):
         column.get()
-    out = _host((9, 11), "float32")
+    out = E.host_field((9, 11), "float32")
     point = sampling.Sample(fields, pos_i=pi, pos_j=pj, pos_k=pk, outside="fill", fill_value=-1, out=out)
     assert point.result.ptr == out.ptr and point.result.shape == (9, 11) and point.column(2).shape == (11,)
     assert (point.launches, point.domain, point.fill_value, point.outside) == (2, (12, 9, 5), -1.0, "fill")
     del pk
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        point()
+    E.refuses_a_dead_array(point)

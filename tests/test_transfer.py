@@ -3,62 +3,39 @@ that are never dereferenced), the path and the launch count the library reports,
 argument checks, and numpy's own two conversions on the edge values the GPU test plants."""
 
 import ctypes
-import gc
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
 import device_layouts as L
+import entry_checks as E
 import transfer_ref as R
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, transfer
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 3)  # the shape of a host field where a test states none
 DST, SRC = 0x10_0000, 0x4000_0000  # made-up device addresses, far apart
 
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_field_copy\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const int64_t extent[3]", "int dst_elem_size",
-                      "int src_elem_size", "int flags", "void* stream", "int* paths", "int* launches"]
-    fn = _lib.load().gt4mi_field_copy
-    fp, i64p, c_int, ip = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_int)
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, i64p, c_int, c_int, c_int, ctypes.c_void_p, ip, ip]
-    assert "gt4mi_field_copy" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_field_copy")
     # the header says what the entry replaces, and the enums of header and binding agree
-    comment = text[: text.index("int gt4mi_field_copy(")].rsplit("/* ----", 1)[1]
-    assert "slicing" in comment and "cp.asarray" in comment
-    for name in ("PATH_ROWS", "PATH_TILES", "PATH_ITEMS", "CONVERT", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_COPY_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"COPY_{name}") == value, name
+    E.check_binding("gt4mi_field_copy",
+                    ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const int64_t extent[3]", "int dst_elem_size",
+                     "int src_elem_size", "int flags", "void* stream", "int* paths", "int* launches"],
+                    prefix="COPY", constants=("PATH_ROWS", "PATH_TILES", "PATH_ITEMS", "CONVERT", "DRY_RUN"), phrases=("slicing", "cp.asarray"))
     assert (transfer.PATH_ROWS, transfer.PATH_TILES, transfer.PATH_ITEMS) == (R.ROWS, R.TILES, R.ITEMS) == (0, 1, 2)
 
 
-def _field(ptr, shape=(6, 6, 2), strides=None, origin=(1, 1, 0), itemsize=8, layout="ifirst"):
-    if strides is None:
-        ni, nj, nk = shape
-        strides = {"ifirst": (1, ni, ni * nj), "kfirst": (nj * nk, nk, 1), "jfirst": (nj, 1, ni * nj)}[layout]
-        strides = tuple(s * itemsize for s in strides)
-    return _lib.Field.make(ptr, shape, strides, origin)
+def _field(ptr, shape=(6, 6, 2), *rest, **kwargs):  # (this file's shape)
+    return E.field(ptr, shape, *rest, **kwargs)
 
 
 def _call(dst, src, nfields=1, extent=(4, 4, 2), dsize=8, ssize=8, flags=0, want_paths=True):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
     paths = (ctypes.c_int * max(nfields, 1))(*([-1] * max(nfields, 1)))
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_field_copy(as_arg(dst), as_arg(src), nfields, _lib.domain3(extent) if extent is not None else None, dsize, ssize,
-                              flags | _lib.COPY_DRY_RUN, None, paths if want_paths else None, ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value, list(paths)
+    rc, msg, launches = E.call("gt4mi_field_copy", as_arg(dst), as_arg(src), nfields, int64s(extent), dsize, ssize, flags | _lib.COPY_DRY_RUN, None,
+                               paths if want_paths else None, outs=(77,))
+    return rc, msg, launches, list(paths)
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -130,7 +107,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == UNS and b"overlap in memory" in msg
     rc, msg, _, _ = _call(d, _field(DST + last - first + 8))  # the byte ranges of the BOXES (not of the arrays) do not meet
     assert rc == 0, msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, _, _ = _call(two(d, _field(DST + 0x1000)), two(s, _field(DST + 64)), nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, _, _ = _call(two(d, _field(DST + 128)), two(s, _field(SRC + 0x1000)), nfields=2)
@@ -191,23 +168,20 @@ def test_a_mixed_call_reports_one_path_per_pair_and_conversion_keeps_them():
     shape, extent = (40, 36, 9), (38, 34, 9)
     layouts = [("ifirst", "kfirst"), ("kfirst", "kfirst"), ("jfirst", "ifirst")]
     for dsize, ssize, flags in ((8, 8, 0), (4, 8, _lib.COPY_CONVERT), (8, 4, _lib.COPY_CONVERT)):
-        d = (_lib.Field * 3)(*[_field(DST + n * 0x10_0000, shape, itemsize=dsize, layout=dl) for n, (dl, _) in enumerate(layouts)])
-        s = (_lib.Field * 3)(*[_field(SRC + n * 0x10_0000, shape, itemsize=ssize, layout=sl) for n, (_, sl) in enumerate(layouts)])
+        d = E.table(_field(DST + n * 0x10_0000, shape, itemsize=dsize, layout=dl) for n, (dl, _) in enumerate(layouts))
+        s = E.table(_field(SRC + n * 0x10_0000, shape, itemsize=ssize, layout=sl) for n, (_, sl) in enumerate(layouts))
         rc, msg, launches, paths = _call(d, s, nfields=3, extent=extent, dsize=dsize, ssize=ssize, flags=flags)
         assert rc == 0 and launches == 1 and paths == [R.TILES, R.ROWS, R.TILES], msg
 
 
 def test_launches_are_one_per_eight_pairs():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x1000) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x1000) for n in range(9)])
+    d = E.table(_field(DST + n * 0x1000) for n in range(9))
+    s = E.table(_field(SRC + n * 0x1000) for n in range(9))
     assert [_call(d, s, nfields=n)[2] for n in (1, 8, 9)] == [1, 1, 2]
 
 
 def test_the_kernels_are_in_the_resource_log():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*field_copy_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"field_copy_kernel")
     assert len(kernels) == 6, kernels  # item sizes 1, 2, 4, 8 and the two conversions
     for name, scratch, waves, lds in kernels:
         # every instantiation holds the tile path: no scratch, at least 4 waves per SIMD, a tile of at most 32 KiB
@@ -215,16 +189,6 @@ def test_the_kernels_are_in_the_resource_log():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 3), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 @pytest.mark.parametrize("kwargs, error, match", [
     (dict(halo=2.0), ValueError, "halo must be"),
     (dict(halo=(1, 2, 3)), ValueError, "halo must be"),
@@ -240,13 +204,13 @@ def _host_field(shape=(8, 9, 3), dtype="float64"):
 ])
 def test_python_refusals_need_no_gpu(kwargs, error, match):
     with pytest.raises(error, match=match):
-        transfer.copy_fields(_host_field(), _host_field(), **kwargs)
+        transfer.copy_fields(E.host_field(HOST), E.host_field(HOST), **kwargs)
     with pytest.raises(error, match=match):
-        transfer.FieldCopy([_host_field()], [_host_field()], **kwargs)
+        transfer.FieldCopy([E.host_field(HOST)], [E.host_field(HOST)], **kwargs)
     with pytest.raises(error, match=match):
-        transfer.Download([_host_field()], **kwargs)
+        transfer.Download([E.host_field(HOST)], **kwargs)
     with pytest.raises(error, match=match):
-        transfer.Upload(_host_field(), **kwargs)
+        transfer.Upload(E.host_field(HOST), **kwargs)
 
 
 def test_python_refusals_about_the_fields_themselves():
@@ -258,37 +222,37 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(ValueError, match="at least one"):
         T.Download([])
     with pytest.raises(ValueError, match="2 destination.s. and 1 source"):
-        T.copy_fields([_host_field(), _host_field()], [_host_field()])
+        T.copy_fields([E.host_field(HOST), E.host_field(HOST)], [E.host_field(HOST)])
     with pytest.raises(TypeError, match="host"):
-        T.copy_fields(torch.zeros(4, 4, 2), _host_field())  # as_device_array's own refusal
+        T.copy_fields(torch.zeros(4, 4, 2), E.host_field(HOST))  # as_device_array's own refusal
     with pytest.raises(TypeError):
-        T.copy_fields(_host_field(), np.zeros((4, 4, 2)))
+        T.copy_fields(E.host_field(HOST), np.zeros((4, 4, 2)))
     with pytest.raises(ValueError, match="IJ or IJK"):
-        T.copy_fields(_host_field((8,)), _host_field((8,)))
+        T.copy_fields(E.host_field((8,)), E.host_field((8,)))
     # dtypes: the sides of a call share one each; different ones need convert, and convert is float32 <-> float64 only
     with pytest.raises(TypeError, match="share a dtype"):
-        T.copy_fields([_host_field(), _host_field(dtype="float32")], [_host_field(), _host_field()])
+        T.copy_fields([E.host_field(HOST), E.host_field(HOST, dtype="float32")], [E.host_field(HOST), E.host_field(HOST)])
     with pytest.raises(TypeError, match="pass convert=True"):
-        T.copy_fields(_host_field(dtype="float32"), _host_field())
+        T.copy_fields(E.host_field(HOST, dtype="float32"), E.host_field(HOST))
     with pytest.raises(TypeError, match="pass convert=True"):
-        T.copy_fields(_host_field(dtype="int32"), _host_field(dtype="float32"))  # the same item size is not the same dtype
+        T.copy_fields(E.host_field(HOST, dtype="int32"), E.host_field(HOST, dtype="float32"))  # the same item size is not the same dtype
     with pytest.raises(TypeError, match="only float32 <-> float64"):
-        T.copy_fields(_host_field(dtype="int32"), _host_field(), convert=True)
+        T.copy_fields(E.host_field(HOST, dtype="int32"), E.host_field(HOST), convert=True)
     with pytest.raises(TypeError, match="device fields"):
-        T.copy_fields(_host_field(dtype="float32"), _host_field(), convert=True)
+        T.copy_fields(E.host_field(HOST, dtype="float32"), E.host_field(HOST), convert=True)
     with pytest.raises(TypeError, match="only float32 <-> float64"):
-        T.Download([_host_field(dtype="int32")], dtype=np.float32)
+        T.Download([E.host_field(HOST, dtype="int32")], dtype=np.float32)
     with pytest.raises(TypeError, match="only float32 <-> float64"):
-        T.Upload([_host_field()], dtype=np.int64)
+        T.Upload([E.host_field(HOST)], dtype=np.int64)
     with pytest.raises(ValueError, match="slots"):
-        T.Download([_host_field()], slots=0)
+        T.Download([E.host_field(HOST)], slots=0)
     # the common domain is what fits EVERY field; a stated one that does not fit is the library's refusal
     with pytest.raises(ValueError, match="src 0: origin 0 . extent 8 along axis 0 is outside the array .shape 7."):
-        T.copy_fields(_host_field(), _host_field((7, 9, 3)), domain=(8, 9, 3))
+        T.copy_fields(E.host_field(HOST), E.host_field((7, 9, 3)), domain=(8, 9, 3))
     with pytest.raises(TypeError, match="device fields"):
-        T.copy_fields(_host_field(), _host_field((7, 9, 3)))
+        T.copy_fields(E.host_field(HOST), E.host_field((7, 9, 3)))
     # a field onto itself
-    x = _host_field()
+    x = E.host_field(HOST)
     with pytest.raises(TypeError, match="overlap in memory"):
         T.copy_fields(x, x)
 
@@ -296,17 +260,12 @@ def test_python_refusals_about_the_fields_themselves():
 def test_a_frozen_copy_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a FieldCopy whose device check
     is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    a, b = _host_field(), _host_field()
+    E.on_device(monkeypatch)
+    a, b = E.host_field(HOST), E.host_field(HOST)
     cp = transfer.FieldCopy([a], [b], halo=1)
     assert cp.launches == 1 and cp.paths == [transfer.PATH_ROWS] and cp.extent == (8, 9, 3) and cp.domain == (6, 7, 3)
     del b
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        cp()
+    E.refuses_a_dead_array(cp)
 
 
 # ---- the layouts every GPU test of a utility entry puts its buffers in -------------------------------------------------------------

@@ -3,20 +3,17 @@
 through the dry run (made-up addresses that are never dereferenced), the declaration, the kernels' resources and the Python
 interface's argument checks."""
 
-import ctypes
-import gc
 import math
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import vertical_interp_ref as V
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, vertical
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 EPS = float(np.finfo(np.float64).eps)
 LEVELS = [2, 3, 4, 5, 6, 17]
 KINDS = ["inside", "reversed", "shuffled", "on_levels", "outside_both_ends", "nan"]
@@ -250,30 +247,16 @@ def test_outside_values():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_vertical_interp\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* src_coord",
-                      "const gt4mi_field* dst_coord", "const int64_t extent_ij[2]", "int64_t ns", "int64_t nd", "int elem_size",
-                      "int coord_elem_size", "int method", "int outside", "double fill_value", "int flags", "void* stream", "int* launches"]
-    fn = _lib.load().gt4mi_vertical_interp
-    fp, i64p, c_int, i64 = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, fp, fp, i64p, i64, i64, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.c_void_p,
-                           ctypes.POINTER(c_int)]
-    assert "gt4mi_vertical_interp" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_vertical_interp")
     # the header states the contract and that the reference has no counterpart; the enums of header and binding agree
-    comment = text[: text.index("int gt4mi_vertical_interp(")].rsplit("/* ----", 1)[1]
-    for phrase in ("no reference counterpart", "user stencils", "while k < ns-2 and z[k+1] <= x", "while k > 0 and z[k] > x",
-                   "(1.0 - t) * q[k] + t * q[k+1]", "((w0*q0 + w1*q1) + w2*q2) + w3*q3", "k < 1 or k > ns-3", "canonical quiet NaN",
-                   "Path independence", "no address depends on the data"):
-        assert phrase in comment, phrase
-    for name in ("NEAREST", "LINEAR", "CUBIC", "CUBIC_MONOTONE", "OUTSIDE_CLAMP", "OUTSIDE_LINEAR", "OUTSIDE_FILL", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_VINTERP_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"VINTERP_{name}") == value, name
+    E.check_binding("gt4mi_vertical_interp",
+                    ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* src_coord",
+                     "const gt4mi_field* dst_coord", "const int64_t extent_ij[2]", "int64_t ns", "int64_t nd", "int elem_size",
+                     "int coord_elem_size", "int method", "int outside", "double fill_value", "int flags", "void* stream", "int* launches"],
+                    prefix="VINTERP",
+                    constants=("NEAREST", "LINEAR", "CUBIC", "CUBIC_MONOTONE", "OUTSIDE_CLAMP", "OUTSIDE_LINEAR", "OUTSIDE_FILL", "DRY_RUN"),
+                    phrases=("no reference counterpart", "user stencils", "while k < ns-2 and z[k+1] <= x", "while k > 0 and z[k] > x",
+                             "(1.0 - t) * q[k] + t * q[k+1]", "((w0*q0 + w1*q1) + w2*q2) + w3*q3", "k < 1 or k > ns-3", "canonical quiet NaN",
+                             "Path independence", "no address depends on the data"))
     assert vertical.INTERP_METHODS == {"nearest": 0, "linear": 1, "cubic": 2, "cubic_monotone": 3}
     assert vertical.OUTSIDE == {"clamp": 0, "linear": 1, "fill": 2}
 
@@ -282,21 +265,13 @@ DST, SRC, ZS, ZD = 0x10_0000, 0x4000_0000, 0x8000_0000, 0xC000_0000  # made-up d
 NS, ND = 5, 3
 
 
-def _field(ptr, nk, shape_ij=(6, 6), strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj = shape_ij
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, (ni, nj, nk), strides, origin)
+def _field(ptr, nk, shape_ij=(6, 6), strides=None, origin=(1, 1, 0), itemsize=8):  # (nk first; this file's plane)
+    return E.field(ptr, (*shape_ij, nk), strides, origin, itemsize)
 
 
 def _call(dst, src, zs, zd, nfields=1, extent=(4, 4), ns=NS, nd=ND, size=8, coord_size=8, method=1, outside=0, fill=math.nan, flags=0):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_vertical_interp(as_arg(dst), as_arg(src), nfields, as_arg(zs), as_arg(zd),
-                                   (ctypes.c_int64 * 2)(*extent) if extent is not None else None, ns, nd, size, coord_size, method, outside,
-                                   fill, flags | _lib.VINTERP_DRY_RUN, None, ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value
+    return E.call("gt4mi_vertical_interp", as_arg(dst), as_arg(src), nfields, as_arg(zs), as_arg(zd), int64s(extent), ns, nd, size, coord_size,
+                  method, outside, fill, flags | _lib.VINTERP_DRY_RUN, None, outs=(77,))
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -382,7 +357,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == 0, msg
     refused(UNS, b"vertical_interp: dst 0 and src_coord overlap in memory", d, s, _field(DST + 64, NS), zd)
     refused(UNS, b"vertical_interp: dst 0 and dst_coord overlap in memory", d, s, zs, column(DST + 8 * 40, ND))
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     refused(UNS, b"vertical_interp: dst 0 and src 1 overlap in memory", two(d, _field(DST + 0x1000, ND)), two(s, _field(DST + 64, NS)), zs, zd,
             nfields=2)
     refused(UNS, b"vertical_interp: dst 0 and dst 1 overlap in memory", two(d, _field(DST + 128, ND)), two(s, _field(SRC + 0x1000, NS)), zs, zd,
@@ -398,17 +373,14 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
 
 
 def test_launches_are_one_per_eight_pairs():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x1000, ND) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x1000, NS) for n in range(9)])
+    d = E.table(_field(DST + n * 0x1000, ND) for n in range(9))
+    s = E.table(_field(SRC + n * 0x1000, NS) for n in range(9))
     zs, zd = _field(ZS, NS), _field(ZD, ND)
     assert [_call(d, s, zs, zd, nfields=n)[::2] for n in (1, 8, 9)] == [(0, 1), (0, 1), (0, 2)]
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*vertical_interp_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"vertical_interp_kernel")
     # 2 field types x 2 coordinate types x 4 methods x the register budgets for 1, 4 and 8 entries
     assert len(kernels) == 48 and len({name for name, *_ in kernels}) == 48, kernels
     for name, scratch, waves, lds in kernels:
@@ -416,18 +388,8 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def _good(**over):
-    args = dict(dst=_host_field((8, 9, 3)), src=_host_field(), src_coord=_host_field((8, 9, 5)), dst_coord=_host_field((3,)))
+    args = dict(dst=E.host_field((8, 9, 3)), src=E.host_field(HOST), src_coord=E.host_field((8, 9, 5)), dst_coord=E.host_field((3,)))
     args.update(over)
     return args.pop("dst"), args.pop("src"), args
 
@@ -450,8 +412,8 @@ def _good(**over):
 def test_python_refusals_need_no_gpu(kwargs, error, match):
     dst, src, coords = _good()
     if kwargs.get("origin") == (0, 0, 4):
-        coords["dst_coord"] = _host_field((7,))  # (origin 4 leaves 3 of them)
-        dst = _host_field((8, 9, 7))
+        coords["dst_coord"] = E.host_field((7,))  # (origin 4 leaves 3 of them)
+        dst = E.host_field((8, 9, 7))
     with pytest.raises(error, match=match):
         vertical.interpolate_levels(dst, src, **coords, **kwargs)
     with pytest.raises(error, match=match):
@@ -466,7 +428,7 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(ValueError, match="at least one"):
         R([], [], **coords)
     with pytest.raises(ValueError, match="2 destination.s. and 1 source"):  # unequal list lengths
-        R([dst, _host_field((8, 9, 3))], [src], **coords)
+        R([dst, E.host_field((8, 9, 3))], [src], **coords)
     with pytest.raises(TypeError, match="host"):
         R(torch.zeros(8, 9, 3, dtype=torch.float64), src, **coords)  # as_device_array's own refusal of a host array
     with pytest.raises(TypeError):
@@ -474,51 +436,46 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         R(dst, src, src_coord=np.zeros((8, 9, 5)), dst_coord=coords["dst_coord"])
     with pytest.raises(ValueError, match="takes IJK fields"):
-        R(_host_field((8, 9)), src, **coords)
+        R(E.host_field((8, 9)), src, **coords)
     with pytest.raises(ValueError, match="dst_coord must be an IJK field or a Field.K."):
-        R(dst, src, src_coord=coords["src_coord"], dst_coord=_host_field((9, 3)))
+        R(dst, src, src_coord=coords["src_coord"], dst_coord=E.host_field((9, 3)))
     # dtypes: the fields share one, the coordinate fields share one (not necessarily the same), all float32 or float64
     with pytest.raises(TypeError, match="share a dtype"):
-        R(_host_field((8, 9, 3), "float32"), src, **coords)
+        R(E.host_field((8, 9, 3), "float32"), src, **coords)
     with pytest.raises(TypeError, match="interpolate_levels takes float32 or float64 fields"):
-        R(_host_field((8, 9, 3), "int64"), _host_field(dtype="int64"), **coords)
+        R(E.host_field((8, 9, 3), "int64"), E.host_field(HOST, dtype="int64"), **coords)
     with pytest.raises(TypeError, match="src_coord and dst_coord share a dtype"):
-        R(dst, src, src_coord=coords["src_coord"], dst_coord=_host_field((3,), "float32"))
+        R(dst, src, src_coord=coords["src_coord"], dst_coord=E.host_field((3,), "float32"))
     with pytest.raises(TypeError, match="coordinate fields are float32 or float64"):
-        R(dst, src, src_coord=_host_field((8, 9, 5), "int32"), dst_coord=_host_field((3,), "int32"))
+        R(dst, src, src_coord=E.host_field((8, 9, 5), "int32"), dst_coord=E.host_field((3,), "int32"))
     with pytest.raises(TypeError, match="device fields"):  # float32 fields against float64 coordinates is a combination of its own
-        R(_host_field((8, 9, 3), "float32"), _host_field(dtype="float32"), **coords)
+        R(E.host_field((8, 9, 3), "float32"), E.host_field(HOST, dtype="float32"), **coords)
     # levels: the sources share theirs, a coordinate field has exactly as many
     with pytest.raises(ValueError, match="sources of one call share their number of levels: 5 and 4"):
-        R([dst, _host_field((8, 9, 3))], [src, _host_field((8, 9, 4))], **coords)
+        R([dst, E.host_field((8, 9, 3))], [src, E.host_field((8, 9, 4))], **coords)
     with pytest.raises(ValueError, match="src_coord has 6 levels along K, the sources have 5"):
-        R(dst, src, src_coord=_host_field((8, 9, 6)), dst_coord=coords["dst_coord"])
+        R(dst, src, src_coord=E.host_field((8, 9, 6)), dst_coord=coords["dst_coord"])
     with pytest.raises(ValueError, match="dst_coord has 4 levels along K, the destinations have 3"):
-        R(dst, src, src_coord=coords["src_coord"], dst_coord=_host_field((4,)))
+        R(dst, src, src_coord=coords["src_coord"], dst_coord=E.host_field((4,)))
     with pytest.raises(ValueError, match="ns = 1 source"):
-        R(dst, _host_field((8, 9, 1)), src_coord=_host_field((1,)), dst_coord=coords["dst_coord"])
+        R(dst, E.host_field((8, 9, 1)), src_coord=E.host_field((1,)), dst_coord=coords["dst_coord"])
     # a field onto itself; a dst that is also the coordinate field
-    x = _host_field((8, 9, 5))
+    x = E.host_field((8, 9, 5))
     with pytest.raises(TypeError, match="dst 0 and src 0 overlap in memory"):
-        R(x, x, src_coord=coords["src_coord"], dst_coord=_host_field((5,)))
-    z = _host_field((8, 9, 5))
+        R(x, x, src_coord=coords["src_coord"], dst_coord=E.host_field((5,)))
+    z = E.host_field((8, 9, 5))
     with pytest.raises(TypeError, match="dst 0 and src_coord overlap in memory"):
-        R(z, _host_field((8, 9, 5)), src_coord=z, dst_coord=_host_field((5,)))
+        R(z, E.host_field((8, 9, 5)), src_coord=z, dst_coord=E.host_field((5,)))
 
 
 def test_a_frozen_interpolation_knows_its_box_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a VerticalInterp whose device
     check is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    dsts, srcs = [_host_field((8, 9, 3)) for _ in range(9)], [_host_field((10, 9, 5)) for _ in range(9)]
-    zs, zd = _host_field((8, 9, 5), "float32"), _host_field((3,), "float32")
+    E.on_device(monkeypatch)
+    dsts, srcs = [E.host_field((8, 9, 3)) for _ in range(9)], [E.host_field((10, 9, 5)) for _ in range(9)]
+    zs, zd = E.host_field((8, 9, 5), "float32"), E.host_field((3,), "float32")
     vi = vertical.VerticalInterp(dsts, srcs, src_coord=zs, dst_coord=zd, method="cubic", outside="fill", fill_value=-1, halo=1)
     assert (vi.ns, vi.nd, vi.launches, vi.extent, vi.domain, vi.origin, vi.method, vi.outside) == (5, 3, 2, (8, 9), (6, 7), (1, 1, 0), "cubic", "fill")
     assert vertical.VerticalInterp(dsts[:8], srcs[:8], src_coord=zs, dst_coord=zd).launches == 1
     del zd
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        vi()
+    E.refuses_a_dead_array(vi)

@@ -3,20 +3,17 @@ they do not depend on the order of operations, so they pin the contract itself),
 (made-up addresses that are never dereferenced), the declaration, the kernels' resources and the Python interface's argument
 checks."""
 
-import ctypes
-import gc
 import math
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
+import entry_checks as E
 import vertical_remap_ref as V
+from entry_checks import INV, OOB, UNS, as_arg, int64s
 from gt4py_amd import _lib, vertical
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-INV, OOB, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_OUT_OF_BOUNDS, _lib.ERR_UNSUPPORTED
+HOST = (8, 9, 5)  # the shape of a host field where a test states none
 EPS = float(np.finfo(np.float64).eps)
 METHODS = [V.PCM, V.PLM]
 
@@ -147,27 +144,13 @@ def test_the_array_form_rounds_once_and_broadcasts_a_shared_column_of_edges():
 
 # ---- the C entry ---------------------------------------------------------------------------------------------------------------
 def test_binding_declares_the_header_signature_and_the_abi_is_still_8():
-    text = (ROOT / "include" / "gt4py_amd.h").read_text()
-    assert re.search(r"#define GT4MI_ABI_VERSION 8\b", text) and _lib.GT4MI_ABI_VERSION == 8
-    assert _lib.load().gt4mi_abi_version() == 8
-    decl = re.search(r"int gt4mi_vertical_remap\((.*?)\);", text, re.S).group(1)
-    params = [" ".join(p.split()) for p in decl.split(",")]
-    assert params == ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* src_edges",
-                      "const gt4mi_field* dst_edges", "const int64_t extent_ij[2]", "int64_t ns", "int64_t nd", "int elem_size",
-                      "int edge_elem_size", "int method", "int flags", "void* stream", "int* launches"]
-    fn = _lib.load().gt4mi_vertical_remap
-    fp, i64p, c_int, i64 = ctypes.POINTER(_lib.Field), ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64
-    assert fn.restype is c_int
-    assert fn.argtypes == [fp, fp, c_int, fp, fp, i64p, i64, i64, c_int, c_int, c_int, c_int, ctypes.c_void_p, ctypes.POINTER(c_int)]
-    assert "gt4mi_vertical_remap" in _lib.EXPORTED_SYMBOLS
-    assert hasattr(ctypes.CDLL(str(_lib.LIB_PATH)), "gt4mi_vertical_remap")
     # the header states the contract and that the reference has no counterpart; the enums of header and binding agree
-    comment = text[: text.index("int gt4mi_vertical_remap(")].rsplit("/* ----", 1)[1]
-    for phrase in ("no reference counterpart", "user stencils", "(r - l) / d", "zs[k+1] >= hi", "copysign", "ns + nd - 1"):
-        assert phrase in comment, phrase
-    for name in ("PCM", "PLM", "DRY_RUN"):
-        value = int(re.search(rf"GT4MI_REMAP_{name} = (\d+)", text).group(1))
-        assert getattr(_lib, f"REMAP_{name}") == value, name
+    E.check_binding("gt4mi_vertical_remap",
+                    ["const gt4mi_field* dst", "const gt4mi_field* src", "int nfields", "const gt4mi_field* src_edges",
+                     "const gt4mi_field* dst_edges", "const int64_t extent_ij[2]", "int64_t ns", "int64_t nd", "int elem_size",
+                     "int edge_elem_size", "int method", "int flags", "void* stream", "int* launches"],
+                    prefix="REMAP", constants=("PCM", "PLM", "DRY_RUN"),
+                    phrases=("no reference counterpart", "user stencils", "(r - l) / d", "zs[k+1] >= hi", "copysign", "ns + nd - 1"))
     assert vertical.METHODS == {"pcm": _lib.REMAP_PCM, "plm": _lib.REMAP_PLM}
 
 
@@ -175,21 +158,13 @@ DST, SRC, ZS, ZD = 0x10_0000, 0x4000_0000, 0x8000_0000, 0xC000_0000  # made-up d
 NS, ND = 5, 3
 
 
-def _field(ptr, nk, shape_ij=(6, 6), strides=None, origin=(1, 1, 0), itemsize=8):
-    ni, nj = shape_ij
-    if strides is None:
-        strides = (itemsize, ni * itemsize, ni * nj * itemsize)
-    return _lib.Field.make(ptr, (ni, nj, nk), strides, origin)
+def _field(ptr, nk, shape_ij=(6, 6), strides=None, origin=(1, 1, 0), itemsize=8):  # (nk first; this file's plane)
+    return E.field(ptr, (*shape_ij, nk), strides, origin, itemsize)
 
 
 def _call(dst, src, zs, zd, nfields=1, extent=(4, 4), ns=NS, nd=ND, size=8, edge_size=8, method=0, flags=0):
-    lib = _lib.load()
-    launches = ctypes.c_int(77)
-    as_arg = lambda f: ctypes.byref(f) if isinstance(f, _lib.Field) else f  # noqa: E731
-    rc = lib.gt4mi_vertical_remap(as_arg(dst), as_arg(src), nfields, as_arg(zs), as_arg(zd),
-                                  (ctypes.c_int64 * 2)(*extent) if extent is not None else None, ns, nd, size, edge_size, method,
-                                  flags | _lib.REMAP_DRY_RUN, None, ctypes.byref(launches))
-    return rc, lib.gt4mi_last_error(), launches.value
+    return E.call("gt4mi_vertical_remap", as_arg(dst), as_arg(src), nfields, as_arg(zs), as_arg(zd), int64s(extent), ns, nd, size, edge_size,
+                  method, flags | _lib.REMAP_DRY_RUN, None, outs=(77,))
 
 
 def test_every_refusal_of_the_c_entry_without_a_gpu():
@@ -282,7 +257,7 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
     assert rc == UNS and b"dst 0 and src_edges overlap in memory" in msg
     rc, msg, _ = _call(d, s, zs, column(DST + 8 * 40, ND + 1))
     assert rc == UNS and b"dst 0 and dst_edges overlap in memory" in msg
-    two = lambda a, b: (_lib.Field * 2)(a, b)  # noqa: E731
+    two = lambda a, b: E.table((a, b))  # noqa: E731
     rc, msg, _ = _call(two(d, _field(DST + 0x1000, ND)), two(s, _field(DST + 64, NS)), zs, zd, nfields=2)
     assert rc == UNS and b"dst 0 and src 1 overlap in memory" in msg
     rc, msg, _ = _call(two(d, _field(DST + 128, ND)), two(s, _field(SRC + 0x1000, NS)), zs, zd, nfields=2)
@@ -301,17 +276,14 @@ def test_every_refusal_of_the_c_entry_without_a_gpu():
 
 
 def test_launches_are_one_per_eight_pairs():
-    d = (_lib.Field * 9)(*[_field(DST + n * 0x1000, ND) for n in range(9)])
-    s = (_lib.Field * 9)(*[_field(SRC + n * 0x1000, NS) for n in range(9)])
+    d = E.table(_field(DST + n * 0x1000, ND) for n in range(9))
+    s = E.table(_field(SRC + n * 0x1000, NS) for n in range(9))
     zs, zd = _field(ZS, NS + 1), _field(ZD, ND + 1)
     assert [_call(d, s, zs, zd, nfields=n)[2] for n in (1, 3, 8, 9)] == [1, 1, 1, 2]
 
 
 def test_the_kernels_are_in_the_resource_log_without_scratch():
-    log = _lib.LIB_PATH.with_name("libgt4py_amd.resources.log")
-    assert log.exists(), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
-    kernels = re.findall(r"remark: Function Name: (\S*vertical_remap_kernel\S*).*?ScratchSize \[bytes/lane\]: (\d+).*?"
-                         r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", log.read_text(), re.S)
+    kernels = E.kernel_resources(r"vertical_remap_kernel")
     # 2 field types x 2 edge types x 2 methods x the register budgets for 1, 4 and 8 entries
     assert len(kernels) == 24 and len({name for name, *_ in kernels}) == 24, kernels
     for name, scratch, waves, lds in kernels:
@@ -319,18 +291,8 @@ def test_the_kernels_are_in_the_resource_log_without_scratch():
 
 
 # ---- the Python interface: every refusal before any GPU work ---------------------------------------------------------------
-def _host_field(shape=(8, 9, 5), dtype="float64"):
-    """A DeviceArray around HOST memory: enough for every argument check (they need no device); a call that passed them all
-    is refused last, for not being on the device."""
-    import torch
-
-    from gt4py_amd.storage.device_array import DeviceArray, torch_dtype
-
-    return DeviceArray(torch.zeros(shape, dtype=torch_dtype(dtype)))
-
-
 def _good(**over):
-    args = dict(dst=_host_field((8, 9, 3)), src=_host_field(), src_edges=_host_field((8, 9, 6)), dst_edges=_host_field((4,)))
+    args = dict(dst=E.host_field((8, 9, 3)), src=E.host_field(HOST), src_edges=E.host_field((8, 9, 6)), dst_edges=E.host_field((4,)))
     args.update(over)
     return args.pop("dst"), args.pop("src"), args
 
@@ -363,7 +325,7 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(ValueError, match="at least one"):
         R([], [], **edges)
     with pytest.raises(ValueError, match="2 destination.s. and 1 source"):
-        R([dst, _host_field((8, 9, 3))], [src], **edges)
+        R([dst, E.host_field((8, 9, 3))], [src], **edges)
     with pytest.raises(TypeError, match="host"):
         R(torch.zeros(8, 9, 3, dtype=torch.float64), src, **edges)  # as_device_array's own refusal
     with pytest.raises(TypeError):
@@ -371,48 +333,43 @@ def test_python_refusals_about_the_fields_themselves():
     with pytest.raises(TypeError):
         R(dst, src, src_edges=np.zeros((8, 9, 6)), dst_edges=edges["dst_edges"])
     with pytest.raises(ValueError, match="takes IJK fields"):
-        R(_host_field((8, 9)), src, **edges)
+        R(E.host_field((8, 9)), src, **edges)
     with pytest.raises(ValueError, match="dst_edges must be an IJK field or a Field.K."):
-        R(dst, src, src_edges=edges["src_edges"], dst_edges=_host_field((9, 4)))
+        R(dst, src, src_edges=edges["src_edges"], dst_edges=E.host_field((9, 4)))
     # dtypes: the fields share one, the edge fields share one (not necessarily the same), all float32 or float64
     with pytest.raises(TypeError, match="share a dtype"):
-        R(_host_field((8, 9, 3), "float32"), src, **edges)
+        R(E.host_field((8, 9, 3), "float32"), src, **edges)
     with pytest.raises(TypeError, match="float32 or float64 fields"):
-        R(_host_field((8, 9, 3), "int64"), _host_field(dtype="int64"), **edges)
+        R(E.host_field((8, 9, 3), "int64"), E.host_field(HOST, dtype="int64"), **edges)
     with pytest.raises(TypeError, match="src_edges and dst_edges share a dtype"):
-        R(dst, src, src_edges=edges["src_edges"], dst_edges=_host_field((4,), "float32"))
+        R(dst, src, src_edges=edges["src_edges"], dst_edges=E.host_field((4,), "float32"))
     with pytest.raises(TypeError, match="edge fields are float32 or float64"):
-        R(dst, src, src_edges=_host_field((8, 9, 6), "int32"), dst_edges=_host_field((4,), "int32"))
+        R(dst, src, src_edges=E.host_field((8, 9, 6), "int32"), dst_edges=E.host_field((4,), "int32"))
     with pytest.raises(TypeError, match="device fields"):  # float32 fields against float64 edges is a combination of its own
-        R(_host_field((8, 9, 3), "float32"), _host_field(dtype="float32"), **edges)
+        R(E.host_field((8, 9, 3), "float32"), E.host_field(HOST, dtype="float32"), **edges)
     # levels: the sources share theirs, an edge field has exactly one more
     with pytest.raises(ValueError, match="sources of one call share their number of levels: 5 and 4"):
-        R([dst, _host_field((8, 9, 3))], [src, _host_field((8, 9, 4))], **edges)
+        R([dst, E.host_field((8, 9, 3))], [src, E.host_field((8, 9, 4))], **edges)
     with pytest.raises(ValueError, match="src_edges has 5 edges along K, 5 levels need 6"):
-        R(dst, src, src_edges=_host_field((8, 9, 5)), dst_edges=edges["dst_edges"])
+        R(dst, src, src_edges=E.host_field((8, 9, 5)), dst_edges=edges["dst_edges"])
     with pytest.raises(ValueError, match="dst_edges has 3 edges along K, 3 levels need 4"):
-        R(dst, src, src_edges=edges["src_edges"], dst_edges=_host_field((3,)))
+        R(dst, src, src_edges=edges["src_edges"], dst_edges=E.host_field((3,)))
     # a field onto itself; a dst that is also the edge field
-    x = _host_field((8, 9, 5))
+    x = E.host_field((8, 9, 5))
     with pytest.raises(TypeError, match="dst 0 and src 0 overlap in memory"):
-        R(x, x, src_edges=edges["src_edges"], dst_edges=_host_field((6,)))
-    z = _host_field((8, 9, 6))
+        R(x, x, src_edges=edges["src_edges"], dst_edges=E.host_field((6,)))
+    z = E.host_field((8, 9, 6))
     with pytest.raises(TypeError, match="dst 0 and src_edges overlap in memory"):
-        R(z, _host_field((8, 9, 5)), src_edges=z, dst_edges=_host_field((7,)))
+        R(z, E.host_field((8, 9, 5)), src_edges=z, dst_edges=E.host_field((7,)))
 
 
 def test_a_frozen_remap_knows_its_box_and_refuses_to_run_after_an_array_died(monkeypatch):
     """The weak references are taken last, behind the device check: what they guard is shown on a VerticalRemap whose device
     check is made to pass for host memory -- the call itself is never reached, the dead reference is found first."""
-    import torch
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda: None)
-    dsts, srcs = [_host_field((8, 9, 3)) for _ in range(9)], [_host_field((10, 9, 5)) for _ in range(9)]
-    zs, zd = _host_field((8, 9, 6), "float32"), _host_field((4,), "float32")
+    E.on_device(monkeypatch)
+    dsts, srcs = [E.host_field((8, 9, 3)) for _ in range(9)], [E.host_field((10, 9, 5)) for _ in range(9)]
+    zs, zd = E.host_field((8, 9, 6), "float32"), E.host_field((4,), "float32")
     vr = vertical.VerticalRemap(dsts, srcs, src_edges=zs, dst_edges=zd, method="plm", halo=1)
     assert (vr.ns, vr.nd, vr.launches, vr.extent, vr.domain, vr.origin, vr.method) == (5, 3, 2, (8, 9), (6, 7), (1, 1, 0), "plm")
     del zd
-    gc.collect()
-    with pytest.raises(RuntimeError, match="no longer exists"):
-        vr()
+    E.refuses_a_dead_array(vr)
