@@ -293,6 +293,16 @@ class Bound:
         if rc != _lib.OK:
             _lib.check(self._entry, rc)
 
+    def _wait(self) -> None:
+        """What ``get()`` of a class with results waits for: the stream of the last DIRECT call (``self._stream``) and the stream
+        that is current now.  A replay of a captured graph is no call of the object: it runs on the stream it is replayed on,
+        while ``self._stream`` still names the capture's stream, on which nothing ran.  So: call ``get()`` with the replay's
+        stream current (or synchronise that stream first)."""
+        self._stream.synchronize()
+        current = self._current_stream()
+        if current != self._stream:
+            current.synchronize()
+
     def _check_alive(self) -> None:
         for r in self._refs:  # (a plain loop: this runs in front of every call)
             if r() is None:

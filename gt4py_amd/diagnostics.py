@@ -199,11 +199,12 @@ class _StatsCall(Bound):
     _record = None  # what get() makes of one entry's block of the result
 
     def get(self) -> list:
-        """Synchronise the stream of the last call and return its results, one record per entry (``RuntimeError`` before the
-        first call)."""
+        """Synchronise the stream of the last call and the stream that is current now (where a replay of a captured graph ran:
+        call ``get()`` with that stream current) and return the results, one record per entry (``RuntimeError`` before the first
+        call)."""
         if self._stream is None:
             raise RuntimeError(f"{self._name}.get: the object has not been called yet")
-        self._stream.synchronize()
+        self._wait()
         return [self._record(block) for block in self.result.tensor.cpu().numpy()]
 
     def _row(self, what: str, name: str, entry: int) -> DeviceArray:

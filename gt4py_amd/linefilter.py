@@ -179,7 +179,7 @@ class LineSpectrum(_Lines):
         (``RuntimeError`` before the first call)."""
         if self._stream is None:
             raise RuntimeError("LineSpectrum.get: the object has not been called yet")
-        self._stream.synchronize()
+        self._wait()
         rows = self.result.tensor.cpu().numpy()
         out = np.empty(rows.shape[:1] + rows.shape[2:], dtype=np.complex128)
         out.real, out.imag = rows[:, 0], rows[:, 1]  # (the parts as they are: 1j * inf would put a NaN beside it)

@@ -80,7 +80,9 @@ class LineFind(Bound):
     ``result`` is a float64 :class:`DeviceArray` of shape ``(nf, 3, nB, nA)`` (rows in the order of :data:`ROWS`; A < B the two
     other axes: the layout of ``LineStats.result``); :meth:`section` hands out one row of it as an ``(nA, nB)`` view, which a
     stencil takes as ``Field[IJ, np.float64]`` (axis K), ``Field[IK, ...]`` (axis J) or ``Field[JK, ...]`` (axis I) in the same
-    stream with no synchronisation in between.  Every call overwrites it.  The object holds raw pointers and weak references to
+    stream with no synchronisation in between.  Every call overwrites it.  The levels are passed BY VALUE at each call: a captured
+    graph keeps the levels of its capture, :meth:`set_level` changes the next direct call only.  :meth:`get` also waits for the stream
+    that is current then, so after a replay call it with the replay's stream current.  The object holds raw pointers and weak references to
     the CALLER's objects, not the arrays: it refuses to run once one of them has died."""
 
     _entry, _dry_run_bit = "gt4mi_line_find", _lib.FIND_DRY_RUN
@@ -164,7 +166,7 @@ class LineFind(Bound):
         the first call)."""
         if self._stream is None:
             raise RuntimeError("LineFind.get: the object has not been called yet")
-        self._stream.synchronize()
+        self._wait()
         return [Found.from_rows(block, self.what) for block in self.result.tensor.cpu().numpy()]
 
     def section(self, name: str, entry: int = 0) -> DeviceArray:

@@ -149,7 +149,7 @@ class Sample(Bound):
         call)."""
         if self._stream is None:
             raise RuntimeError("Sample.get: the object has not been called yet")
-        self._stream.synchronize()
+        self._wait()
         return self.result.tensor.cpu().numpy()
 
     def column(self, n: int = 0) -> DeviceArray:

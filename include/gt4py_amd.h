@@ -790,7 +790,9 @@ int gt4mi_line_find(const gt4mi_field* fields, int nfields, const gt4mi_field* c
  * `result` holds nfields x nrows x (nbins + 3) int64 counters, result[(k * nrows + row) * (nbins + 3) + slot]: the bins, then
  * GT4MI_HISTOGRAM_BELOW, GT4MI_HISTOGRAM_ABOVE and GT4MI_HISTOGRAM_NAN at nbins + 0, 1, 2.  It is aligned to 8 bytes and meets no field and
  * not the edges.  No byte outside it is written.  Without GT4MI_HISTOGRAM_ACCUMULATE it is zeroed first, in stream order, by a
- * hipMemsetAsync on `stream`; with the flag the counts are ADDED to what it holds (a run-long PDF: one call per step into one result).
+ * small kernel on `stream` (not a hipMemsetAsync: replays of a captured call were seen to leave other words than zero with it,
+ * for a reason that was not found); with the flag the counts are ADDED to what it holds (a run-long PDF: one call per step into
+ * one result).
  * THE CONTRACT (csrc/field_histogram.hip.h states it again, tests/histogram_ref.py restates it in plain Python and in numpy).  Every item x
  * of a row's box is converted exactly to float64 and lands in exactly one counter of the row:
  *   nan      if x != x
@@ -817,7 +819,7 @@ int gt4mi_line_find(const gt4mi_field* fields, int nfields, const gt4mi_field* c
  * field, more than 2^31 - 1 items or 2^24 levels (GT4MI_ERR_UNSUPPORTED); a box that does not fit its field (GT4MI_ERR_OUT_OF_BOUNDS).
  * Every check runs before anything is enqueued.  With GT4MI_HISTOGRAM_DRY_RUN the checks run (those of the edges among them), *path and
  * *launches are set and no device is touched; `edges` and `result` may then be NULL (what is passed is checked).  *launches (may be NULL) =
- * the kernels the call enqueues: 1 (the zeroing is a memset, not a kernel). */
+ * the counting kernels the call enqueues: 1 (the zeroing is not counted). */
 enum { GT4MI_HISTOGRAM_MAX_FIELDS = 8, GT4MI_HISTOGRAM_MAX_BINS = 4096, GT4MI_HISTOGRAM_EXTRA = 3 };
 enum { GT4MI_HISTOGRAM_BELOW = 0, GT4MI_HISTOGRAM_ABOVE = 1, GT4MI_HISTOGRAM_NAN = 2 };
 enum { GT4MI_HISTOGRAM_WHOLE = 0, GT4MI_HISTOGRAM_BY_K = 1 };
