@@ -168,6 +168,14 @@ def recognise(stencil: ir.Stencil, options: gt_definitions.BuildOptions) -> Opti
 # ---------------------------------------------------------------------------------------------
 # the generated StencilObject subclass
 # ---------------------------------------------------------------------------------------------
+def launch_key(domain, arrays, origins):
+    """Key of the cached ``Field`` descriptors of a call, made of everything they hold: the domain, per array its identity AND
+    its address, shape and byte strides as they are now (the tensor behind one object can be re-pointed), and the origins.
+    A pure function."""
+    return (tuple(int(d) for d in domain), tuple((id(a), a.ptr, tuple(a.shape), tuple(a.strides)) for a in arrays),
+            tuple(tuple(o) for o in origins))
+
+
 class HipStencilObject(StencilObject):
     """StencilObject whose ``run`` launches a gfx950 kernel through the C ABI."""
 
@@ -186,10 +194,11 @@ class HipStencilObject(StencilObject):
         except Exception as ex:  # pragma: no cover - no GPU
             raise RuntimeError("hip:mi300 needs PyTorch-ROCm with a visible MI355X") from ex
 
-        # ctypes structs of a call are cached per (arrays, origins, domain): building them costs more Python
-        # time than the launch.  Arrays are remembered by identity through weak references.
+        # ctypes structs of a call are cached per `launch_key`: building them costs more Python time than the
+        # launch.  An array is its object (remembered through a weak reference) together with the address, shape
+        # and strides it has at this call; scalars are passed on every call and are not part of a plan.
         names = [binding.roles[r] for r in binding.roles if binding.roles[r] in cls._gt_field_info_]
-        ckey = (tuple(int(d) for d in domain), tuple(id(arguments[n]) for n in names), tuple(tuple(origin[n]) for n in names))
+        ckey = launch_key(domain, [arguments[n] for n in names], [origin[n] for n in names])
         entry = cls._gt_launch_cache_.get(ckey)
         if entry is not None and all(r() is arguments[n] for n, r in entry[0]):
             _, dom, refs = entry

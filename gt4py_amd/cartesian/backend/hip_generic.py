@@ -293,6 +293,22 @@ def select_twin(kern, twins, lead: int, no_alias: bool, geometry, domain, levels
     return label, (-(-ni // kern.block[0]), -(-nj // kern.block[1]), nk), tuple(kern.block)
 
 
+def scalar_bits(dtype, value) -> bytes:
+    """The bytes a scalar argument has in the kernel-argument block: ``value`` converted to the parameter's dtype.  ``0.0`` and
+    ``-0.0`` differ, two NaNs of one payload agree, ``1``, ``1.0`` and ``True`` agree.  TypeError for what is not hashable (a 0-d
+    array, which numpy would convert all the same): such a call is not cached."""
+    hash(value)
+    return np.dtype(dtype).type(value).tobytes()
+
+
+def launch_key(stream, domain, arrays, origins, dtypes, values):
+    """Key of a launch plan, made of everything the plan holds: the stream (whose scratch buffer its temporaries point into), the
+    domain, per array its identity AND its address, shape and byte strides as they are now (the tensor behind one object can be
+    re-pointed), the origins, and the bits of every scalar as the kernel receives it.  A pure function; TypeError = do not cache."""
+    return (stream, *domain, tuple((id(a), a.ptr, tuple(a.shape), tuple(a.strides)) for a in arrays),
+            tuple(tuple(o) for o in origins), tuple(scalar_bits(t, v) for t, v in zip(dtypes, values)))
+
+
 class HipGenericStencilObject(StencilObject):
     """StencilObject whose ``run`` launches run-time compiled gfx950 kernels, one per stage."""
 
@@ -314,13 +330,15 @@ class HipGenericStencilObject(StencilObject):
         except Exception as ex:  # pragma: no cover - no GPU
             raise RuntimeError("hip:mi300 needs PyTorch-ROCm with a visible MI355X") from ex
         dI, dJ, dK = (int(d) for d in domain)
-        # Launch plans are cached per (arrays, origins, domain, scalars): filling the argument block costs
-        # 20-50 us of Python, a cached call ~10 us.  Arrays are remembered by identity through weak
-        # references, so a recycled id() can never alias a dead array.
+        # Launch plans are cached per `launch_key`: filling the argument block costs 20-50 us of Python, a cached call
+        # ~10 us.  An array is its object (remembered through a weak reference, so a recycled id() can never alias a
+        # dead array) together with the address, shape and strides it has at this call; a scalar is its bits in the
+        # parameter's dtype.
         try:
             # ... and per stream: temporaries live in a scratch buffer that concurrent streams must not share
-            ckey = (stream, dI, dJ, dK, tuple(id(arguments[d.name]) for d in plan.api_fields),
-                    tuple(tuple(origin[d.name]) for d in plan.api_fields), tuple(arguments[p.name] for p in plan.params))
+            ckey = launch_key(stream, (dI, dJ, dK), [arguments[d.name] for d in plan.api_fields],
+                              [origin[d.name] for d in plan.api_fields], [p.dtype for p in plan.params],
+                              [arguments[p.name] for p in plan.params])
             entry = cls._gt_launch_cache_.get(ckey)
         except TypeError:  # an unhashable scalar
             ckey = entry = None
