@@ -10,7 +10,14 @@ flags and the stream go and an :class:`Out` where the entry takes an out-pointer
 the descriptors (:func:`field_table`, :func:`_common_domain`), sets ``_flags`` where the object has flags of its own, calls
 :meth:`Bound._dry_run` -- every check of the library on exactly that list, nothing enqueued, the out values returned -- and
 :meth:`Bound._bind` last.  ``__call__`` is the base's: the same list with the object's flags, the stream that is current then and
-null out-pointers."""
+null out-pointers.
+
+A utility WITH RESULTS is a subclass of :class:`BoundResult`, whose ``__call__`` keeps the stream; its ``get()`` opens with
+:meth:`BoundResult._wait` (the refusal before the first call, then the synchronisation) and reads ``result``.  Buffers that the
+object owns and that the entry takes as pointers beside its fields (a result, a workspace, a table) are null class attributes
+that ``_arguments()`` reads; where the constructor would call ``_dry_run``, it calls :meth:`Bound._own_buffers` with a function
+that allocates them and sets the pointers -- the library's refusals come first, the host-array refusal second, an allocation last.
+A device view of one entry checks its index with :meth:`Bound._index`, and the synchronous function is :func:`one_shot`."""
 
 from __future__ import annotations
 
@@ -159,6 +166,15 @@ def _float_pairs(who: str, dst, src, halo, method, methods, *, shared, names: Se
 AXES = {"I": 0, "J": 1, "K": 2}
 
 
+def _axis_index(axis) -> int:
+    """``"I"``, ``"J"``, ``"K"`` or 0, 1, 2 as 0, 1, 2."""
+    if isinstance(axis, str) and axis.upper() in AXES:
+        return AXES[axis.upper()]
+    if not isinstance(axis, bool) and isinstance(axis, (int, np.integer)) and 0 <= int(axis) <= 2:
+        return int(axis)
+    raise ValueError(f"axis must be 'I', 'J', 'K' or 0, 1, 2, not {axis!r}")
+
+
 def _coefficient(a: DeviceArray, axis: int, start) -> "_lib.Field":
     """A field every line reads: IJK, or 1-d along ``axis`` (broadcast: stride 0 along the two other axes)."""
     if a.ndim == 1:  # n items along the line axis: every line reads the same ones
@@ -266,6 +282,25 @@ class Bound:
     def _dry_run(self) -> list:
         return dry_run(self._entry, self._dry_run_bit, self._flags, self._arguments())
 
+    def _own_buffers(self, who: str, arrays, allocate) -> list:
+        """The dry run of a call with buffers of its own, whose pointers are still null: every check of the library, nothing
+        enqueued; then ``allocate(torch, device, outs)`` -- the device of the first of ``arrays``, what the dry run returned --
+        makes the buffers and sets the pointers.  Returns what that dry run returned.  ``who``, ``arrays``: as for :meth:`_bind`."""
+        outs = self._dry_run()
+        refuse_host_arrays(who, arrays)  # (nothing is allocated for a call that cannot be bound)
+        import torch
+
+        allocate(torch, arrays[0].tensor.device, outs)
+        self._dry_run()  # the buffers against the fields (overlap, alignment): the dry run once more, now with them
+        return outs
+
+    def _index(self, entry, noun: str = "entry") -> int:
+        """``entry`` as an index into the ``_n`` entries of the call; ``noun``: what the refusal calls them."""
+        entry = int(entry)
+        if not 0 <= entry < self._n:
+            raise IndexError(f"{noun} {entry} of {self._n}")
+        return entry
+
     def _bind(self, who: str, arrays, objects) -> None:
         """``who``: the public function's name; ``arrays``: the DeviceArrays of the call; ``objects``: what the caller passed."""
         refuse_host_arrays(who, arrays)  # (last: none of the checks before needs a device)
@@ -293,18 +328,42 @@ class Bound:
         if rc != _lib.OK:
             _lib.check(self._entry, rc)
 
-    def _wait(self) -> None:
-        """What ``get()`` of a class with results waits for: the stream of the last DIRECT call (``self._stream``) and the stream
-        that is current now.  A replay of a captured graph is no call of the object: it runs on the stream it is replayed on,
-        while ``self._stream`` still names the capture's stream, on which nothing ran.  So: call ``get()`` with the replay's
-        stream current (or synchronise that stream first)."""
-        self._stream.synchronize()
-        current = self._current_stream()
-        if current != self._stream:
-            current.synchronize()
-
     def _check_alive(self) -> None:
         for r in self._refs:  # (a plain loop: this runs in front of every call)
             if r() is None:
                 name = type(self).__name__
                 raise RuntimeError(f"{name}: an array this call was bound to no longer exists; build a new {name}")
+
+
+class BoundResult(Bound):
+    """A frozen call whose ``get()`` brings a result to the host: the call keeps its stream for it."""
+
+    _stream = None  # the stream of the last direct call
+
+    def __call__(self) -> None:  # (Bound's, in one frame of its own: this is the host time of a call)
+        self._check_alive()
+        self._stream = self._current_stream()  # (kept for get())
+        rc = self._native(*self._before, self._stream.cuda_stream, *self._after)
+        if rc != _lib.OK:
+            _lib.check(self._entry, rc)
+
+    def _wait(self) -> None:
+        """What ``get()`` opens with: ``RuntimeError`` before the first call, else it waits for the stream of the last DIRECT call
+        (``self._stream``) and the stream that is current now.  A replay of a captured graph is no call of the object: it runs on
+        the stream it is replayed on, while ``self._stream`` still names the capture's stream, on which nothing ran.  So: call
+        ``get()`` with the replay's stream current (or synchronise that stream first)."""
+        if self._stream is None:
+            raise RuntimeError(f"{type(self).__name__}.get: the object has not been called yet")
+        self._stream.synchronize()
+        current = self._current_stream()
+        if current != self._stream:
+            current.synchronize()
+
+
+def one_shot(frozen_class, fields, **kwargs):
+    """The synchronous form of a frozen call with results: ``fields`` are the positional arguments as the public function got
+    them, the fields themselves or one list or tuple of them; freeze, call, get."""
+    fields = list(fields[0]) if len(fields) == 1 and isinstance(fields[0], (tuple, list)) else list(fields)
+    frozen = frozen_class(fields, **kwargs)
+    frozen()
+    return frozen.get()

@@ -39,7 +39,7 @@ from typing import Any, List, NamedTuple, Optional, Sequence, Union
 import numpy as np
 
 from . import _lib
-from ._bound import AXES, FLAGS, FLOATS, STREAM, Bound, Out, _box_of, _halo4, _shape3, refuse_host_arrays
+from ._bound import FLAGS, FLOATS, STREAM, BoundResult, Out, _axis_index, _box_of, _halo4, _shape3, one_shot
 from .storage.device_array import DeviceArray, as_device_array
 
 
@@ -122,7 +122,7 @@ def merge(stats: Sequence[Stats]) -> Stats:
     return out
 
 
-class _StatsCall(Bound):
+class _StatsCall(BoundResult):
     """What :class:`FieldStats` and :class:`LevelStats` share: everything but the entry, the public function's name in the
     messages and the shape of a result block."""
 
@@ -132,7 +132,9 @@ class _StatsCall(Bound):
     def _result_block(self) -> tuple:
         raise NotImplementedError
 
-    def _arguments(self) -> tuple:  # (no workspace and no result until the first dry run has said how large they are)
+    _workspace_ptr, _workspace_bytes, _result_ptr = None, 0, None  # (until the first dry run has said how large they are)
+
+    def _arguments(self) -> tuple:
         return (self._fields, self._others, self._n, self._domain3, self._itemsize, self._workspace_ptr, self._workspace_bytes,
                 self._result_ptr, FLAGS, STREAM, Out(ctypes.c_int64), Out(ctypes.c_int))
 
@@ -175,35 +177,25 @@ class _StatsCall(Bound):
             if o is not None:
                 self._others[n] = describe(o, True)
         self._domain3 = _lib.domain3(domain)
-        # every check of the library, nothing enqueued; also: the workspace the call needs and how many kernels it makes
-        self._workspace_ptr, self._workspace_bytes, self._result_ptr = None, 0, None
-        needed, self.launches = self._dry_run()
-        refuse_host_arrays(who, every)  # (nothing is allocated for a call that cannot be bound)
-        import torch
 
-        self._workspace = torch.empty(needed // 8, dtype=torch.float64, device=first.tensor.device)
-        self.result = DeviceArray(torch.zeros((self._n,) + self._result_block(), dtype=torch.float64, device=first.tensor.device))
-        self._workspace_ptr, self._workspace_bytes, self._result_ptr = self._workspace.data_ptr(), needed, self.result.ptr
-        self._dry_run()  # the buffers against the fields (overlap, alignment): the dry run once more, now with them
+        def allocate(torch, device, outs):
+            needed = outs[0]
+            self._workspace = torch.empty(needed // 8, dtype=torch.float64, device=device)
+            self.result = DeviceArray(torch.zeros((self._n,) + self._result_block(), dtype=torch.float64, device=device))
+            self._workspace_ptr, self._workspace_bytes, self._result_ptr = self._workspace.data_ptr(), needed, self.result.ptr
+
+        # the dry run says: the workspace the call needs, how many kernels it makes and, for LineStats, the kernel the strides selected
+        _, self.launches, *path = self._own_buffers(who, every, allocate)
+        if path:
+            self.path, = path
         self._bind(who, every, fields + [o for o in others if o is not None])
-        self._stream = None
 
-    def __call__(self) -> None:
-        self._check_alive()
-        self._stream = self._current_stream()  # (kept for get())
-        rc = self._native(*self._before, self._stream.cuda_stream, *self._after)
-        if rc != _lib.OK:
-            _lib.check(self._entry, rc)
-
-    _name = ""      # the class's name in get()'s refusal
     _record = None  # what get() makes of one entry's block of the result
 
     def get(self) -> list:
         """Synchronise the stream of the last call and the stream that is current now (where a replay of a captured graph ran:
         call ``get()`` with that stream current) and return the results, one record per entry (``RuntimeError`` before the first
         call)."""
-        if self._stream is None:
-            raise RuntimeError(f"{self._name}.get: the object has not been called yet")
         self._wait()
         return [self._record(block) for block in self.result.tensor.cpu().numpy()]
 
@@ -211,18 +203,14 @@ class _StatsCall(Bound):
         """Row ``name`` of entry ``entry`` of ``result``, as the device holds it; ``what``: what the caller calls it."""
         if name not in PROFILE_ROWS:
             raise ValueError(f"no {what} {name!r}: the rows are {', '.join(PROFILE_ROWS)}")
-        entry = int(entry)
-        if not 0 <= entry < self._n:
-            raise IndexError(f"entry {entry} of {self._n}")
-        return self.result[entry, PROFILE_ROWS.index(name)]
+        return self.result[self._index(entry), PROFILE_ROWS.index(name)]
 
 
 def _one_shot(frozen_class, fields, other, **kwargs):
-    """The synchronous form of a frozen call: ``other`` for every field or one per field, freeze, call, get."""
+    """The synchronous form of a statistics call: ``other`` for every field or one per field, then :func:`one_shot` on the fields
+    as ONE tuple (they come positionally only: a list among them is no field)."""
     others = list(other) if isinstance(other, (list, tuple)) else None if other is None else [other] * len(fields)
-    frozen = frozen_class(fields, others=others, **kwargs)
-    frozen()
-    return frozen.get()
+    return one_shot(frozen_class, (fields,), others=others, **kwargs)
 
 
 class FieldStats(_StatsCall):
@@ -236,7 +224,7 @@ class FieldStats(_StatsCall):
     The object holds raw pointers and weak references to the CALLER's objects, not the arrays: it refuses to run once one of
     them has died.  (An exporter that cannot be weakly referenced is held instead, so its memory stays valid.)"""
 
-    _who, _entry, _name, _record = "field_stats", "gt4mi_field_stats", "FieldStats", Stats.from_row
+    _who, _entry, _record = "field_stats", "gt4mi_field_stats", Stats.from_row
 
     def _result_block(self) -> tuple:
         return (_lib.STATS_SLOTS,)
@@ -390,7 +378,7 @@ class LevelStats(_StatsCall):
     The object holds raw pointers and weak references to the CALLER's objects, as :class:`FieldStats` does: it refuses to run
     once one of them has died."""
 
-    _who, _entry, _name, _record = "level_stats", "gt4mi_level_stats", "LevelStats", Profile.from_rows
+    _who, _entry, _record = "level_stats", "gt4mi_level_stats", Profile.from_rows
 
     def _result_block(self) -> tuple:
         return (_lib.LEVEL_STATS_ROWS, self.domain[2])
@@ -418,15 +406,6 @@ def level_stats(*fields, other: Union[None, Any, Sequence[Any]] = None, origin: 
 # ---- along a line: zonal means and their kin ------------------------------------------------------------------------------------
 #: the rows of a LineStats result block, in order: those of a LevelStats block
 LINE_ROWS = PROFILE_ROWS
-
-
-def _axis_index(axis) -> int:
-    """``"I"``, ``"J"``, ``"K"`` or 0, 1, 2 as 0, 1, 2."""
-    if isinstance(axis, str) and axis.upper() in AXES:
-        return AXES[axis.upper()]
-    if not isinstance(axis, bool) and isinstance(axis, (int, np.integer)) and 0 <= int(axis) <= 2:
-        return int(axis)
-    raise ValueError(f"axis must be 'I', 'J', 'K' or 0, 1, 2, not {axis!r}")
 
 
 def _np_minimum(a, b):
@@ -510,20 +489,16 @@ class LineStats(_StatsCall):
     whatever the axis, the layout or the other lines are.  The object holds raw pointers and weak references to the CALLER's
     objects, as :class:`FieldStats` does: it refuses to run once one of them has died."""
 
-    _who, _entry, _name, _record = "line_stats", "gt4mi_line_stats", "LineStats", Lines.from_rows
+    _who, _entry, _record = "line_stats", "gt4mi_line_stats", Lines.from_rows
 
     def __init__(self, fields: Sequence[Any], *, axis, others: Optional[Sequence[Any]] = None, origin: Optional[Sequence[int]] = None,
                  domain: Optional[Sequence[int]] = None, halo=0):
-        self.axis, self.path = _axis_index(axis), None
+        self.axis = _axis_index(axis)
         super().__init__(fields, others=others, origin=origin, domain=domain, halo=halo)
 
     def _arguments(self) -> tuple:
         return (self._fields, self._others, self._n, self._domain3, self.axis, self._itemsize, self._workspace_ptr, self._workspace_bytes,
                 self._result_ptr, FLAGS, STREAM, Out(ctypes.c_int64), Out(ctypes.c_int), Out(ctypes.c_int))
-
-    def _dry_run(self) -> list:
-        needed, launches, self.path = super()._dry_run()
-        return [needed, launches]
 
     def _result_block(self) -> tuple:
         a, b = (d for d in range(3) if d != self.axis)

@@ -31,7 +31,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _as_list, _box_of, _halo4, field_table, refuse_host_arrays
+from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _as_list, _box_of, _halo4, field_table, one_shot
 from .storage.device_array import DeviceArray, as_device_array
 
 BYS = {None: _lib.HISTOGRAM_WHOLE, "K": _lib.HISTOGRAM_BY_K}
@@ -151,6 +151,7 @@ class Histogram(Bound):
     holds raw pointers and weak references to the CALLER's fields, not the arrays: it refuses to run once one has died."""
 
     _entry, _dry_run_bit = "gt4mi_field_histogram", _lib.HISTOGRAM_DRY_RUN
+    _edges_ptr = _result_ptr = None
 
     def _arguments(self) -> tuple:
         return (self._fields, self._n, self._extent3, self._size, self.bins, self._edges_ptr, self._edges_host, self._by, self._result_ptr,
@@ -191,18 +192,15 @@ class Histogram(Bound):
         self._extent3 = _lib.domain3(domain)
         self._edges_host = self.edges.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         self._flags = (_lib.HISTOGRAM_ACCUMULATE if self.accumulate else 0) | (_lib.HISTOGRAM_EDGES_PER_FIELD if e.ndim == 2 else 0)
-        self._edges_ptr = self._result_ptr = None
-        path, self.launches = self._dry_run()  # every check of the library, the edges among them; nothing enqueued
-        self.path = PATHS.get(path)
-        refuse_host_arrays("histogram", arrays)  # (nothing is allocated for a call that cannot be bound)
-        import torch
-
-        device = first.tensor.device
         self.rows = domain[2] if by == "K" else 1
-        self._edges_device = torch.from_numpy(self.edges).to(device)
-        self.result = DeviceArray(torch.zeros((self._n, self.rows, self.bins + _lib.HISTOGRAM_EXTRA), dtype=torch.int64, device=device))
-        self._edges_ptr, self._result_ptr = self._edges_device.data_ptr(), self.result.ptr
-        self._dry_run()  # the buffers against the fields (overlap, alignment): the dry run once more, now with them
+
+        def allocate(torch, device, outs):
+            self._edges_device = torch.from_numpy(self.edges).to(device)
+            self.result = DeviceArray(torch.zeros((self._n, self.rows, self.bins + _lib.HISTOGRAM_EXTRA), dtype=torch.int64, device=device))
+            self._edges_ptr, self._result_ptr = self._edges_device.data_ptr(), self.result.ptr
+
+        path, self.launches = self._own_buffers("histogram", arrays, allocate)  # (the library's checks: the edges among them)
+        self.path = PATHS.get(path)
         self._bind("histogram", arrays, fields)
 
     @classmethod
@@ -217,16 +215,10 @@ class Histogram(Bound):
         """Zero the result on the current stream, in stream order (for ``accumulate=True``: the start of a new period)."""
         self.result.tensor.zero_()
 
-    def _entry_index(self, entry: int) -> int:
-        entry = int(entry)
-        if not 0 <= entry < self._n:
-            raise IndexError(f"entry {entry} of {self._n}")
-        return entry
-
     def counts(self, entry: int = 0) -> DeviceArray:
         """The device view (no copy) of the bins of one field, ``(nb,)`` or ``(nk, nb)`` int64: what the last call (or the calls
         since the last :meth:`reset`) left there, in stream order."""
-        block = self.result[self._entry_index(entry)]
+        block = self.result[self._index(entry)]
         return block[:, : self.bins] if self.by == "K" else block[0, : self.bins]
 
     def get(self) -> List[Hist]:
@@ -253,7 +245,4 @@ def histogram(*fields, edges, by: Optional[str] = None, halo=0, origin: Optional
 
     Raises ``ValueError`` / ``TypeError`` (with the library's message) before any GPU work.  In a time loop build a
     :class:`Histogram` once instead and read it a step late."""
-    fields = list(fields[0]) if len(fields) == 1 and isinstance(fields[0], (tuple, list)) else list(fields)
-    frozen = Histogram(fields, edges=edges, by=by, halo=halo, origin=origin, domain=domain)
-    frozen()
-    return frozen.get()
+    return one_shot(Histogram, fields, edges=edges, by=by, halo=halo, origin=origin, domain=domain)

@@ -31,7 +31,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._bound import FLAGS, STREAM, Bound, Out, _as_list, _line_pairs, field_table, refuse_host_arrays
+from ._bound import FLAGS, STREAM, Bound, BoundResult, Out, _as_list, _line_pairs, field_table, one_shot
 from .storage.device_array import DeviceArray, as_device_array
 
 PATHS = {_lib.LINE_PATH_LANES: "lanes", _lib.LINE_PATH_TILES: "tiles", _lib.LINE_PATH_ITEMS: "items"}
@@ -59,12 +59,9 @@ class _Lines(Bound):
         return (self._dst, self._src, self._n, self._response, self._response_extent, self._twiddle_ptr, self._result_ptr, self._extent3,
                 self._axis, self._size, self._mode, FLAGS, STREAM, Out(ctypes.c_int), Out(ctypes.c_int))
 
-    def _own_tables(self, who: str, arrays) -> None:
-        """After the first dry run: the arrays are on a device, the twiddle table goes there (built once, owned by the object)."""
-        refuse_host_arrays(who, arrays)  # (nothing is allocated for a call that cannot be bound)
-        import torch
-
-        self._twiddles = torch.from_numpy(twiddles(self.n)).to(arrays[0].tensor.device)
+    def _own_twiddles(self, torch, device, outs) -> None:
+        """The twiddle table on the device: built once, owned by the object (what :meth:`_own_buffers` calls)."""
+        self._twiddles = torch.from_numpy(twiddles(self.n)).to(device)
         self._twiddle_ptr = self._twiddles.data_ptr()
 
 
@@ -102,10 +99,8 @@ class LineFilter(_Lines):
         self._response_extent = (ctypes.c_int64 * 2)(*((1, 1) if r.ndim == 1 else r.shape[:2]))
         self._extent3 = _lib.domain3(self.extent)
         self._axis, self._size = ax, d_arrays[0].itemsize
-        path, self.launches = self._dry_run()  # every check of the library, nothing enqueued
+        path, self.launches = self._own_buffers("filter_lines", d_arrays + s_arrays + [r], self._own_twiddles)
         self.path = PATHS.get(path)
-        self._own_tables("filter_lines", d_arrays + s_arrays + [r])
-        self._dry_run()  # the twiddles against the fields (overlap, alignment): the dry run once more, now with them
         self._bind("filter_lines", d_arrays + s_arrays + [r], dsts + srcs + [response])
 
 
@@ -130,7 +125,7 @@ def filter_lines(dst, src, *, axis: str = "I", response, halo=0, origin: Optiona
     LineFilter(dst, src, axis=axis, response=response, halo=halo, origin=origin)()
 
 
-class LineSpectrum(_Lines):
+class LineSpectrum(_Lines, BoundResult):
     """The forward transform alone, for up to 8 fields per launch: frozen like :class:`LineFilter`, with a result the object owns.
 
     ``result`` is a float64 :class:`DeviceArray` of shape ``(nf, 2, ea, eb, nh)``: row 0 the real, row 1 the imaginary part,
@@ -151,24 +146,16 @@ class LineSpectrum(_Lines):
         self._src = field_table(arrays, start)
         self._extent3 = _lib.domain3(self.extent)
         self._axis, self._size = ax, arrays[0].itemsize
-        path, self.launches = self._dry_run()  # every check of the library, nothing enqueued
+
+        def allocate(torch, device, outs):
+            self._own_twiddles(torch, device, outs)
+            ea, eb = (self.extent[d] for d in range(3) if d != ax)
+            self.result = DeviceArray(torch.zeros((self._n, 2, ea, eb, self.n // 2 + 1), dtype=torch.float64, device=device))
+            self._result_ptr = self.result.ptr
+
+        path, self.launches = self._own_buffers("spectrum_lines", arrays, allocate)
         self.path = PATHS.get(path)
-        self._own_tables("spectrum_lines", arrays)
-        import torch
-
-        ea, eb = (self.extent[d] for d in range(3) if d != ax)
-        self.result = DeviceArray(torch.zeros((self._n, 2, ea, eb, self.n // 2 + 1), dtype=torch.float64, device=arrays[0].tensor.device))
-        self._result_ptr = self.result.ptr
-        self._dry_run()  # the result and the twiddles against the fields: the dry run once more, now with them
         self._bind("spectrum_lines", arrays, fields)
-        self._stream = None
-
-    def __call__(self) -> None:
-        self._check_alive()
-        self._stream = self._current_stream()  # (kept for get())
-        rc = self._native(*self._before, self._stream.cuda_stream, *self._after)
-        if rc != _lib.OK:
-            _lib.check(self._entry, rc)
 
     def coefficients(self) -> DeviceArray:
         """The device view ``(nf, 2, ea, eb, nh)`` of the result: what the LAST call left there, in stream order."""
@@ -177,8 +164,6 @@ class LineSpectrum(_Lines):
     def get(self) -> np.ndarray:
         """Synchronise the stream of the last call and return the coefficients as a complex128 numpy array ``(nf, ea, eb, nh)``
         (``RuntimeError`` before the first call)."""
-        if self._stream is None:
-            raise RuntimeError("LineSpectrum.get: the object has not been called yet")
         self._wait()
         rows = self.result.tensor.cpu().numpy()
         out = np.empty(rows.shape[:1] + rows.shape[2:], dtype=np.complex128)
@@ -199,7 +184,4 @@ def spectrum_lines(*fields, axis: str = "I", halo=0, origin: Optional[Sequence[i
     wavenumbers ``0 .. n // 2``: a complex128 numpy array ``(nf, ea, eb, nh)``, in one kernel launch (per 8 fields) on the current
     stream, then a synchronisation of that stream.  Arguments as for :func:`filter_lines`.  In a time loop build a
     :class:`LineSpectrum` once instead."""
-    fields = list(fields[0]) if len(fields) == 1 and isinstance(fields[0], (tuple, list)) else list(fields)
-    frozen = LineSpectrum(fields, axis=axis, halo=halo, origin=origin)
-    frozen()
-    return frozen.get()
+    return one_shot(LineSpectrum, fields, axis=axis, halo=halo, origin=origin)

@@ -30,8 +30,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._bound import FLAGS, STREAM, Bound, Out, _as_list, _coefficient, _line_pairs, field_table, refuse_host_arrays
-from .diagnostics import _axis_index
+from ._bound import FLAGS, STREAM, BoundResult, Out, _as_list, _axis_index, _coefficient, _line_pairs, field_table, one_shot
 from .storage.device_array import DeviceArray
 
 WHATS = {"crossing": _lib.FIND_CROSSING, "argmax": _lib.FIND_ARGMAX, "argmin": _lib.FIND_ARGMIN}
@@ -67,7 +66,7 @@ class Found:
         return f"Found(shape={self.position.shape}, {'crossings' if self.value is None else 'value'})"
 
 
-class LineFind(Bound):
+class LineFind(BoundResult):
     """The frozen form of :func:`find_lines`: arguments are checked (through the library's dry run), the descriptors and the result
     buffer built ONCE; ``__call__()`` makes only the ctypes call, on the stream that is current THEN, and does not synchronise;
     :meth:`get` synchronises that stream and returns one :class:`Found` per field.
@@ -86,6 +85,7 @@ class LineFind(Bound):
     the CALLER's objects, not the arrays: it refuses to run once one of them has died."""
 
     _entry, _dry_run_bit = "gt4mi_line_find", _lib.FIND_DRY_RUN
+    _result_ptr = None
 
     def _arguments(self) -> tuple:
         coord = None if self._coord is None else ctypes.byref(self._coord)
@@ -125,19 +125,15 @@ class LineFind(Bound):
         self._extent3 = _lib.domain3(self.extent)
         self._axis, self._size, self._what, self._direction = ax, arrays[0].itemsize, WHATS[what], DIRECTIONS[direction]
         self._flags = _lib.FIND_REVERSE if self.reverse else 0
-        self._result_ptr = None
-        path, self.launches = self._dry_run()  # every check of the library, nothing enqueued
-        self.path = PATHS.get(path)
-        refuse_host_arrays("find_lines", arrays + z_arrays)  # (nothing is allocated for a call that cannot be bound)
-        import torch
 
-        a, b = (d for d in range(3) if d != ax)
-        self.result = DeviceArray(torch.zeros((self._n, _lib.FIND_ROWS, self.extent[b], self.extent[a]), dtype=torch.float64,
-                                              device=arrays[0].tensor.device))
-        self._result_ptr = self.result.ptr
-        self._dry_run()  # the result against the fields (overlap, alignment): the dry run once more, now with it
+        def allocate(torch, device, outs):
+            a, b = (d for d in range(3) if d != ax)
+            self.result = DeviceArray(torch.zeros((self._n, _lib.FIND_ROWS, self.extent[b], self.extent[a]), dtype=torch.float64, device=device))
+            self._result_ptr = self.result.ptr
+
+        path, self.launches = self._own_buffers("find_lines", arrays + z_arrays, allocate)
+        self.path = PATHS.get(path)
         self._bind("find_lines", arrays + z_arrays, fields + list(shared))
-        self._stream = None
 
     @property
     def level(self) -> Optional[tuple]:
@@ -154,18 +150,9 @@ class LineFind(Bound):
             raise ValueError(f"one level for every field or one per field: {len(values)} levels for {self._n} field(s)")
         self._level[:] = values
 
-    def __call__(self) -> None:
-        self._check_alive()
-        self._stream = self._current_stream()  # (kept for get())
-        rc = self._native(*self._before, self._stream.cuda_stream, *self._after)
-        if rc != _lib.OK:
-            _lib.check(self._entry, rc)
-
     def get(self) -> List[Found]:
         """Synchronise the stream of the last call and return its results, one :class:`Found` per field (``RuntimeError`` before
         the first call)."""
-        if self._stream is None:
-            raise RuntimeError("LineFind.get: the object has not been called yet")
         self._wait()
         return [Found.from_rows(block, self.what) for block in self.result.tensor.cpu().numpy()]
 
@@ -177,10 +164,7 @@ class LineFind(Bound):
         rows = ROWS[:2] + (("crossings",) if self.what == "crossing" else ("value",))
         if name not in rows:
             raise ValueError(f"no section {name!r}: the rows of what={self.what!r} are {', '.join(rows)}")
-        entry = int(entry)
-        if not 0 <= entry < self._n:
-            raise IndexError(f"entry {entry} of {self._n}")
-        return self.result[entry, rows.index(name)].transpose()
+        return self.result[self._index(entry), rows.index(name)].transpose()
 
 
 def find_lines(*fields, axis="K", what: str = "crossing", level=None, direction: str = "any", reverse: bool = False, coord=None,
@@ -209,8 +193,5 @@ def find_lines(*fields, axis="K", what: str = "crossing", level=None, direction:
 
     Raises ``ValueError`` / ``TypeError`` (with the library's message) before any GPU work.  In a time loop build a
     :class:`LineFind` once instead."""
-    fields = list(fields[0]) if len(fields) == 1 and isinstance(fields[0], (tuple, list)) else list(fields)
-    frozen = LineFind(fields, axis=axis, what=what, level=level, direction=direction, reverse=reverse, coord=coord, missing=missing, halo=halo,
-                      origin=origin)
-    frozen()
-    return frozen.get()
+    return one_shot(LineFind, fields, axis=axis, what=what, level=level, direction=direction, reverse=reverse, coord=coord, missing=missing,
+                    halo=halo, origin=origin)

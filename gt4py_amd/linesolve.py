@@ -32,7 +32,7 @@ import ctypes
 from typing import Optional, Sequence
 
 from . import _lib
-from ._bound import AXES, FLAGS, STREAM, Bound, Out, _coefficient, _line_pairs, field_table, refuse_host_arrays  # noqa: F401 - AXES is public here
+from ._bound import AXES, FLAGS, STREAM, Bound, Out, _coefficient, _line_pairs, field_table  # noqa: F401 - AXES is public here
 from .storage.device_array import DeviceArray
 
 PATHS = {_lib.LINE_PATH_LANES: "lanes", _lib.LINE_PATH_TILES: "tiles", _lib.LINE_PATH_ITEMS: "items"}
@@ -52,8 +52,9 @@ class LineSolve(Bound):
     objects, not the arrays: it refuses to run once one of them has died."""
 
     _entry, _dry_run_bit = "gt4mi_line_solve", _lib.LINE_DRY_RUN
+    _workspace_ptr, _workspace_bytes = None, 0  # (until the first dry run has said how large the workspace is)
 
-    def _arguments(self) -> tuple:  # (no workspace until the first dry run has said how large it is)
+    def _arguments(self) -> tuple:
         lower, diag, upper = self._coefficients
         return (self._out, self._rhs, self._n, ctypes.byref(lower), ctypes.byref(diag), ctypes.byref(upper), self._extent3, self._axis,
                 self._size, FLAGS, self._workspace_ptr, self._workspace_bytes, STREAM, Out(ctypes.c_int64), Out(ctypes.c_int), Out(ctypes.c_int))
@@ -71,19 +72,16 @@ class LineSolve(Bound):
         self._extent3 = _lib.domain3(self.extent)
         self._axis, self._size = ax, o_arrays[0].itemsize
         self._flags = _lib.LINE_PERIODIC if self.periodic else 0
-        # every check of the library, nothing enqueued; also: the workspace the call needs, its path and how many kernels it makes
-        self._workspace_ptr, self._workspace_bytes = None, 0
-        needed, path, self.launches = self._dry_run()
-        self.path = PATHS.get(path)
         arrays = o_arrays + r_arrays + c_arrays
-        refuse_host_arrays("solve_lines", arrays)
-        import torch
 
-        first = o_arrays[0].tensor
-        #: the elimination factors of every line (and, for a periodic call, the closure's solution); private layout
-        self.workspace = DeviceArray(torch.empty(max(needed // self._size, 1), dtype=first.dtype, device=first.device))
-        self._workspace_ptr, self._workspace_bytes = self.workspace.ptr, needed
-        self._dry_run()  # (the workspace against every field)
+        def allocate(torch, device, outs):
+            #: the elimination factors of every line (and, for a periodic call, the closure's solution); private layout
+            self.workspace = DeviceArray(torch.empty(max(outs[0] // self._size, 1), dtype=o_arrays[0].tensor.dtype, device=device))
+            self._workspace_ptr, self._workspace_bytes = self.workspace.ptr, outs[0]
+
+        # the dry run says: the workspace the call needs, its path and how many kernels it makes
+        _, path, self.launches = self._own_buffers("solve_lines", arrays, allocate)
+        self.path = PATHS.get(path)
         self._bind("solve_lines", arrays, outs + rhss + [lower, diag, upper])
 
 

@@ -36,7 +36,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._bound import FLAGS, FLOATS, STREAM, Bound, Out, _as_list, _common_domain, _halo4, _origin3, field_table
+from ._bound import FLAGS, FLOATS, STREAM, BoundResult, Out, _as_list, _common_domain, _halo4, _origin3, field_table
 from .horizontal import METHODS
 from .storage.device_array import DeviceArray, as_device_array
 
@@ -48,7 +48,7 @@ def _list_field(a: DeviceArray) -> "_lib.Field":
     return _lib.Field.make(a.ptr, (a.shape[0], 1, 1), (a.strides[0], 0, 0), (0, 0, 0))
 
 
-class Sample(Bound):
+class Sample(BoundResult):
     """The frozen form of :func:`sample` (what ``FrozenStencil`` is for stencils): arguments are checked (through the library's dry
     run), the native descriptors and the result built ONCE; ``__call__()`` makes only the ctypes call, on the stream that is
     current THEN, and does not synchronise; :meth:`get` synchronises that stream and returns a numpy array.
@@ -135,30 +135,17 @@ class Sample(Bound):
         # every check of the library, nothing enqueued; also: how many kernels
         self.launches, = self._dry_run()
         self._bind("sample", arrays + p_arrays + [self.result], fields + positions + ([] if out is None else [out]))
-        self._stream = None
-
-    def __call__(self) -> None:
-        self._check_alive()
-        self._stream = self._current_stream()  # (kept for get())
-        rc = self._native(*self._before, self._stream.cuda_stream, *self._after)
-        if rc != _lib.OK:
-            _lib.check(self._entry, rc)
 
     def get(self) -> np.ndarray:
         """Synchronise the stream of the last call and return ``result`` as a numpy array (``RuntimeError`` before the first
         call)."""
-        if self._stream is None:
-            raise RuntimeError("Sample.get: the object has not been called yet")
         self._wait()
         return self.result.tensor.cpu().numpy()
 
     def column(self, n: int = 0) -> DeviceArray:
         """The device view of field ``n`` of ``result``: ``(npoints, nk)`` in column mode -- K contiguous --, ``(npoints,)`` in
         point mode.  It holds what the LAST call left there, in stream order."""
-        n = int(n)
-        if not 0 <= n < self._n:
-            raise IndexError(f"field {n} of {self._n}")
-        return self.result[n]
+        return self.result[self._index(n, "field")]
 
 
 def sample(fields, *, pos_i, pos_j, pos_k=None, method: str = "linear", outside: str = "clamp", fill_value: float = math.nan, halo=0,
