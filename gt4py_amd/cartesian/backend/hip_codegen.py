@@ -158,7 +158,17 @@ GT_DEV double gt_pow(double a, double b) {
     }
     return __ocml_pow_f64(a, b);
 }
-GT_DEV float gt_pow(float a, float b) { return __ocml_pow_f32(a, b); }
+// float: the same repeated multiplication in double, rounded once.  A power that is a float is exact at every step (its
+// factors have fewer bits); the device library's pow is a unit off there too (1.5f ** 4 = 0x1.440002p+2, not 5.0625).
+GT_DEV float gt_pow(float a, float b) {
+    if (b >= 1.0f && b <= 16.0f && b == __builtin_truncf(b) && (a - a) == 0.0f && a != 0.0f) {
+        double r = 1.0;
+        for (int n = (int)b; n > 0; --n) r *= (double)a;
+        const double m = __builtin_fabs(r);
+        if (m > 0x1p-126 && m < 0x1p127) return (float)r;
+    }
+    return __ocml_pow_f32(a, b);
+}
 template <class T> GT_DEV T gt_pow(T a, T b) {
     T r = 1;
     for (T n = 0; n < b; ++n) r *= a;
@@ -212,8 +222,17 @@ GT_OCML1(log)
 GT_OCML1(log10)
 GT_OCML1(cbrt)
 GT_MATH1(erf, __ocml_erf_f64, __ocml_erf_f32)
-GT_MATH1(erfc, __ocml_erfc_f64, __ocml_erfc_f32)
-GT_MATH1(gamma, __ocml_tgamma_f64, __ocml_tgamma_f32)
+// erfc and gamma: the device library's, with the CLASS of the result at the ends of the range the reference's (scipy.special),
+// where the two differ (tests/test_gpu_float_tables.py; device value, reference value):
+//   erfc, double: scipy gives 0 as soon as x * x > MAXLOG = log(DBL_MAX), x > 26.64, the device library subnormal numbers up to
+//                 x = 27.2 (erfc(27.0): 0x0.0000000019e0fp-1022, 0)
+//   erfc, float:  scipy rounds its double result, 0 from x = 0x1.41bbf8p+3 on, where the true value is below half of the smallest
+//                 subnormal (erfc(0x1.41bbf8p+3f): 0x1p-149, 0)
+//   gamma, double: scipy overflows from MAXGAM = 0x1.573fae561f647p+7 on, one number early (there: 0x1.ffffffffffe55p+1023, inf)
+GT_DEV double gt_erfc(double a) { return a * a > 0x1.62e42fefa39efp+9 && a > 0.0 ? 0.0 : __ocml_erfc_f64(a); }
+GT_DEV float gt_erfc(float a) { return a >= 0x1.41bbf8p+3f ? 0.0f : __ocml_erfc_f32(a); }
+GT_DEV double gt_gamma(double a) { return a >= 0x1.573fae561f647p+7 ? __builtin_inf() : __ocml_tgamma_f64(a); }
+GT_DEV float gt_gamma(float a) { return __ocml_tgamma_f32(a); }
 GT_MATH1(round, __builtin_rint, __builtin_rintf)  // ties to even, like np.round / std::nearbyint
 // ties away from zero the way the reference's numpy backend spells it (gtc/ufuncs.py:31-33)
 GT_DEV double gt_round_away_from_zero(double a) { return __builtin_copysign(__builtin_floor(__builtin_fabs(a) + 0.5), a); }
